@@ -12,7 +12,10 @@ DUST2_LAMBERT_FOG (= Renderer.cs:830-860), CullMode.Back, DepthTest.LessEqual, B
 At N>1 the same frame is sharded by tile rows (one band per rank, no collective while rendering)
 and the colour bands are gathered to rank 0 over RCCL each step: strong scaling.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps frames, writes
+the last frame with --dump-outputs DIR and prints the line; --full adds what takes runs of its own: hipEvents in the timed region,
+the one-stream kernel pass and stage breakdown behind it (`roofline`, `ms_per_step_unpipelined`) and the CPU baseline
+(`cpu_baseline`).
 """
 import argparse
 import json
@@ -26,6 +29,9 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 HBM_MEASURED_GBS = 6290.0
 BYTES_PER_WRITTEN_FRAGMENT = 20  # 16 B float4 colour + 4 B float depth
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: frames up to this size in all are written whole ...
+DUMP_SAMPLE_PIXELS = 1 << 20     # ... larger ones as this many pixel positions, drawn once with a fixed seed
+DUMP_SEED = 12345
 
 
 def build_scene(name, args):
@@ -50,13 +56,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--prime", type=int, default=32, help="untimed setup frames before warmup (runtime/buffer initialisation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: hipEvents around the raster kernel in the timed region, a "
+                         "one-stream pass and a per-stage breakdown behind it (roofline, ms_per_step_unpipelined) and, at N=1, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last step as DIR/<name>.npy (float32): colour and depth at N=1, "
+                         "rank 0's gathered colour at N>1; whole if at most 64 MB, else a fixed seeded sample of pixels (+ pixel_index)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--bilinear", action="store_true",
                     help="cfg3 through the BUILD-DEFINED bilinear texture filter (4 texel gathers per fragment) instead of the reference's "
                          "nearest filter (Texture.cs:43-63); parity is against the build's own oracle definition only")
     ap.add_argument("--fake-world", type=int, default=0,
                     help="self-test of the N>1 code path in ONE process: act as rank 0 of N, collectives stubbed (numbers are meaningless)")
-    ap.add_argument("--no-profile-events", action="store_true", help="do not record hipEvents around kernels in the timed region")
+    ap.add_argument("--no-profile-events", action="store_true", help="--full without hipEvents around kernels (and without the passes behind the timed region)")
     ap.add_argument("--gather", choices=["rgb32f", "rgba32f", "p2p"], default="rgb32f",
                     help="N>1: what reaches rank 0 per frame and how -- rgb32f = the present payload of MainWindow.OnRender "
                          "(Vector4 -> Vector3 flatten, 12 B/pixel) by an RCCL gather, rgba32f = the raw colour buffer (16 B/pixel) "
@@ -84,6 +96,8 @@ def main():
                          "flag on the GPU, record_stream, checkpoint / resend: the RCCL leg rehearsed on the one GPU of a test box")
     ap.add_argument("--print-src-hash", action="store_true", help="print the kernel-source hash (tools/profile_round.sh) and exit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.print_src_hash:
         print(kernel_source_hash())
         return
@@ -101,6 +115,7 @@ def main():
     if args.force_dist and args.gather == "p2p":
         raise SystemExit("--force-dist rehearses the RCCL gather modes (a process cannot open its own IPC handle): use rgb32f or rgba32f")
     dist_on = world > 1 or args.force_dist          # the multi-GPU code path (bands, band buffers, gather, checkpoints)
+    profile = args.full and not args.no_profile_events
 
     import torch                      # plumbing: device memory for the bands, streams, RCCL
     import torch.distributed as dist
@@ -315,11 +330,13 @@ def main():
     for _ in range(max(args.prime, 1) if args.pipelining else 0):
         step()
     barrier()
+    # the prime may run longer by wall time: a camera-jitter sequence restarts here, so the timed frames are the same in every run
+    state["frame_no"] = 0
     for _ in range(args.warmup):
         step()
     barrier()
     dev.reset_stats()
-    if not args.no_profile_events:
+    if profile:
         dev.profile_reset()
         # hipEvents around the dominant kernel, on the stream it is launched on: on EVERY launch of a short timed region (the driver's
         # 20 steps: a mean of 5 samples moved by 7 % between two passes of one run), on every 4th launch of a long one (an event pair
@@ -333,12 +350,19 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     render_s = 1e-3 * sum(a.elapsed_time(b) for a, b in state["ev"]) if dist_on else 0.0
-    prof = dev.profile() if not args.no_profile_events else None
-    samples = np.sort(dev.raster_samples()) if not args.no_profile_events else None
+    prof = dev.profile() if profile else None
+    samples = np.sort(dev.raster_samples()) if profile else None
     st = dev.stats()
+    if args.dump_outputs and rank == 0:
+        if dist_on:
+            frames = {"color": frame_t.cpu().numpy()}                 # what rank 0 holds: the gathered frame
+        else:
+            color, depth = window._read(True, True)                     # what SceneRenderer.render() hands its caller
+            frames = {"color": color, "depth": depth}
+        dump_outputs(args.dump_outputs, frames, np)
     stage_ms = None
     isolated = None
-    if not args.no_profile_events:
+    if profile:
         # OUTSIDE the timed region, frames NOT in flight (one stream: a kernel has the chip to itself, which is what a kernel's
         # roofline is quoted on): (1) the raster kernel of every launch of as many frames as were timed, and the frame time,
         # (2) a per-stage breakdown from a few frames with events around every stage
@@ -479,7 +503,7 @@ def main():
                 out["roofline"]["valu_floor"] = vf
         if isolated is not None:
             out["ms_per_step_unpipelined"] = isolated["ms_per_step_unpipelined"]
-        if not dist_on and not args.no_cpu_baseline:
+        if args.full and not dist_on and not args.no_cpu_baseline:
             renderer.jitter_views(0, 0.0)              # the comparison frame is the unperturbed one
             out["cpu_baseline"] = cpu_baseline(scene, renderer, np)
         print(json.dumps(out), flush=True)
@@ -490,6 +514,23 @@ def main():
     dev.close()
     if dist_on and not args.fake_world:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, frames, np):
+    """--dump-outputs: `frames` (name -> float32 array of H x W [x C]) as out_dir/<name>.npy.  Whole when they hold at most
+    DUMP_MAX_BYTES together; otherwise the same DUMP_SAMPLE_PIXELS pixel positions of each (seeded, sorted), as rows of
+    <name>.npy, and their flat indices y * W + x as pixel_index.npy (float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    if sum(a.nbytes for a in frames.values()) <= DUMP_MAX_BYTES:
+        for name, a in frames.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        return
+    h, w = next(iter(frames.values())).shape[:2]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, min(DUMP_SAMPLE_PIXELS, h * w), replace=False))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    for name, a in frames.items():
+        rows = a.reshape(h * w, -1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(rows[:, 0] if a.ndim == 2 else rows, dtype=np.float32))
 
 
 def launch_ranks_if_needed(args, argv, run=None):

@@ -139,3 +139,27 @@ def test_multi_gpu_model_predicts_from_the_committed_single_gpu_stage_times():
         assert m["front_ms"] > m["raster_ms"] * 0 and (prev is None or m["render_ms"] < prev)   # rendering scales, the replicated front end does not
         prev = m["render_ms"]
     assert bench.multi_gpu_model("cfg2", 2, 1080, 1920, 3)["render_ms"] is None          # no committed single-GPU line of that config: gather only
+
+
+def test_bench_dump_outputs_whole_or_one_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float32 frames written whole while they fit the budget, else the same seeded pixel positions of
+    each (sorted flat indices in pixel_index.npy), identical from call to call."""
+    bench = _bench_module()
+    rng = np.random.default_rng(4)
+    color = rng.standard_normal((48, 64, 4)).astype(np.float32)
+    depth = rng.standard_normal((48, 64)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), {"color": color, "depth": depth}, np)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["color.npy", "depth.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "color.npy"), color)
+    assert np.array_equal(np.load(tmp_path / "whole" / "depth.npy"), depth)
+    bench.DUMP_MAX_BYTES, bench.DUMP_SAMPLE_PIXELS = 1024, 100
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"color": color, "depth": depth}, np)
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and idx.shape == (100,) and np.all(np.diff(idx) > 0) and idx[-1] < 48 * 64
+    k = idx.astype(np.int64)
+    c, z = np.load(tmp_path / "a" / "color.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert c.dtype == z.dtype == np.float32 and c.shape == (100, 4) and z.shape == (100,)
+    assert np.array_equal(c, color.reshape(-1, 4)[k]) and np.array_equal(z, depth.reshape(-1)[k])
+    for f in ("pixel_index.npy", "color.npy", "depth.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -17,5 +17,5 @@ for t in 1 4 8; do
   SWR_AB_TPW=$t timeout -k 10 200 python tools/ab/stages.py softwarerenderer_amd/libswr_hip_ab.so cfg2 2>&1 | tail -1 | sed "s/^/tpw=$t /" | tee -a $OUT || exit 1
 done
 for t in 1 4 8; do
-  SWR_LIB=libswr_hip_ab.so SWR_AB_TPW=$t timeout -k 10 300 python bench.py --steps 30 --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('bench tpw=$t', d['ms_per_step'], d.get('ms_per_step_unpipelined'), d['roofline']['kernel_ms'])" | tee -a $OUT || exit 1
+  SWR_LIB=libswr_hip_ab.so SWR_AB_TPW=$t timeout -k 10 300 python bench.py --full --steps 30 --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('bench tpw=$t', d['ms_per_step'], d.get('ms_per_step_unpipelined'), d['roofline']['kernel_ms'])" | tee -a $OUT || exit 1
 done
