@@ -85,7 +85,7 @@ namespace SoftwareRenderer
 
     public enum SwrProgram { FlatColor = 0, Gouraud = 1, Dust2LambertFog = 2, Phong4Point = 3, DebugVaryings = 4 }
 
-    // ---------------------------------------------------------------- the 59 entry points ----
+    // ---------------------------------------------------------------- the 63 entry points ----
     // Shaders.VertexInput (Shaders.cs:10-24) IS swr_vertex: four sequential System.Numerics fields, 48 bytes, blittable.
     // Matrix4x4 is 16 sequential floats M11..M44 (row-major, row-vector convention): passed by address, no marshalling.
     internal static unsafe class Native
@@ -150,6 +150,11 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_device_name(IntPtr ctx, byte* buf, int buflen);
         [DllImport(Lib)] public static extern int swr_selftest_division(IntPtr ctx, ulong samples, ulong seed, ulong* out8);
         [DllImport(Lib)] public static extern int swr_debug_counters(IntPtr ctx, ulong* out8);
+        // user fragment programs (a Shaders.FragmentShader restated in C++, see ShaderMap.Register)
+        [DllImport(Lib)] public static extern int swr_program_create(IntPtr ctx, byte* fragmentSource, out int programId);
+        [DllImport(Lib)] public static extern int swr_program_destroy(IntPtr ctx, int programId);
+        [DllImport(Lib)] public static extern int swr_program_set_constants(IntPtr ctx, int programId, float* values, int n);
+        [DllImport(Lib)] public static extern int swr_program_validate(byte* fragmentSource, byte* log, int logLen);
     }
 
     // ---------------------------------------------------------------- numerics probe ----
@@ -358,15 +363,52 @@ namespace SoftwareRenderer
     // Delegates cannot cross the ABI.  The application has exactly one shader pair (Renderer.VertexShader and the lambda
     // `input => FragmentShader(input, texture)`, Renderer.cs:450-459,830-860): it is recognised by its methods, and the
     // fields it closes over -- the Renderer's light / fog fields (Renderer.cs:39-44) and the captured Texture -- are read
-    // through reflection, so Renderer.cs needs no edit.  Anything else returns false (managed path).
-    static class ShaderMap
+    // through reflection, so Renderer.cs needs no edit.  A fragment method registered with its C++ restatement (Register, the
+    // porting guide in INTEGRATION.md) resolves to a user program compiled into the raster kernel.  Anything else returns false
+    // (managed path).
+    public static class ShaderMap
     {
         static readonly BindingFlags Any = BindingFlags.Instance | BindingFlags.Public | BindingFlags.NonPublic;
+        static readonly Dictionary<MethodInfo, string> sources = new Dictionary<MethodInfo, string>();
+        static readonly Dictionary<MethodInfo, int> programs = new Dictionary<MethodInfo, int>();
+
+        // `method`'s body restated against the contract of swr.h (swr_fragment).  Checked at once (swr_program_validate: a compile
+        // error throws ArgumentException with the compiler's log); compiled for the context on first use.  Delegates are matched by
+        // their method: register the delegate the application hands to RenderMesh (for Renderer.cs:450-459, the lambda
+        // `input => FragmentShader(input, texture)`; its closure's Texture is passed on as the draw's texture).
+        public static unsafe void Register(Shaders.FragmentShader method, string source)
+        {
+            byte[] src = System.Text.Encoding.UTF8.GetBytes(source + "\0");
+            byte[] log = new byte[16384];
+            int rc;
+            fixed (byte* s = src) fixed (byte* l = log) rc = Native.swr_program_validate(s, l, log.Length);
+            if (rc == -1) throw new ArgumentException(System.Text.Encoding.UTF8.GetString(log).TrimEnd('\0'));
+            if (rc != 0) throw new NotSupportedException($"swr_program_validate: {rc}");
+            lock (sources) { sources[method.Method] = source; programs.Remove(method.Method); }
+        }
+
+        static unsafe bool TryUserProgram(Shaders.FragmentShader fs, out int id)
+        {
+            id = 0;
+            if (fs == null) return false;
+            lock (sources)
+            {
+                MethodInfo m = fs.Method;
+                if (!sources.TryGetValue(m, out string source)) return false;
+                if (programs.TryGetValue(m, out id)) return true;
+                byte[] src = System.Text.Encoding.UTF8.GetBytes(source + "\0");
+                fixed (byte* s = src) SwrContext.Check(Native.swr_program_create(SwrContext.Handle, s, out id));
+                programs[m] = id;
+                return true;
+            }
+        }
 
         public static bool TryResolve(Shaders.VertexShader vs, Shaders.FragmentShader fs, out SwrProgram program, out SwrUniforms uniforms, out IntPtr texture)
         {
             program = SwrProgram.Dust2LambertFog; uniforms = default; texture = IntPtr.Zero;
             if (vs?.Target is not Renderer renderer || vs.Method.Name != "VertexShader") return false;
+            bool user = TryUserProgram(fs, out int userId);
+            if (user) program = (SwrProgram)userId;                                // ids >= SWR_PROG_USER_BASE (256)
             object closure = fs?.Target;
             if (closure == null) return false;
             Texture captured = null;
@@ -377,7 +419,7 @@ namespace SoftwareRenderer
                 if (v is Texture t) captured = t;
                 if (ReferenceEquals(v, renderer)) sameRenderer = true;
             }
-            if (!sameRenderer) return false;                                   // a fragment lambda of some other object
+            if (!sameRenderer && !user) return false;                          // a fragment lambda of some other object
             uniforms.LightDirection = Get<Vector3>(renderer, "LightDirection");
             uniforms.LightColor = Get<Vector4>(renderer, "LightColor");
             uniforms.FogColor = Get<Vector4>(renderer, "FogColor");

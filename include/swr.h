@@ -27,7 +27,10 @@
 #ifndef SWR_H
 #define SWR_H
 
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
+#include <stddef.h>
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -68,6 +71,9 @@ enum {
                                      * Rasterizer.Interpolate delivers them -- (ScreenCoords.x + Normal.x, ScreenCoords.y + Normal.y,
                                      * Barycentric.x + Normal.z, Barycentric.y + 0.5); Rasterizer.cs:390,598-613,638 */
 };
+/* USER fragment programs (any Shaders.FragmentShader delegate, restated in C++): swr_program_create compiles one at run time into
+ * the raster kernel and returns an id >= SWR_PROG_USER_BASE, which the render calls accept as `program`. */
+#define SWR_PROG_USER_BASE 256
 
 /* Shaders.VertexInput, Shaders.cs:10-24 -- 48 bytes, identical memory layout */
 typedef struct swr_vertex {
@@ -252,6 +258,30 @@ int  swr_render_mesh_culled(swr_context* ctx, const swr_mesh* mesh,
                             const float model[16], const float view[16], const float projection[16],
                             int program, const swr_uniforms* uniforms, const swr_texture* texture,
                             int cull_mode, int depth_test, int blend_mode);
+/* User fragment programs --------------------------------------------------------------------------------------------------------
+ * Source contract (softwarerenderer_amd/csrc/swr_program.hip.h is the prelude compiled in front of the text; INTEGRATION.md has a
+ * porting guide): the text defines
+ *     __device__ float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
+ * `in` = Shaders.VertexOutput after Rasterizer.Interpolate (Rasterizer.cs:566-640): clip_position, color, tex_coord, normal,
+ * screen_coords, barycentric, world_normal (Data["WorldNormal"]); the vertex stage is Renderer.VertexShader (Renderer.cs:830-846,
+ * Interpolate = true).  `env` = the draw's uniforms, constants[64], the pixel x, y; helpers swr_sample (Texture.Sample), swr_has_texture,
+ * swr_dot3, swr_lerp (this library's System.Numerics model), swr_max, swr_clamp (MathF.Max, Math.Clamp), swr_discard() (a null
+ * result: W <= 0 or NaN writes nothing, Rasterizer.cs:511).  Compiled with this library's switches and its numerics model; the
+ * program is inlined into the raster kernel.
+ * A batch holds the draws of one program: switching to, from or between user programs flushes (as SWR_PROG_DEBUG_VARYINGS does).
+ * DebugMode.Wireframe with a user program is SWR_ERR_UNSUPPORTED.  `uniforms` may be NULL for a user program (it reads zeros). */
+/* compile for this context's device: *program_id >= SWR_PROG_USER_BASE.  Compile error -> SWR_ERR_INVALID_ARG with the compiler's
+ * log in swr_last_error(ctx); run-time compiler (libhiprtc) not loadable -> SWR_ERR_UNSUPPORTED */
+int  swr_program_create(swr_context* ctx, const char* fragment_source, int* program_id);
+/* the id stops being valid for new draws; draws already recorded still render with the program */
+int  swr_program_destroy(swr_context* ctx, int program_id);
+/* up to 64 floats the program reads as env.constants[i] (the rest read 0).  A draw takes a copy when it is RECORDED, as a C# closure
+ * captures its fields: later calls do not change recorded draws */
+int  swr_program_set_constants(swr_context* ctx, int program_id, const float* values, int n);
+/* compile only, without a context or a device: SWR_OK, SWR_ERR_INVALID_ARG (log = compiler messages, NUL-terminated, truncated to
+ * log_len) or SWR_ERR_UNSUPPORTED */
+int  swr_program_validate(const char* fragment_source, char* log, int log_len);
+
 int  swr_flush(swr_context* ctx);    /* execute recorded draws (asynchronous on the stream) */
 int  swr_sync(swr_context* ctx);     /* flush + wait for the stream */
 /* Frames in flight.  The reference's loop renders frames back to back (Renderer.cs:404-419: RenderScene per frame; Rasterizer.cs:

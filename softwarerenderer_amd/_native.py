@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("SWR_LIB", "") or "libswr_hip.so"))
 
 SWR_OK = 0
+SWR_PROG_USER_BASE = 256     # ids of user fragment programs (swr_program_create) are >= this
 SWR_ABI_EXPECTED = 3
 SWR_ERR_INVALID_ARG = -1
 SWR_ERR_HIP = -2
@@ -71,6 +72,7 @@ EXPORTS = [
     "swr_mesh_create", "swr_mesh_destroy", "swr_set_state", "swr_initialize_tile_locks", "swr_render_mesh",
     "swr_render_mesh_arrays", "swr_mesh_bounds", "swr_is_sphere_in_frustum", "swr_render_mesh_culled", "swr_flush", "swr_sync", "swr_interpolate", "swr_get_stats", "swr_reset_stats",
     "swr_profile_enable", "swr_profile_get", "swr_profile_reset", "swr_profile_raster_samples", "swr_device_name", "swr_debug_counters", "swr_selftest_division",
+    "swr_program_create", "swr_program_destroy", "swr_program_set_constants", "swr_program_validate",
 ]
 
 _libs = {}
@@ -150,6 +152,10 @@ def load(name: str = None) -> C.CDLL:
         "swr_device_name": (I, [P, C.c_char_p, I]),
         "swr_debug_counters": (I, [P, C.POINTER(C.c_uint64)]),
         "swr_selftest_division": (I, [P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "swr_program_create": (I, [P, C.c_char_p, C.POINTER(I)]),
+        "swr_program_destroy": (I, [P, I]),
+        "swr_program_set_constants": (I, [P, I, fp, I]),
+        "swr_program_validate": (I, [C.c_char_p, C.c_char_p, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -48,14 +48,25 @@ public:
     void Sync() const { check(swr_sync(ctx_)); }
     swr_stats Stats() const { swr_stats s; check(swr_get_stats(ctx_, &s)); return s; }
     void ResetStats() const { check(swr_reset_stats(ctx_)); }
+    // user fragment programs (contract in swr.h): compile errors throw std::invalid_argument carrying the compiler's log
+    int CompileProgram(const std::string& source) const { int id = 0; check(swr_program_create(ctx_, source.c_str(), &id)); return id; }
+    void DestroyProgram(int id) const { check(swr_program_destroy(ctx_, id)); }
+    void SetProgramConstants(int id, const std::vector<float>& values) const {
+        check(swr_program_set_constants(ctx_, id, values.empty() ? nullptr : values.data(), (int)values.size()));
+    }
 private:
     swr_context* ctx_ = nullptr;
 };
 
+class Texture;
+struct ShaderProgram;
 struct Shaders {
     using VertexInput = swr_vertex;           // Shaders.cs:10-24, 48 bytes
     enum class Program { FlatColor = SWR_PROG_FLAT_COLOR, Gouraud = SWR_PROG_GOURAUD,
                          Dust2LambertFog = SWR_PROG_DUST2_LAMBERT_FOG, Phong4Point = SWR_PROG_PHONG_4POINT };
+    // any Shaders.FragmentShader restated in C++ against the contract of swr.h, compiled for `dev` (a user program)
+    static ShaderProgram Custom(const Device& dev, const std::string& source, const swr_uniforms& uniforms = swr_uniforms{},
+                                const Texture* texture = nullptr, std::vector<float> constants = {});
 };
 static_assert(sizeof(Shaders::VertexInput) == 48, "VertexInput must match Shaders.cs:10-24");
 
@@ -79,10 +90,19 @@ private:
 };
 
 struct ShaderProgram {                        // stands in for (VertexShader, FragmentShader), Shaders.cs:97-98
-    Shaders::Program program = Shaders::Program::Gouraud;
+    Shaders::Program program = Shaders::Program::Gouraud;   // a built-in, or a user program id (>= SWR_PROG_USER_BASE)
     swr_uniforms uniforms{};
     const Texture* texture = nullptr;
+    std::vector<float> constants;             // user programs: set before each draw (each draw captures them when recorded)
 };
+
+inline ShaderProgram Shaders::Custom(const Device& dev, const std::string& source, const swr_uniforms& uniforms,
+                                     const Texture* texture, std::vector<float> constants) {
+    ShaderProgram p;
+    p.program = static_cast<Shaders::Program>(dev.CompileProgram(source));
+    p.uniforms = uniforms; p.texture = texture; p.constants = std::move(constants);
+    return p;
+}
 
 inline swr_uniforms DefaultUniforms() {      // Renderer.cs:39-44
     swr_uniforms u{};
@@ -137,6 +157,7 @@ public:
                            BlendMode blendMode = BlendMode::Alpha) {
         const Device& d = window.device();
         d.check(swr_set_state(d.ctx(), NearClip, FarClip, (int)RenderDebugMode));
+        if ((int)shader.program >= SWR_PROG_USER_BASE) d.SetProgramConstants((int)shader.program, shader.constants);
         d.check(swr_render_mesh_arrays(d.ctx(), vertices.data(), (int)vertices.size(), indices.data(), (int)indices.size(),
                                        model.data(), view.data(), projection.data(), (int)shader.program, &shader.uniforms,
                                        shader.texture ? shader.texture->handle() : nullptr,

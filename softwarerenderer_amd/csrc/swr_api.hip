@@ -15,6 +15,8 @@
 // (batch_poisoned in swr_device.h).  The framebuffer is touched by the raster stream only, so everything a caller orders against
 // `stream` (flatten, read-back, collectives) still sees frames in submission order.
 #include <hip/hip_runtime.h>
+#include <hip/hiprtc.h>            // (types only: the run-time compiler is loaded with dlopen, see RtcLib)
+#include <dlfcn.h>
 
 #include <algorithm>
 #include <cstddef>
@@ -22,9 +24,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
+#if defined(SWR_RTC_FLAGS)
+#include "swr_rtc_sources.inc"     // the headers user fragment programs compile against (Makefile: RTC_INC)
+#endif
 
 #include "swr.h"
 #include "swr_device.h"
@@ -35,6 +42,9 @@
 #include "swr_cull.hip.h"
 
 using namespace swr;
+
+#define SWR_STR2(x) #x
+#define SWR_STR(x) SWR_STR2(x)
 
 struct swr_mesh {
     float4* d_bounds = nullptr;               // Mesh.SphereBounds (ModelLoader.cs:291), computed on first use
@@ -92,10 +102,23 @@ struct RasterSet {
     bool raster_pending = false;      // raster_done has been recorded and the stream has not been drained since
 };
 
+// A user fragment program loaded on the context's device (swr_program_create): the two k_raster_c<SWR_PROG_CUSTOM> instantiations
+// (with / without BlendMode.None's row early-out) of its run-time compiled code object.  Shared by the context's table and every
+// recorded or in-flight draw that uses it: the module is unloaded when the last of them lets go, and a batch only lets go once its
+// kernels are known to be over (retire_batch / free_garbage).
+struct UserProg {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn[2] = { nullptr, nullptr };     // [EARLYOUT]
+    float constants[64] = {};                        // swr_program_set_constants: copied into each draw when it is recorded
+    ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
+};
+
 struct DrawCmd {
     DrawParams p;
     swr_mesh* mesh;
     bool frustum_cull = false;                 // render only if IsSphereInFrustum(mesh bounds, model, view, proj)
+    std::shared_ptr<UserProg> prog;            // user programs only: the program ...
+    std::shared_ptr<const std::vector<float>> uconsts;   // ... and its 64 constants as they were when the draw was recorded
 };
 
 // one flush = one batch; kept until the host has seen that it fitted (optimistic execution, see swr::Ctrl)
@@ -150,6 +173,9 @@ struct swr_context {
     std::vector<DrawCmd> draws;
     uint64_t pend_verts = 0, pend_tris = 0;
     std::vector<swr_mesh*> garbage;           // transient meshes no recorded draw needs any more, possibly still read by kernels in flight
+    std::map<int, std::shared_ptr<UserProg>> progs;     // live user programs by id (swr_program_create / _destroy)
+    int next_prog = SWR_PROG_USER_BASE;
+    std::vector<std::shared_ptr<UserProg>> prog_garbage; // programs of retired batches whose kernels may still run (see garbage)
     std::vector<swr_mesh*> mesh_pool;         // transient meshes whose batches are KNOWN to be complete: their device buffers are handed to the
     size_t mesh_pool_bytes = 0;               // next swr_render_mesh_arrays call instead of hipFree / hipMalloc (both synchronise the device)
     uint64_t stale_dropped[2] = { 0, 0 };     // present tickets dropped by back-pressure whose pixels predate a replay (swr_present_wait reports them)
@@ -200,6 +226,137 @@ namespace {
     } while (0)
 
 int fail(swr_context* c, int code, const char* msg) { c->err = msg; return code; }
+
+// ---- user fragment programs: the run-time compiler ------------------------------------------------------------------------------
+// hiprtc is opened with dlopen on first use, not linked: a machine without it loads this library as before, and the program entry
+// points answer SWR_ERR_UNSUPPORTED.
+struct RtcLib {
+    bool ok = false;
+    std::string why;
+    decltype(&hiprtcCreateProgram) create = nullptr;
+    decltype(&hiprtcDestroyProgram) destroy = nullptr;
+    decltype(&hiprtcAddNameExpression) add_name = nullptr;
+    decltype(&hiprtcCompileProgram) compile = nullptr;
+    decltype(&hiprtcGetLoweredName) lowered = nullptr;
+    decltype(&hiprtcGetProgramLogSize) log_size = nullptr;
+    decltype(&hiprtcGetProgramLog) log = nullptr;
+    decltype(&hiprtcGetCodeSize) code_size = nullptr;
+    decltype(&hiprtcGetCode) code = nullptr;
+};
+const RtcLib& rtc_lib() {
+    static const RtcLib lib = [] {
+        RtcLib r;
+#if !defined(SWR_RTC_FLAGS)
+        r.why = "this build carries no kernel sources for run-time compilation (built without the Makefile's SWR_RTC_FLAGS)";
+        return r;
+#else
+        std::vector<std::string> names = { "libhiprtc.so", "libhiprtc.so.7" };
+        if (const char* rp = getenv("ROCM_PATH")) names.push_back(std::string(rp) + "/lib/libhiprtc.so");
+        names.push_back("/opt/rocm/lib/libhiprtc.so");
+        void* h = nullptr;
+        for (auto& n : names) if ((h = dlopen(n.c_str(), RTLD_NOW | RTLD_LOCAL))) break;
+        if (!h) { r.why = "the HIP run-time compiler (libhiprtc.so) cannot be loaded"; return r; }
+        bool all = true;
+        auto sym = [&](auto& fp, const char* name) { fp = reinterpret_cast<std::remove_reference_t<decltype(fp)>>(dlsym(h, name)); all = all && fp; };
+        sym(r.create, "hiprtcCreateProgram"); sym(r.destroy, "hiprtcDestroyProgram"); sym(r.add_name, "hiprtcAddNameExpression");
+        sym(r.compile, "hiprtcCompileProgram"); sym(r.lowered, "hiprtcGetLoweredName"); sym(r.log_size, "hiprtcGetProgramLogSize");
+        sym(r.log, "hiprtcGetProgramLog"); sym(r.code_size, "hiprtcGetCodeSize"); sym(r.code, "hiprtcGetCode");
+        if (!all) { r.why = "libhiprtc.so lacks an entry point this library needs"; return r; }
+        r.ok = true;
+        return r;
+#endif
+    }();
+    return lib;
+}
+
+struct RtcCode { std::vector<char> code; std::string names[2]; };   // code object + mangled k_raster_c<SWR_PROG_CUSTOM> names [EARLYOUT]
+
+// Compiles a user fragment program into a gfx950 code object: SWR_OK, SWR_ERR_INVALID_ARG (log = the compiler's messages) or
+// SWR_ERR_UNSUPPORTED.  In-process cache keyed by the source (the switches are this library's own).
+int rtc_compile(const char* user_src, std::shared_ptr<const RtcCode>& out, std::string& log) {
+    const RtcLib& R = rtc_lib();
+    if (!R.ok) { log = R.why; return SWR_ERR_UNSUPPORTED; }
+#if defined(SWR_RTC_FLAGS)
+    static std::mutex mu;
+    static std::map<std::string, std::shared_ptr<const RtcCode>> cache;
+    const std::string key(user_src);
+    {
+        std::lock_guard<std::mutex> g(mu);
+        auto it = cache.find(key);
+        if (it != cache.end()) { out = it->second; return SWR_OK; }
+    }
+    // prelude (contract + helpers), the user's text under its own file name, then the kernel
+    const std::string src = std::string("#include \"swr_program.hip.h\"\n#line 1 \"fragment.hip\"\n") + user_src +
+                            "\n#line 1 \"swr_program_kernel\"\n#include \"swr_raster_c.hip.h\"\n";
+    // the Makefile's code-generation switches, this build's System.Numerics model, and the fenced LDS hand-offs (the unfenced ones are
+    // verified per (hipcc, source) pair only, DESIGN.md section 8: a run-time compiled kernel is not that pair)
+    std::vector<std::string> opts;
+    {
+        const std::string f = SWR_RTC_FLAGS;
+        size_t i = 0;
+        while (i < f.size()) {
+            const size_t j = f.find(' ', i);
+            const std::string o = f.substr(i, j == std::string::npos ? std::string::npos : j - i);
+            if (!o.empty()) opts.push_back(o);
+            if (j == std::string::npos) break;
+            i = j + 1;
+        }
+    }
+    opts.push_back("-DSWR_RTC_PROGRAM=1");
+    opts.push_back("-DSWR_WAVE_LDS_FENCE=1");
+    opts.push_back("-DSWR_NUMERICS_FMA=" SWR_STR(SWR_NUMERICS_FMA));
+    opts.push_back("-DSWR_DOT_PAIRWISE=" SWR_STR(SWR_DOT_PAIRWISE));
+    std::vector<const char*> copts;
+    for (auto& o : opts) copts.push_back(o.c_str());
+    const std::string expr[2] = { "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, false>",
+                                  "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, true>" };
+    hiprtcProgram prog = nullptr;
+    if (R.create(&prog, src.c_str(), "swr_user_program.hip", k_rtc_n_headers, k_rtc_headers, k_rtc_header_names) != HIPRTC_SUCCESS) {
+        log = "hiprtcCreateProgram failed";
+        return SWR_ERR_UNSUPPORTED;
+    }
+    for (auto& e : expr) R.add_name(prog, e.c_str());
+    const hiprtcResult cr = R.compile(prog, (int)copts.size(), copts.data());
+    size_t ls = 0;
+    log.clear();
+    if (R.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
+        log.resize(ls);
+        if (R.log(prog, &log[0]) != HIPRTC_SUCCESS) log.clear();
+        while (!log.empty() && log.back() == '\0') log.pop_back();
+    }
+    auto code = std::make_shared<RtcCode>();
+    bool ok = cr == HIPRTC_SUCCESS;
+    for (int k = 0; ok && k < 2; ++k) {
+        const char* mangled = nullptr;
+        ok = R.lowered(prog, expr[k].c_str(), &mangled) == HIPRTC_SUCCESS && mangled;
+        if (ok) code->names[k] = mangled;
+    }
+    size_t cs = 0;
+    ok = ok && R.code_size(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
+    if (ok) { code->code.resize(cs); ok = R.code(prog, code->code.data()) == HIPRTC_SUCCESS; }
+    R.destroy(&prog);
+    if (ok) {
+        // tools/custom_program_numbers.py: the code object as compiled, for its resource usage (never set in production)
+        if (const char* dir = getenv("SWR_PROGRAM_DUMP_DIR")) {
+            const std::string path = std::string(dir) + "/swr_user_program_" + std::to_string(std::hash<std::string>()(key)) + ".co";
+            if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(code->code.data(), 1, code->code.size(), f); fclose(f); }
+        }
+    }
+    if (!ok) {
+        if (log.empty()) log = "the fragment program did not compile";
+        return SWR_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> g(mu);
+    out = cache.emplace(key, std::shared_ptr<const RtcCode>(code)).first->second;
+    return SWR_OK;
+#else
+    (void)user_src; (void)out;
+    return SWR_ERR_UNSUPPORTED;
+#endif
+}
+
+// the batch has kernels of its own (DEBUG_VARYINGS or ONE user program): 0 for every other built-in program
+int kernel_class(int program) { return program == SWR_PROG_DEBUG_VARYINGS || program >= SWR_PROG_USER_BASE ? program : 0; }
 
 int ensure(swr_context* c, DevBuf& b, size_t bytes, bool zero_new = false) {
     if (bytes <= b.cap) return SWR_OK;
@@ -368,6 +525,7 @@ void pool_mesh(swr_context* c, swr_mesh* m) {
 void free_garbage(swr_context* c) {       // streams must be idle: nothing in flight reads the garbage any more
     for (swr_mesh* m : c->garbage) pool_mesh(c, m);
     c->garbage.clear();
+    c->prog_garbage.clear();
     trim_mesh_pool(c);
 }
 
@@ -421,10 +579,29 @@ int ensure_front_stream(swr_context* c) {
 }
 
 enum { MODE_SYNC = 0, MODE_ASYNC = 1 };
-static bool b_has_debug_varyings(const Batch& b) {
-    for (auto& d : b.draws) if (d.p.program == SWR_PROG_DEBUG_VARYINGS) return true;
+// byte offset of the captured constants (64 floats per draw) in a user-program batch's upload block: behind the draws, block maps,
+// bounds pointers and visibility words (execute_batch lays them out the same way)
+static size_t user_consts_offset(const Batch& b) {
+    const size_t nd = b.draws.size();
+    size_t nv = 0, nt = 0;
+    bool any_cull = false;
+    for (auto& d : b.draws) {
+        nv += (d.p.n_verts + SWR_GEOM_BLOCK - 1) / SWR_GEOM_BLOCK; nt += (d.p.n_tris + SWR_GEOM_BLOCK - 1) / SWR_GEOM_BLOCK;
+        any_cull = any_cull || d.frustum_cull;
+    }
+    const size_t off_vb = (nd * sizeof(DrawParams) + 255) & ~(size_t)255;
+    const size_t off_tb = (off_vb + nv * sizeof(BlockMap) + 255) & ~(size_t)255;
+    const size_t off_bp = (off_tb + nt * sizeof(BlockMap) + 255) & ~(size_t)255;
+    const size_t off_vis = (off_bp + (any_cull ? nd * sizeof(void*) : 0) + 255) & ~(size_t)255;
+    return (off_vis + (any_cull ? nd * 4 : 0) + 255) & ~(size_t)255;
+}
+// the batch's fragment program reads VertexOutput.Normal (DEBUG_VARYINGS, every user program): k_vertex and the clipper store it
+static bool b_needs_vnorm(const Batch& b) {
+    for (auto& d : b.draws) if (d.p.program == SWR_PROG_DEBUG_VARYINGS || d.p.program >= SWR_PROG_USER_BASE) return true;
     return false;
 }
+static bool b_has_debug_varyings(const Batch& b) { return !b.draws.empty() && b.draws[0].p.program == SWR_PROG_DEBUG_VARYINGS; }
+static bool b_has_user_program(const Batch& b) { return !b.draws.empty() && b.draws[0].p.program >= SWR_PROG_USER_BASE; }
 const unsigned long long kMaxPairs = 1ull << 30;       // list entries per round (4 GiB of slot ids)
 
 // pairs every set in use can hold (the optimistic flush is checked against this on the device)
@@ -603,7 +780,8 @@ int bin_and_raster(swr_context* c, RasterSet& S, hipStream_t F, const Batch& b, 
         ra.recs = S.d_recs.as<TriRec>();
         ra.vout = S.d_vout.as<VOut>();
         ra.vout_bytes = (uint32_t)std::min<size_t>(S.d_vout.cap, 0xfffffff0u);
-        ra.vnorm = b_has_debug_varyings(b) ? S.d_vnorm.as<float4>() : nullptr;
+        ra.vnorm = b_needs_vnorm(b) ? S.d_vnorm.as<float4>() : nullptr;
+        ra.user_consts = b_has_user_program(b) ? reinterpret_cast<const float*>((const char*)S.d_upload.p + user_consts_offset(b)) : nullptr;
         ra.draws = reinterpret_cast<const DrawParams*>(S.d_upload.p);
         ra.tile_start = S.d_tile_start.as<uint32_t>();
         ra.tile_count = S.d_tile_count.as<uint32_t>();
@@ -636,7 +814,12 @@ int bin_and_raster(swr_context* c, RasterSet& S, hipStream_t F, const Batch& b, 
                                 d.p.blend == SWR_BLEND_ALPHA && d.p.depth_test == SWR_DEPTH_LESSEQUAL;
             }
             ra.depth_only_grows = grows ? 1 : 0;
-            if (b_has_debug_varyings(b)) {        // (never mixed with other programs, never wireframe: swr_render_mesh / flush_locked)
+            if (b_has_user_program(b)) {          // (one user program per batch, never wireframe: record_draw / flush_locked)
+                void* args[] = { &ra, &mk, &pc };
+                hipFunction_t fn = b.draws[0].prog->fn[none ? 1 : 0];
+                SWR_HIP(c, hipModuleLaunchKernel(fn, g.x, 1, 1, t.x, 1, 1, 0, c->stream, args, nullptr));
+            }
+            else if (b_has_debug_varyings(b)) {   // (never mixed with other programs, never wireframe: swr_render_mesh / flush_locked)
                 if (none) hipLaunchKernelGGL((k_raster_c<false, true, SWR_PROG_DEBUG_VARYINGS, -1, -1, true>), g, t, 0, c->stream, ra, mk, pc);
                 else hipLaunchKernelGGL((k_raster_c<false, true, SWR_PROG_DEBUG_VARYINGS>), g, t, 0, c->stream, ra, mk, pc);
             }
@@ -714,7 +897,8 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
         for (uint32_t j : frag_reps) {
             const DrawParams& q = hp[j];
             if (q.program == p.program && q.blend == p.blend && q.depth_test == p.depth_test && q.tex == p.tex && q.tex_w == p.tex_w &&
-                q.tex_h == p.tex_h && memcmp(&q.u, &p.u, sizeof p.u) == 0) { p.frag_draw = j; break; }
+                q.tex_h == p.tex_h && memcmp(&q.u, &p.u, sizeof p.u) == 0 &&
+                (p.program < SWR_PROG_USER_BASE || *b.draws[j].uconsts == *b.draws[i].uconsts)) { p.frag_draw = j; break; }
         }
         // a representative must have its k_vertex block 0 run (it writes fog_r1 / fog_den): it has vertices and is not subject to the
         // device-side frustum test; the list is bounded so that a batch of thousands of distinct materials stays linear
@@ -737,10 +921,11 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
     for (auto& d : b.draws) any_cull = any_cull || d.frustum_cull;
     const size_t off_bp = (off_tb + tblocks.size() * sizeof(BlockMap) + 255) & ~(size_t)255;     // per-draw bounds pointers
     const size_t off_vis = (off_bp + (any_cull ? nd * sizeof(void*) : 0) + 255) & ~(size_t)255;   // per-draw visibility words
-    const size_t up_bytes = off_vis + (any_cull ? nd * 4 : 0);
+    const bool user = b_has_user_program(b);
+    const size_t up_bytes = user ? user_consts_offset(b) + nd * 64 * sizeof(float) : off_vis + (any_cull ? nd * 4 : 0);
     if ((rc = ensure(c, S.d_upload, up_bytes))) return rc;
     if ((rc = ensure(c, S.d_vout, (size_t)(V + 4 * T) * sizeof(VOut)))) return rc;
-    const bool dbgv = b_has_debug_varyings(b);
+    const bool dbgv = b_needs_vnorm(b);
     if (dbgv && (rc = ensure(c, S.d_vnorm, S.d_vout.cap / 4))) return rc;        // one float4 per VOut entry
     if ((rc = ensure(c, S.d_recs, (size_t)(spt * T) * sizeof(TriRec)))) return rc;
     if ((rc = ensure(c, c->d_slot_tb, (size_t)(spt * T) * 8))) return rc;
@@ -774,6 +959,10 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
     if (any_cull) {
         const float4** bp = reinterpret_cast<const float4**>(stage + off_bp);
         for (size_t i = 0; i < nd; ++i) bp[i] = b.draws[i].frustum_cull ? b.draws[i].mesh->d_bounds : nullptr;
+    }
+    if (user) {                                   // each draw's captured constants (k_raster_c reads those of the draw's frag_draw)
+        float* uc = reinterpret_cast<float*>(stage + user_consts_offset(b));
+        for (size_t i = 0; i < nd; ++i) memcpy(uc + 64 * i, b.draws[i].uconsts->data(), 64 * sizeof(float));
     }
     SWR_HIP(c, hipMemcpyAsync(S.d_upload.p, stage, up_bytes, hipMemcpyHostToDevice, F));
     const DrawParams* d_draws = reinterpret_cast<const DrawParams*>(S.d_upload.p);
@@ -823,8 +1012,10 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
 
 // complete = the batch's kernels are known to have finished (the stream was drained, or an event behind them has been waited for)
 void retire_batch(swr_context* c, Batch& b, bool complete = false) {
-    for (auto& d : b.draws)
+    for (auto& d : b.draws) {
         if (d.mesh && d.mesh->transient) { if (complete) pool_mesh(c, d.mesh); else c->garbage.push_back(d.mesh); }
+        if (d.prog && !complete) c->prog_garbage.push_back(std::move(d.prog));      // (its module stays loaded until the streams are idle)
+    }
     b.draws.clear();
 }
 
@@ -883,12 +1074,13 @@ int flush_locked(swr_context* c) {
     memcpy(b.clear_rgba, c->clear_rgba, 16);
     b.near_clip = c->near_clip;
     b.wireframe = c->debug_mode == SWR_DEBUG_WIREFRAME;
-    if (b.wireframe && b_has_debug_varyings(b)) {
+    if (b.wireframe && b_needs_vnorm(b)) {
         // DrawLine hands Interpolate the TRIANGLE's outputs[0..1] for all three edges (Rasterizer.cs:421-423); a line record keeps the
         // edge's end points, not those two vertices' screen positions, so the program's ScreenCoords term is not available there
         for (auto& d : b.draws) if (d.mesh && d.mesh->transient) c->garbage.push_back(d.mesh);
         c->pend_verts = c->pend_tris = 0;
-        return fail(c, SWR_ERR_UNSUPPORTED, "SWR_PROG_DEBUG_VARYINGS is not available in DebugMode.Wireframe");
+        return fail(c, SWR_ERR_UNSUPPORTED, b_has_user_program(b) ? "user fragment programs are not available in DebugMode.Wireframe"
+                                                                   : "SWR_PROG_DEBUG_VARYINGS is not available in DebugMode.Wireframe");
     }
     b.seq = c->next_seq++;
     b.color = c->color; b.depth = c->depth;
@@ -975,8 +1167,16 @@ static bool band_rejects(const swr_context* c, const swr_mesh* m, const float* m
 int record_draw(swr_context* c, swr_mesh* mesh, const float* model, const float* view, const float* proj,
                 int program, const swr_uniforms* u, const swr_texture* tex, int cull, int depth_test, int blend, bool frustum_cull = false) {
     if (!mesh || !model || !view || !proj) return fail(c, SWR_ERR_INVALID_ARG, "null argument to render_mesh");
-    if (program < SWR_PROG_FLAT_COLOR || program > SWR_PROG_DEBUG_VARYINGS)
+    std::shared_ptr<UserProg> uprog;
+    if (program >= SWR_PROG_USER_BASE) {
+        auto it = c->progs.find(program);
+        if (it == c->progs.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed user program id");
+        if (c->debug_mode == SWR_DEBUG_WIREFRAME)
+            return fail(c, SWR_ERR_UNSUPPORTED, "user fragment programs are not available in DebugMode.Wireframe");
+        uprog = it->second;
+    } else if (program < SWR_PROG_FLAT_COLOR || program > SWR_PROG_DEBUG_VARYINGS) {
         return fail(c, SWR_ERR_INVALID_ARG, "unknown program id");
+    }
     if ((program == SWR_PROG_DUST2_LAMBERT_FOG || program == SWR_PROG_PHONG_4POINT) && !u)
         return fail(c, SWR_ERR_INVALID_ARG, "this program needs a uniform block");
     if (cull < 0 || cull > 2 || depth_test < 0 || depth_test > 7 || blend < 0 || blend > 3)
@@ -995,8 +1195,9 @@ int record_draw(swr_context* c, swr_mesh* mesh, const float* model, const float*
         int rc = flush_locked(c);
         if (rc) return rc;
     }
-    // SWR_PROG_DEBUG_VARYINGS has kernels of its own: a batch holds either only such draws or none (submission order is kept)
-    if (!c->draws.empty() && (c->draws.back().p.program == SWR_PROG_DEBUG_VARYINGS) != (program == SWR_PROG_DEBUG_VARYINGS)) {
+    // SWR_PROG_DEBUG_VARYINGS and each user program have kernels of their own: a batch holds either only such draws or none
+    // (submission order is kept)
+    if (!c->draws.empty() && kernel_class(c->draws.back().p.program) != kernel_class(program)) {
         int rc = flush_locked(c);
         if (rc) return rc;
     }
@@ -1014,6 +1215,10 @@ int record_draw(swr_context* c, swr_mesh* mesh, const float* model, const float*
     d.p.nm_flags = c->nm_flags;
     d.mesh = mesh;
     d.frustum_cull = frustum_cull;
+    if (uprog) {       // the constants as they are NOW (a C# closure's captured fields): later set_constants calls leave this draw alone
+        d.uconsts = std::make_shared<const std::vector<float>>(uprog->constants, uprog->constants + 64);
+        d.prog = std::move(uprog);
+    }
     if (frustum_cull) { int rc = ensure_bounds(c, mesh); if (rc) return rc; }
     c->draws.push_back(d);
     c->pend_verts += mesh->n_verts; c->pend_tris += n_tris;
@@ -1105,8 +1310,6 @@ int swr_abi_version(void) { return SWR_ABI_VERSION; }
 #ifndef SWR_BUILD_EXTRA
 #define SWR_BUILD_EXTRA ""
 #endif
-#define SWR_STR2(x) #x
-#define SWR_STR(x) SWR_STR2(x)
 const char* swr_build_info(void) {
     return "hipcc=" SWR_BUILD_HIPCC "; csrc_sha256=" SWR_BUILD_SRC_SHA "; fma=" SWR_STR(SWR_NUMERICS_FMA) "; dot=" SWR_STR(SWR_DOT_PAIRWISE) "; extra=" SWR_BUILD_EXTRA;
 }
@@ -1186,6 +1389,8 @@ void swr_destroy(swr_context* c) {
     c->inflight.clear();
     collect_spans(c);
     free_garbage(c);
+    c->draws.clear();
+    c->progs.clear();                        // (streams idle: the modules unload here)
     for (swr_mesh* m : c->mesh_pool) destroy_mesh(m);
     c->mesh_pool.clear();
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
@@ -1677,6 +1882,52 @@ int swr_is_sphere_in_frustum(swr_context* c, const float center_radius[4], const
     SWR_HIP(c, hipMemcpyAsync(&r, base + 192, 4, hipMemcpyDeviceToHost, c->stream));
     SWR_HIP(c, hipStreamSynchronize(c->stream));
     *inside = (int)r;
+    return SWR_OK;
+}
+
+int swr_program_validate(const char* src, char* log, int log_len) {
+    if (!src) return SWR_ERR_INVALID_ARG;
+    std::shared_ptr<const RtcCode> code;
+    std::string msg;
+    const int rc = rtc_compile(src, code, msg);
+    if (log && log_len > 0) {
+        const size_t n = std::min(msg.size(), (size_t)log_len - 1);
+        memcpy(log, msg.data(), n); log[n] = '\0';
+    }
+    return rc;
+}
+
+int swr_program_create(swr_context* c, const char* src, int* program_id) {
+    SWR_ENTER(c);
+    if (!src || !program_id) return fail(c, SWR_ERR_INVALID_ARG, "null argument to swr_program_create");
+    std::shared_ptr<const RtcCode> code;
+    std::string log;
+    const int rc = rtc_compile(src, code, log);
+    if (rc) { c->err = log; return rc; }
+    auto p = std::make_shared<UserProg>();
+    SWR_HIP(c, hipModuleLoadData(&p->mod, code->code.data()));
+    for (int k = 0; k < 2; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
+    const int id = c->next_prog++;
+    c->progs[id] = std::move(p);
+    *program_id = id;
+    return SWR_OK;
+}
+
+int swr_program_destroy(swr_context* c, int program_id) {
+    SWR_ENTER(c);
+    auto it = c->progs.find(program_id);
+    if (it == c->progs.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed user program id");
+    c->progs.erase(it);                  // draws already recorded hold the program until their batch is over
+    return SWR_OK;
+}
+
+int swr_program_set_constants(swr_context* c, int program_id, const float* values, int n) {
+    SWR_ENTER(c);
+    auto it = c->progs.find(program_id);
+    if (it == c->progs.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed user program id");
+    if (n < 0 || n > 64 || (n > 0 && !values)) return fail(c, SWR_ERR_INVALID_ARG, "between 0 and 64 constants");
+    float* k = it->second->constants;
+    for (int i = 0; i < 64; ++i) k[i] = i < n ? values[i] : 0.0f;
     return SWR_OK;
 }
 

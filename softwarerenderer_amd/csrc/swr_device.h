@@ -6,8 +6,10 @@
 // -fhip-fp32-correctly-rounded-divide-sqrt); f32 denormals are kept (hipcc default).
 #pragma once
 
+#ifndef __HIPCC_RTC__               // (run-time compiled fragment programs: the prelude of swr_program.hip.h declares these)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#endif
 #include "swr.h"
 
 // System.Numerics models.  Whether .NET 9 fuses the multiply-adds of Vector4.Transform / Vector3.TransformNormal /
@@ -28,6 +30,9 @@
 #endif                       // (x, y, z, 0) lanes of a Vector128: 0 sequential (xx + yy) + zz; 1 dpps order (xx + yy) + (zz + 0);
                              // 2 two shuffle-adds (Vector128.Sum) (xx + zz) + (yy + 0)
 
+// k_raster_c's program parameter for a USER fragment program (swr_program_create, include/swr.h): the instantiation exists only in
+// the code objects compiled at run time (swr_program.hip.h, SWR_RTC_PROGRAM); draws carry the user id (>= SWR_PROG_USER_BASE)
+#define SWR_PROG_CUSTOM 5
 #define SWR_TILE 16                      // Rasterizer.cs:53 TileSize -- part of the numerical contract
 #define SWR_FLOAT_MINVALUE (-3.40282347e+38f)   // float.MinValue, MainWindow.cs:425,434
 #define SWR_EPSILON 1e-6f                // Rasterizer.cs:52

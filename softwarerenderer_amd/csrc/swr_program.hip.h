@@ -1,0 +1,110 @@
+// swr_program.hip.h -- the source contract of USER fragment programs (swr_program_create, include/swr.h).  Compiled only at run
+// time (hiprtc, SWR_RTC_PROGRAM defined): the library embeds this header and the kernel headers, the prelude below comes first,
+// then the user's text, then k_raster_c.  The product library never includes it.
+//
+// The user defines one function:
+//     __device__ float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
+// `in` is Shaders.VertexOutput after Rasterizer.Interpolate (Rasterizer.cs:566-640) with Interpolate = true -- the vertex stage is
+// Renderer.VertexShader (Renderer.cs:830-846), as for SWR_PROG_DUST2_LAMBERT_FOG -- computed with the arithmetic the built-in
+// programs use.  The function is inlined into the raster kernel, so varyings it never reads are never interpolated (or loaded).
+// A result with W <= 0 or NaN writes nothing (Rasterizer.cs:511): swr_discard() is such a result.
+#pragma once
+
+#ifdef __HIPCC_RTC__
+typedef __INT8_TYPE__ int8_t;
+typedef __UINT8_TYPE__ uint8_t;
+typedef __INT16_TYPE__ int16_t;
+typedef __UINT16_TYPE__ uint16_t;
+typedef __INT32_TYPE__ int32_t;
+typedef __UINT32_TYPE__ uint32_t;
+typedef __INT64_TYPE__ int64_t;
+typedef __UINT64_TYPE__ uint64_t;
+typedef __UINTPTR_TYPE__ uintptr_t;
+#ifndef offsetof
+#define offsetof(T, m) __builtin_offsetof(T, m)
+#endif
+#endif
+
+#include "swr_raster.hip.h"
+
+// Shaders.VertexOutput after Interpolate
+struct swr_fs_in {
+    float4 clip_position;        // ClipPosition (x, y, z, w)
+    float4 color;                // Color
+    float2 tex_coord;            // TexCoord
+    float3 normal;               // Normal (object space, VertexInput.Normal interpolated)
+    float2 screen_coords;        // ScreenCoords (pixel position / (width - 1, height - 1) at the vertices, Rasterizer.cs:390)
+    float3 barycentric;          // Barycentric (the perspective-correct weights wa, wb, wc, Rasterizer.cs:583-585,638)
+    float3 world_normal;         // Data["WorldNormal"]: weighted sum renormalised (Rasterizer.cs:680-688)
+};
+
+// what a fragment program closes over: the draw's uniform block, its captured constants, the pixel
+struct swr_fs_env {
+    const swr_uniforms& uniforms;
+    const float* constants;      // constants[0..63] (swr_program_set_constants when the draw was recorded; zeros if never set)
+    int x, y;                    // pixel
+    const uint8_t* tex;          // the draw's texture (null: none) in the layout texture_fetch reads
+    int tex_w, tex_h;
+};
+
+// Texture.Sample (Texture.cs:43-63): nearest, or the build-defined bilinear filter when the texture was switched to it -- the function
+// the built-in programs call.  Without a texture: Vector4.One.
+__device__ __forceinline__ bool swr_has_texture(const swr_fs_env& env) { return env.tex != nullptr && env.tex_h != 0; }
+__device__ __forceinline__ float4 swr_sample(const swr_fs_env& env, float2 uv) {
+    if (!swr_has_texture(env)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    return swr::texture_fetch(env.tex, env.tex_w, env.tex_h, uv.x, uv.y);
+}
+// the build's System.Numerics model (SWR_DOT_PAIRWISE / SWR_NUMERICS_FMA): Vector3.Dot, Lerp's a * (1 - t) + b * t
+__device__ __forceinline__ float swr_dot3(float3 a, float3 b) { return swr::dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
+__device__ __forceinline__ float swr_lerp(float a, float b, float t) { return swr::nm_lerp(a, b, t); }
+__device__ __forceinline__ float4 swr_lerp(float4 a, float4 b, float t) {
+    return make_float4(swr_lerp(a.x, b.x, t), swr_lerp(a.y, b.y, t), swr_lerp(a.z, b.z, t), swr_lerp(a.w, b.w, t));
+}
+// MathF.Max / Math.Clamp as .NET evaluates them
+__device__ __forceinline__ float swr_max(float a, float b) { return swr::mathf_max(a, b); }
+__device__ __forceinline__ float swr_clamp(float v, float lo, float hi) { return swr::math_clamp(v, lo, hi); }
+// a null result: nothing is written (and under BlendMode.None the row's early-out applies)
+__device__ __forceinline__ float4 swr_discard() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+
+// the user's program (always inlined into the raster kernel)
+__device__ __attribute__((always_inline)) float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
+
+namespace swr {
+
+// Rasterizer.Interpolate (Interpolate = true) of everything swr_fs_in holds, from the three outputs as the raster kernel loads them:
+// clip / colour / uv + wn.xy / wn.z rows of VOut, Normal from the side array, the screen positions from the TriRec.  The divisions
+// are the IEEE ones (shade_fragment's division cores return the same quotients), the sums in the reference's order.
+__device__ __forceinline__ swr_fs_in interpolate_fs_in(float w0f, float w1f, float w2f, const float4 clip[3], const float4 col[3],
+                                                       const float4 uvn[3], const float wnz[3], const float4 nrm[3], const float sx[3],
+                                                       const float sy[3], float inv_width, float inv_height) {
+    const float ra = w0f / clip[0].w, rb = w1f / clip[1].w, rc = w2f / clip[2].w;        // :576-578
+    const float inv_sum = (ra + rb) + rc;                                                 // :579
+    const float w = 1.0f / inv_sum;                                                       // :582
+    const float wa = ra * w, wb = rb * w, wc = rc * w;                                    // :583-585
+    auto persp = [&](float a_, float b_, float c_) { return (((a_ * ra + b_ * rb) + c_ * rc) * w); };      // Vector4.Multiply / Add / Multiply
+    swr_fs_in in;
+    in.clip_position = make_float4(persp(clip[0].x, clip[1].x, clip[2].x), persp(clip[0].y, clip[1].y, clip[2].y),
+                                   persp(clip[0].z, clip[1].z, clip[2].z), persp(clip[0].w, clip[1].w, clip[2].w));
+    in.color = make_float4(persp(col[0].x, col[1].x, col[2].x), persp(col[0].y, col[1].y, col[2].y),
+                           persp(col[0].z, col[1].z, col[2].z), persp(col[0].w, col[1].w, col[2].w));
+    in.tex_coord = make_float2(persp(uvn[0].x, uvn[1].x, uvn[2].x), persp(uvn[0].y, uvn[1].y, uvn[2].y));
+    in.normal = make_float3(persp(nrm[0].x, nrm[1].x, nrm[2].x), persp(nrm[0].y, nrm[1].y, nrm[2].y), persp(nrm[0].z, nrm[1].z, nrm[2].z));
+    // outputs[i].ScreenCoords = (screenCoords[i].X * invWidth, screenCoords[i].Y * invHeight), :390
+    const float s0x = sx[0] * inv_width, s1x = sx[1] * inv_width, s2x = sx[2] * inv_width;
+    const float s0y = sy[0] * inv_height, s1y = sy[1] * inv_height, s2y = sy[2] * inv_height;
+    in.screen_coords = make_float2(persp(s0x, s1x, s2x), persp(s0y, s1y, s2y));
+    in.barycentric = make_float3(wa, wb, wc);
+    // InterpolateData, Vector3 key: weighted sum with the normalised weights, then 1 / MathF.Sqrt(lengthSquared) (:680-688)
+    float n0 = (uvn[0].z * wa + uvn[1].z * wb) + uvn[2].z * wc;
+    float n1 = (uvn[0].w * wa + uvn[1].w * wb) + uvn[2].w * wc;
+    float n2 = (wnz[0] * wa + wnz[1] * wb) + wnz[2] * wc;
+    const float len_sq = dot3(n0, n1, n2, n0, n1, n2);
+    if (len_sq > 1e-6f) {
+        const float s = 1.0f / sqrtf(len_sq);
+        n0 = n0 * s; n1 = n1 * s; n2 = n2 * s;
+    }
+    in.world_normal = make_float3(n0, n1, n2);
+    return in;
+}
+
+}  // namespace swr

@@ -22,7 +22,9 @@
 //   not cover, so the links that can run early do: the next window's head words are read at the cut, each lane's next pair and
 //   that pair's prefix counts between replay and shading, the row-start table and stored depth ahead of the election's atomic.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <type_traits>
+#endif
 #include "swr_device.h"
 #include "swr_raster.hip.h"
 
@@ -541,6 +543,40 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
         const float inv_w = 1.0f / (float)(a.fp.width - 1), inv_h = 1.0f / (float)(a.fp.height - 1);      // Rasterizer.cs:362-363
         return shade_debug_varyings(w0f, w1f, w2f, q4.w, q5.w, wc_clip, na, nb, nc, sx, sy, inv_w, inv_h);
     };
+    // SWR_PROG_CUSTOM (code objects compiled at run time only, SWR_RTC_PROGRAM: a batch holds the draws of ONE user program): every
+    // varying of Shaders.VertexOutput -- VOut rows, Normal from the side array, screen positions from the TriRec -- interpolated
+    // (swr_program.hip.h) and handed to the user's swr_fragment, inlined here: what it does not read is neither loaded nor computed
+    auto shade_user = [&L, &a, vout_rsrc](int t, float w0f, float w1f, float w2f, const DrawConsts& dc, uint32_t draw, int px, int py) {
+#ifdef SWR_RTC_PROGRAM
+        if constexpr (PHONG && VG && PROG == SWR_PROG_CUSTOM) {
+            const __amdgpu_buffer_rsrc_t nrm_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.vnorm, 0, (int)(a.vout_bytes >> 2), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.recs, 0, 0x7ffffff0, 0x00020000);
+            auto ld4 = [](__amdgpu_buffer_rsrc_t r, uint32_t off) {
+                const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+                return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+            };
+            const float4 q4 = L.stage[4][t], q6 = L.stage[6][t];
+            const uint32_t off[3] = { __float_as_uint(q4.x), __float_as_uint(q4.y), __float_as_uint(q4.z) };
+            float4 clip[3], col[3], uvn[3], nrm[3];
+            float wnz[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                clip[k] = ld4(vout_rsrc, off[k]); col[k] = ld4(vout_rsrc, off[k] + 16u); uvn[k] = ld4(vout_rsrc, off[k] + 32u);
+                wnz[k] = ld4(vout_rsrc, off[k] + 48u).x;
+                nrm[k] = ld4(nrm_rsrc, off[k] >> 2);
+            }
+            const uint32_t ro = __float_as_uint(q6.x);
+            const float4 r0 = ld4(rec_rsrc, ro), r1 = ld4(rec_rsrc, ro + 16u);
+            const float sx[3] = { r0.x, r0.y, r0.z }, sy[3] = { r0.w, r1.x, r1.y };
+            const float inv_w = 1.0f / (float)(a.fp.width - 1), inv_h = 1.0f / (float)(a.fp.height - 1);      // Rasterizer.cs:362-363
+            const swr_fs_in in = interpolate_fs_in(w0f, w1f, w2f, clip, col, uvn, wnz, nrm, sx, sy, inv_w, inv_h);
+            const swr_fs_env env = { a.draws[draw].u, a.user_consts + 64u * draw, px, py, dc.tex, dc.tex_w, dc.tex_h };
+            return swr_fragment(in, env);
+        }
+#endif
+        (void)L; (void)a; (void)vout_rsrc; (void)t; (void)w0f; (void)w1f; (void)w2f; (void)dc; (void)draw; (void)px; (void)py;
+        return make_float4(0.f, 0.f, 0.f, 0.f);
+    };
     // part: 0 = everything, 1 = only the three uv rows (requested ahead of the chain replay, the texel address hangs
     // on them), 2 = everything but the uv rows, which `V` already holds
     auto load_varyings = [&L, vout_rsrc](int t, bool fastdiv, int part = 0, TriVaryings V = TriVaryings()) {
@@ -967,6 +1003,7 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
                         }
                         if (need_exact)
                             src = (PHONG && PROG == SWR_PROG_DEBUG_VARYINGS) ? shade_debug(t, w0f, w1f, w2f) :
+                                  (PHONG && PROG == SWR_PROG_CUSTOM) ? shade_user(t, w0f, w1f, w2f, dc, draw0, x0 + (pix & 15), y0 + (pix >> 4)) :
                                   shade_fragment<PHONG>(cdp, dc, f_program, f_interp, Vs, w0f, w1f, w2f);                           // :507-509 / :321-323
 #endif
                         // triangles: W > 0 (:511); lines: W != 0 (:325)
@@ -981,6 +1018,7 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
                     e_pass = depth_func(f_dt, d, L.z[pix]);
                     if (e_pass) {
                         e_src = (PHONG && PROG == SWR_PROG_DEBUG_VARYINGS) ? shade_debug(t, w0f, w1f, w2f) :
+                                (PHONG && PROG == SWR_PROG_CUSTOM) ? shade_user(t, w0f, w1f, w2f, dc, draw0, x0 + (pix & 15), y0 + (pix >> 4)) :
                                 shade_fragment<PHONG>(cdp, dc, f_program, f_interp,
                                                       VG ? load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 2, Vg) : load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u),
                                                       w0f, w1f, w2f);

@@ -212,6 +212,22 @@ class Device:
         self._ck(self._lib.swr_get_pipelining(self._ctx, C.byref(m)))
         return int(m.value)
 
+    def compile_program(self, source: str) -> int:
+        """swr_program_create: compile a user fragment program (C++ defining `swr_fragment`, contract in include/swr.h) for this
+        device; returns its id (>= SWR_PROG_USER_BASE).  A compile error raises SwrError(SWR_ERR_INVALID_ARG) with the log."""
+        pid = C.c_int(0)
+        self._ck(self._lib.swr_program_create(self._ctx, source.encode(), C.byref(pid)))
+        return pid.value
+
+    def destroy_program(self, program_id: int):
+        """Draws recorded with the program still render with it."""
+        self._ck(self._lib.swr_program_destroy(self._ctx, int(program_id)))
+
+    def set_program_constants(self, program_id: int, values):
+        """Up to 64 floats the program reads as env.constants[i]; each draw captures them when it is recorded."""
+        a = _f32(values if values is not None else [], None)
+        self._ck(self._lib.swr_program_set_constants(self._ctx, int(program_id), _fptr(a) if a.size else None, int(a.size)))
+
     def set_stream(self, hip_stream: int):
         self._ck(self._lib.swr_set_stream(self._ctx, C.c_void_p(hip_stream)))
 
@@ -266,11 +282,35 @@ class ShaderProgram:
     """Stands in for the reference's (VertexShader, FragmentShader) delegate pair (Shaders.cs:97-98)."""
 
     def __init__(self, program: Program, uniforms: Optional[N.Uniforms] = None, texture: Optional[Texture] = None):
-        self.program = Program(program)
+        # a built-in Program, or the id of a user fragment program (Device.compile_program, >= SWR_PROG_USER_BASE)
+        self.program = Program(program) if int(program) < N.SWR_PROG_USER_BASE else int(program)
         self.uniforms = uniforms if uniforms is not None else default_uniforms()
         self.texture = texture
         self.VertexShader = VertexShader(self)
         self.FragmentShader = FragmentShader(self)
+
+    def _program_for(self, dev: "Device") -> int:
+        return int(self.program)
+
+
+class CustomProgram(ShaderProgram):
+    """A user fragment program given as source (Shaders.Custom): compiled once per Device on first use; `constants` (up to 64
+    floats, the fields the C# closure captures) are set before every draw, so each draw renders with the values it was given."""
+
+    def __init__(self, source: str, uniforms: Optional[N.Uniforms] = None, texture: Optional[Texture] = None, constants=None):
+        super().__init__(Program.FlatColor, uniforms, texture)
+        self.source = source
+        self.constants = constants
+        self._ids = {}          # id(Device) -> (Device, program id)
+
+    def _program_for(self, dev: "Device") -> int:
+        hit = self._ids.get(id(dev))
+        if hit is None or hit[0] is not dev:
+            hit = (dev, dev.compile_program(self.source))
+            self._ids[id(dev)] = hit
+        pid = hit[1]
+        dev.set_program_constants(pid, self.constants)
+        return pid
 
 
 class Shaders:
@@ -296,6 +336,11 @@ class Shaders:
     @staticmethod
     def Phong4Point(uniforms, texture=None):
         return ShaderProgram(Program.Phong4Point, uniforms, texture)
+
+    @staticmethod
+    def Custom(source: str, uniforms=None, texture=None, constants=None):
+        """Any Shaders.FragmentShader restated in C++ against the contract of include/swr.h (swr_program_create)."""
+        return CustomProgram(source, uniforms, texture, constants)
 
 
 class MainWindow:
@@ -576,15 +621,16 @@ class Rasterizer:
         dev._ck(dev._lib.swr_set_state(dev._ctx, float(cls.NearClip), float(cls.FarClip), int(cls.RenderDebugMode)))
         m, v, p = _f32(model, 16), _f32(view, 16), _f32(projection, 16)
         tex = prog.texture._h if prog.texture is not None else None
+        pid = prog._program_for(dev)
         if isinstance(vertices, Mesh):
             fn = dev._lib.swr_render_mesh_culled if frustumCull else dev._lib.swr_render_mesh
-            rc = fn(dev._ctx, vertices._h, _fptr(m), _fptr(v), _fptr(p), int(prog.program),
+            rc = fn(dev._ctx, vertices._h, _fptr(m), _fptr(v), _fptr(p), pid,
                                           C.byref(prog.uniforms), tex, int(cullMode), int(depthTest), int(blendMode))
         else:
             va = as_vertex_array(vertices)
             ia = np.ascontiguousarray(indices, dtype=np.uint16).reshape(-1)
             rc = dev._lib.swr_render_mesh_arrays(dev._ctx, va.ctypes.data, int(va.shape[0]), ia.ctypes.data, int(ia.shape[0]),
-                                                 _fptr(m), _fptr(v), _fptr(p), int(prog.program), C.byref(prog.uniforms), tex,
+                                                 _fptr(m), _fptr(v), _fptr(p), pid, C.byref(prog.uniforms), tex,
                                                  int(cullMode), int(depthTest), int(blendMode))
         if rc == N.SWR_ERR_INVALID_ARG:
             msg = dev._lib.swr_last_error(dev._ctx).decode()
