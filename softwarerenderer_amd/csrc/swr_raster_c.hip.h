@@ -236,7 +236,13 @@ __global__ __launch_bounds__(SWR_COVER_BLOCK) void k_cover(CoverArgs a) {
         // pair_may_cover, S = sum |d_i invArea| M_i): every edge value of the reference's chain is within 35uM_i of the
         // exact edge function (swr_binning.hip.h), so the fragment's float depth (two products, two sums) is within
         // 39.3uS of the exact affine depth; that is maximal at a corner of R; the corners evaluated in float below are
-        // within 7.3uS; margin used: 64uS.  Lines and non-finite cases get +inf (never hidden).
+        // within 7.3uS; margin used: 64uS.  Those are relative errors; a product that underflows errs by up to 2^-150
+        // absolutely instead, whatever its size.  That happens for huge triangles with small depths (d_k * invArea is
+        // subnormal at screen coordinates ~1e17 and depths ~1e-5, and its rounding then moves a corner by up to
+        // 2^-150 M_k: 30 % of the depth there), so the bound adds T = 2^-146 sum (M_k + |d_k invArea| + |d_k| + 1),
+        // which covers every such term of both evaluations (each is <= 2^-150 times one of M_k, |d_k invArea|,
+        // |d_k|, 1, at most twice per k, and the evaluation of T itself loses < 2^-150).  T is below the last bit of
+        // the depth in ordinary frames.  Lines and non-finite cases get +inf (never hidden).
         float zbound = __uint_as_float(0x7f800000u);
         if (!is_line && startX <= endX && startY <= endY) {
             const float fxs = (float)startX, fxe = (float)endX, fys = (float)startY, fye = (float)endY;
@@ -247,16 +253,18 @@ __global__ __launch_bounds__(SWR_COVER_BLOCK) void k_cover(CoverArgs a) {
             const float ea[3] = { sy[1] - sy[2], sy[2] - sy[0], sy[0] - sy[1] };
             const float eb[3] = { sx[2] - sx[1], sx[0] - sx[2], sx[1] - sx[0] };
             const float rx[3] = { sx[1], sx[2], sx[0] }, ry[3] = { sy[1], sy[2], sy[0] };
-            float c00 = 0.f, c10 = 0.f, c01 = 0.f, c11 = 0.f, S = 0.f;
+            float c00 = 0.f, c10 = 0.f, c01 = 0.f, c11 = 0.f, S = 0.f, T = 0.f;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const float kk = dd[k] * inv_area;
                 const float dxs = fxs - rx[k], dxe = fxe - rx[k], dys = fys - ry[k], dye = fye - ry[k];
                 const float xs = ea[k] * dxs, xe = ea[k] * dxe, ys = eb[k] * dys, ye = eb[k] * dye;
                 c00 += kk * (xs + ys); c10 += kk * (xe + ys); c01 += kk * (xs + ye); c11 += kk * (xe + ye);
-                S += fabsf(kk) * (fabsf(ea[k]) * fmaxf(fabsf(dxs), fabsf(dxe)) + fabsf(eb[k]) * fmaxf(fabsf(dys), fabsf(dye)));
+                const float mk = fabsf(ea[k]) * fmaxf(fabsf(dxs), fabsf(dxe)) + fabsf(eb[k]) * fmaxf(fabsf(dys), fabsf(dye));
+                S += fabsf(kk) * mk;
+                T += ((mk + fabsf(kk)) + fabsf(dd[k])) + 1.0f;
             }
-            const float U = fmaxf(fmaxf(c00, c10), fmaxf(c01, c11)) + S * (64.0f / 16777216.0f);
+            const float U = (fmaxf(fmaxf(c00, c10), fmaxf(c01, c11)) + S * (64.0f / 16777216.0f)) + T * 0x1p-146f;
             const bool finite = S < 1.0e30f && c00 == c00 && c10 == c10 && c01 == c01 && c11 == c11;   // fmaxf drops NaNs
             if (finite) zbound = U;
         }

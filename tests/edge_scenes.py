@@ -1,0 +1,521 @@
+"""Adversarial scene families for the raster kernels' shortcuts (test helper; not part of the package).
+
+Three places in the kernels skip work on the strength of a hand-written error bound instead of repeating the reference's
+arithmetic: the tile rejection of binning (pair_may_cover, swr_binning.hip.h), the hierarchical-Z pair drop (k_cover's bound,
+k_raster_c's drop, swr_raster_c.hip.h) and k_cover's fast coverage walk.  Others depend on where inputs fall: the run select of
+pairs flagged SWR_INFO_SIMPLE, the division / reciprocal / sqrt cores (swr_device.h) and depth_only_grows (swr_api.hip).  Random
+scenes almost never land within rounding distance of those bounds; the families below are built to:
+
+  F1  lattice edges: edges through integer pixel samples at tile corners, vertices 1e2..4e6 px away (the chain rounds)
+  F2  hi-Z near ties: one surface drawn 2-4 times with different triangulations, translucent, under Less / LessEqual
+  F3  magnitude ladder: visible triangles whose screen coordinates straddle 1e15, 1e30 and the chain's overflow
+  F4  slivers: needles longer than a tile and much narrower than a pixel (where a row would stop being one run, if any could)
+  F5  guards: the same triangles with every clip vector scaled by 2^k, normals that cancel across the triangle
+  F6  mixed depth tests in one flush over F2's layers
+
+Every family is a seeded function returning a list of scenes.Scene of at most 256 x 256.  Exact screen positions come from
+clip.w = 1 and power-of-two targets: screen_x = (nx * 0.5 + 0.5) * W is then exact for the nx of `ndc_for_pixel`.
+
+The second half restates, in numpy float32, what the tests compare and count: DrawTriangle's setup (Rasterizer.cs:342-399), the
+tile chain of RasterizeTriangle (:445-534), pair_may_cover and k_cover's hi-Z bound with their margins as parameters.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from softwarerenderer_amd import hostmath as hm
+from softwarerenderer_amd import scenes
+from softwarerenderer_amd.rasterizer import BlendMode, CullMode, DepthTest, Program
+
+F32 = np.float32
+TILE = 16
+FLOAT_MIN = F32(-3.40282347e38)
+U = 2.0 ** -24
+
+
+# ============================================================================ construction helpers
+def ndc_for_pixel(X, size):
+    """nx (or, for y, -ny) whose screen coordinate is exactly X on a power-of-two axis of `size` pixels (|X| < 2^22)."""
+    return F32(2.0 * X / size - 1.0)
+
+
+def clip_pos(X, Y, W, H):
+    """Model-space position of screen point (X, Y) under identity matrices (clip.w = 1): (x, y) only."""
+    return float(ndc_for_pixel(X, W)), -float(ndc_for_pixel(Y, H))
+
+
+def z_for_depth(d):
+    """clip.z whose depth (z + 1) * 0.5 is close to d (setup_triangle rounds it; the restatement below says exactly what)."""
+    return float(F32(2.0 * d - 1.0))
+
+
+def w_projection(c=0.0):
+    """Row-vector matrix with clip = (x, y, c * z, z): clip.w is the vertex's z, nz = c."""
+    m = np.zeros((4, 4), dtype=F32)
+    m[0, 0] = m[1, 1] = 1.0
+    m[2, 2] = c
+    m[2, 3] = 1.0
+    return m
+
+
+def _draw(pos, col, proj=None, *, program=Program.Gouraud, cull=CullMode.None_, depth_test=DepthTest.LessEqual,
+          blend=BlendMode.Alpha, normal=None, uv=None):
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    v = scenes.make_vertices(pos, uv=uv, normal=normal, color=np.asarray(col, dtype=np.float64).reshape(-1, 4))
+    assert v.shape[0] <= 65535
+    I = hm.identity()
+    return scenes.Draw(v, np.arange(v.shape[0], dtype=np.uint16), I, I, I if proj is None else proj, program=program,
+                       uniforms=scenes.default_uniforms(), cull=cull, depth_test=depth_test, blend=blend)
+
+
+def _colors(rng, n, alpha):
+    return np.concatenate([rng.uniform(0.05, 1.0, (n, 3)), np.full((n, 1), alpha)], axis=1)
+
+
+# ============================================================================ F1: lattice edges at tile borders
+def _lattice_edge(rng, W, H, near):
+    """(A, B, C, C2, P, tile) of one F1 triangle pair, or None: edge AB through the tile corner sample P (or, near=True, past it
+    by 1e-2.5..10^-0.5 px), C on the inner side, C2 its twin across AB; the tile beyond P touches the triangle at P only."""
+    corners = [(15, 15, 1, 1), (0, 0, -1, -1), (15, 0, 1, -1), (0, 15, -1, 1)]      # offset in the tile, outward side
+    ox, oy, gx, gy = corners[int(rng.integers(0, 4))]
+    ti, tj = int(rng.integers(0, W // TILE)), int(rng.integers(0, H // TILE))
+    P = np.array([TILE * ti + ox, TILE * tj + oy])
+    nrm = np.array([gx * int(rng.integers(1, 41)), gy * int(rng.integers(1, 41))])
+    if np.gcd(*np.abs(nrm)) != 1:
+        return None
+    D = np.array([-nrm[1], nrm[0]])
+    L = np.linalg.norm(D)
+    lo, hi = (6.3, 7.0) if near else (2.0, 6.5)
+    t1, t2 = (max(1, int(10 ** rng.uniform(lo, hi) / L)) for _ in range(2))
+    m = max(1, int(10 ** rng.uniform(1.5 if not near else 4.0, 6.2) / L))
+    r = int(rng.integers(-t2, t1 + 1))
+    A, B = P + t1 * D, P - t2 * D
+    C, C2 = P + m * nrm + r * D, P - m * nrm + r * D
+    if near:
+        e = 10 ** rng.uniform(-2.5, -0.5) * (nrm / np.linalg.norm(nrm))
+        A, B = A + e, B + e
+    elif max(np.abs(np.concatenate([A, B, C, C2]))) >= 4.0e6:
+        return None                                                 # (exact integer screen positions below 2^22)
+    return A, B, C, C2, (ti, tj)
+
+
+@functools.lru_cache(maxsize=None)
+def f1_lattice_edges(seed=0, n=120, n_near=6, W=64, H=64):
+    """Triangles with one edge through a tile corner's pixel sample, the tile beyond that corner on the edge's outer side:
+    bbox /\\ that tile touches the triangle at one sample, where the exact edge value is 0 and the float chain's is rounding
+    noise (the vertices are 1e2..4e6 px away).  Both windings, cull None.  Every triangle has a twin across the same edge
+    (shared edge: no top-left rule, samples on it are covered twice) -- drawn under Additive blend and Alpha blend.
+    At an exact lattice point the corner evaluation of pair_may_cover is exactly 0 (the two products round alike), so binning's
+    margin is only needed where the edge MISSES the sample by less than the chain's noise: n_near such triangles (vertices
+    2e6..1e7 px away) are found by a seeded search over near misses, with the restatement below as the judge (about one
+    candidate in a thousand qualifies: the chain's actual error is far below the 35uM of the proof)."""
+    rng = np.random.default_rng(seed)
+    tris = []
+    def add(A, B, C, C2, z, first=None):
+        verts = [(*clip_pos(*A, W, H), z[0]), (*clip_pos(*B, W, H), z[1]), (*clip_pos(*C, W, H), z[2]), (*clip_pos(*C2, W, H), z[3])]
+        for tri in ((0, 1, 2), (1, 0, 3)):
+            tri = list(tri)
+            if (rng.uniform() < 0.5) if first is None else (first and tri[2] == 2):
+                tri.reverse()                                       # the other winding
+            tris.append([verts[i] for i in tri])
+    while len(tris) < 2 * n:
+        g = _lattice_edge(rng, W, H, near=False)
+        if g is not None:
+            add(*g[:4], [z_for_depth(float(rng.uniform(0.2, 0.8))) for _ in range(4)])
+    found = 0
+    for _ in range(200000):
+        if found == n_near:
+            break
+        g = _lattice_edge(rng, W, H, near=True)
+        if g is None:
+            continue
+        A, B, C, C2, tile = g
+        for flip, tri in ((False, (A, B, C)), (True, (C, B, A))):
+            t = Tri([np.array([*clip_pos(*p, W, H), 0.0, 1.0], dtype=F32) for p in tri], W, H)
+            r = t.rect(*tile) if t.ok else None
+            if r is not None and t.cover(r)[0].any() and not t.pair_may_cover(r, margin=0.0):
+                add(A, B, C, C2, [z_for_depth(float(rng.uniform(0.2, 0.8))) for _ in range(4)], first=flip)
+                found += 1
+                break
+    pos = np.asarray(tris, dtype=np.float64)
+    add_d = _draw(pos, _colors(rng, pos.shape[0] * 3, 0.25), depth_test=DepthTest.Always, blend=BlendMode.Additive)
+    alpha = _draw(pos, _colors(rng, pos.shape[0] * 3, 0.6), depth_test=DepthTest.LessEqual, blend=BlendMode.Alpha)
+    return [scenes.Scene(f"edges_f1_additive_{seed}", W, H, [add_d], clear_color=(0.0, 0.0, 0.0, 1.0)),
+            scenes.Scene(f"edges_f1_alpha_{seed}", W, H, [alpha], clear_color=(0.1, 0.2, 0.3, 1.0))]
+
+
+# ============================================================================ F2: hi-Z near ties
+def _triangulations(corners, centre, rng):
+    """Four triangulations of the quad corners (TL, TR, BR, BL) + centre point: both diagonals, a fan about the centre and a
+    T-junction split of one side (its midpoint is a vertex of two triangles and lies on the third's edge)."""
+    TL, TR, BR, BL = corners
+    mid = tuple((np.asarray(TL) + np.asarray(TR)) / 2.0)
+    return [
+        [(TL, TR, BR), (TL, BR, BL)],
+        [(TL, TR, BL), (TR, BR, BL)],
+        [(TL, TR, centre), (TR, BR, centre), (BR, BL, centre), (BL, TL, centre)],
+        [(TL, mid, BL), (mid, TR, BR), (mid, BR, BL)],
+    ]
+
+
+def _layers(name, W, H, corner_px, depth_of, depth_test, rng, n_layers, base_repeats=10):
+    """One planar surface drawn n_layers times (different triangulations), alpha 0.6, as one draw per layer; the first layer's
+    triangles base_repeats times over."""
+    TLp, TRp, BRp, BLp = corner_px
+    cx = sum(p[0] for p in corner_px) / 4.0
+    cy = sum(p[1] for p in corner_px) / 4.0
+    def vert(p):
+        return (*clip_pos(p[0], p[1], W, H), z_for_depth(depth_of(p[0], p[1])))
+    corners = [vert(p) for p in corner_px]
+    centre = vert((cx, cy))
+    tr = _triangulations(corners, centre, rng)
+    order = rng.permutation(len(tr))[:n_layers]
+    draws = []
+    for j, k in enumerate(order):
+        pos = np.asarray([list(t) for t in tr[k]], dtype=np.float64)
+        if j == 0 and base_repeats > 1:
+            # k_raster_c reads a tile's minimum depth at the start of each batch of pairs (<= 16 pairs, <= 2048 fragments): the
+            # first layer, repeated, fills more than a batch, so that the later layers meet a written tile
+            pos = np.tile(pos, (base_repeats, 1, 1))
+        draws.append(_draw(pos, _colors(rng, pos.shape[0] * 3, 0.6), depth_test=depth_test))
+    return draws
+
+
+def f2_hiz_near_ties(seed=0, W=64, H=64):
+    """Surfaces drawn 2-4 times: (a) fronto-parallel and very slightly tilted, ordinary size; (b) huge triangles (screen
+    coordinates 1e17..5e18) with depths 3e-8..1e-2, where d * invArea is subnormal; (c) depths around 1e30, where S crosses 1e30
+    and the bound switches off.  Each under Less and LessEqual."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for dt in (DepthTest.LessEqual, DepthTest.Less):
+        # (a) the quad overhangs the target so that every tile is covered by the first layer (hi-Z needs the tile's minimum)
+        for tilt in (0.0, 1e-7, 3e-6):
+            d0 = float(rng.uniform(0.3, 0.7))
+            gx, gy = tilt * rng.uniform(-1, 1), tilt * rng.uniform(-1, 1)
+            big = [(-9.0, -7.0), (W + 11.0, -5.0), (W + 7.0, H + 9.0), (-5.0, H + 13.0)]
+            draws = _layers("", W, H, big, lambda x, y: d0 + gx * x + gy * y, dt, rng, int(rng.integers(2, 5)))
+            out.append(scenes.Scene(f"edges_f2_plane_tilt{tilt:g}_{dt.name}_{seed}", W, H, draws))
+        # (b) huge: d * invArea subnormal
+        for j in range(3):
+            R = 10 ** rng.uniform(17, 18.6)
+            d0 = 10 ** rng.uniform(-7.5, -2)
+            ddx, ddy = d0 * rng.uniform(-1e-19, 1e-19, 2) * (j > 0)
+            big = [(-R * rng.uniform(0.6, 1), -R * rng.uniform(0.6, 1)), (R * rng.uniform(0.6, 1), -R * rng.uniform(0.6, 1)),
+                   (R * rng.uniform(0.6, 1), R * rng.uniform(0.6, 1)), (-R * rng.uniform(0.6, 1), R * rng.uniform(0.6, 1))]
+            draws = _layers("", W, H, big, lambda x, y: d0 + ddx * x + ddy * y, dt, rng, int(rng.integers(2, 5)))
+            out.append(scenes.Scene(f"edges_f2_huge{j}_{dt.name}_{seed}", W, H, draws))
+        # (c) S around 1e30
+        for e in (29.0, 30.5):
+            d0 = 10 ** e
+            big = [(-9.0, -7.0), (W + 11.0, -5.0), (W + 7.0, H + 9.0), (-5.0, H + 13.0)]
+            draws = _layers("", W, H, big, lambda x, y: d0 * (1.0 + 1e-7 * x), dt, rng, 3)
+            out.append(scenes.Scene(f"edges_f2_S1e{e:g}_{dt.name}_{seed}", W, H, draws))
+    return out
+
+
+# ============================================================================ F3: magnitude ladder
+LADDER = (1e2, 1e8, 3e14, 9.9e14, 1.01e15, 1e17, 1e19, 1e22, 9.9e29, 1.01e30, 1e33, 3e37)
+
+
+def f3_magnitude_ladder(seed=0, W=64, H=64):
+    """Triangles with a vertex on screen and two at distance R in LADDER (straddling binning's 1e15, the fast walk's and S's 1e30,
+    and the chain's overflow past ~2e19), visible as a wedge at the on-screen vertex.  Half use clip.w = 1 with huge clip.x/y,
+    half small clip.w (w_projection).  FlatColor (no NaN colours), depth Disabled + Additive, and LessEqual + Alpha."""
+    rng = np.random.default_rng(seed)
+    tris_w1, tris_sw = [], []
+    for R in LADDER:
+        got = 0
+        for _ in range(600):                  # past ~2e19 most orientations give NaN edge values: keep the visible ones
+            if got == 3:
+                break
+            a = np.array([rng.uniform(4, W - 4), rng.uniform(4, H - 4)])
+            if R < 1e18 or rng.uniform() < 0.3:
+                th = rng.uniform(0, 2 * np.pi)
+                spread = rng.uniform(0.2, 2.5)
+                u = np.array([np.cos(th), np.sin(th)])
+                v = np.array([np.cos(th + spread), np.sin(th + spread)])
+            else:
+                # axis-aligned far vertices: one product of an edge value is x * 0, so an overflowed edge value is +-Inf, not
+                # Inf - Inf = NaN, and the triangle stays visible with Inf in its chain
+                axes = [np.array(v, dtype=float) for v in ((1, 0), (0, 1), (-1, 0), (0, -1))]
+                i = int(rng.integers(0, 4))
+                u, v = axes[i], axes[(i + (1 if rng.uniform() < 0.5 else 3)) % 4] * (1.0 if rng.uniform() < 0.5 else rng.uniform(1, 2))
+            b = a + R * u * rng.uniform(1.0, 1.5)
+            c = a + R * v * rng.uniform(1.0, 1.5)
+            z = z_for_depth(float(rng.uniform(0.1, 0.9)))
+            tri = [(*clip_pos(*p, W, H), z) for p in (a, b, c)]
+            with np.errstate(all="ignore"):
+                t = Tri([np.array([x, y, zz, 1.0], dtype=F32) for x, y, zz in tri], W, H)
+                if not (t.ok and t.frame()[0].any()):
+                    continue
+            got += 1
+            tris_w1.append(tri)
+            # small clip.w: the far vertices are (n * w, w) with w = 2^-k, n the ndc of the same point
+            k = int(np.clip(np.ceil(np.log2(max(R / W, 1.0))), 0, 126))
+            w = 2.0 ** -k
+            tris_sw.append([(tri[0][0], tri[0][1], 1.0)] + [(float(F32(x)) * w, float(F32(y)) * w, w) for x, y, _ in tri[1:]])
+    out = []
+    for name, tris, proj in (("w1", tris_w1, None), ("smallw", tris_sw, w_projection(0.2))):
+        pos = np.asarray(tris, dtype=np.float64)
+        n = pos.shape[0] * 3
+        add = _draw(pos, _colors(rng, n, 0.2), proj, program=Program.FlatColor, depth_test=DepthTest.Disabled, blend=BlendMode.Additive)
+        le = _draw(pos, _colors(rng, n, 0.7), proj, program=Program.FlatColor, depth_test=DepthTest.LessEqual, blend=BlendMode.Alpha)
+        out.append(scenes.Scene(f"edges_f3_{name}_{seed}", W, H, [add, le], clear_color=(0.0, 0.0, 0.0, 1.0)))
+    return out
+
+
+# ============================================================================ F4: slivers
+def f4_slivers(seed=0, n=160, W=128, H=64):
+    """Needles 24..1500 px long (mostly off screen beyond the visible part), 1e-5..0.5 px wide, at shallow angles to a row or a
+    column: the float chain's noise exceeds the exact edge values there.  (A row of a triangle is one run all the same:
+    tests/test_raster_edges_host.py::test_f4_every_row_of_a_triangle_is_one_run says why.)"""
+    rng = np.random.default_rng(seed)
+    tris = []
+    for i in range(n):
+        a = np.array([rng.uniform(0, W), rng.uniform(0, H)])
+        th = rng.choice([1, -1]) * 10 ** rng.uniform(-3, -0.5) + (np.pi / 2 if i % 3 == 2 else 0.0) + (np.pi if rng.uniform() < 0.5 else 0.0)
+        L = 10 ** rng.uniform(np.log10(24), np.log10(1500))
+        d = np.array([np.cos(th), np.sin(th)])
+        b = a + L * d
+        h = 10 ** rng.uniform(-5, np.log10(0.5))
+        c = a + rng.uniform(0.2, 0.8) * L * d + h * np.array([-d[1], d[0]])
+        a = a - rng.uniform(0, 1) * L * d
+        z = z_for_depth(float(rng.uniform(0.2, 0.8)))
+        tris.append([(*clip_pos(*p, W, H), z) for p in (a, b, c)])
+    pos = np.asarray(tris, dtype=np.float64)
+    add = _draw(pos, _colors(rng, pos.shape[0] * 3, 0.3), program=Program.FlatColor, depth_test=DepthTest.Always, blend=BlendMode.Additive)
+    none = _draw(pos, _colors(rng, pos.shape[0] * 3, 1.0), depth_test=DepthTest.LessEqual, blend=BlendMode.None_)
+    return [scenes.Scene(f"edges_f4_additive_{seed}", W, H, [add], clear_color=(0.0, 0.0, 0.0, 1.0)),
+            scenes.Scene(f"edges_f4_none_{seed}", W, H, [none], clear_color=(0.0, 0.0, 0.0, 1.0))]
+
+
+# ============================================================================ F5: division and sqrt guards
+F5_EXPONENTS = (-127, -126, -100, -84, -83, -60, -41, -40, -39, -20, 0, 20, 39, 40, 41, 60, 83, 84, 100, 125, 126)
+
+
+def f5_guard_scale(seed=0, W=64, H=64, exponents=F5_EXPONENTS):
+    """The same visible triangles drawn with projection 2^k * I for k in `exponents`: the screen positions stay (x 2^k / 2^k is
+    exact while nothing underflows), Interpolate's divisors and clip values cross 2^+-40, 2^83 and 2^+-126.  Vertex normals point
+    opposite ways, so the interpolated world normal's length passes through 0 (the sqrt core's range, the 1e-6 renormalise
+    threshold).  Dust2LambertFog (fog range 1..25: the fog division sees clip.z * 2^k) and Gouraud."""
+    rng = np.random.default_rng(seed)
+    tris, nrm = [], []
+    # a, b symmetric about a pixel sample P, c far out on the perpendicular through P; normals u, -u, u: on the median the
+    # interpolated normal is (wa - wb + wc) u ~ wc u, so its length runs from 0 over 2^-20 and 1e-3 as the rows leave P
+    for m in (1e2, 1e3, 3e4, 1e6, 3e6):
+        P = np.array([int(rng.integers(12, W - 12)), int(rng.integers(12, H - 12))])
+        horizontal = rng.uniform() < 0.5
+        D = np.array([int(rng.integers(3, 12)), 0]) if horizontal else np.array([0, int(rng.integers(3, 12))])
+        perp = np.array([D[1], D[0]]) // max(D) * (1 if rng.uniform() < 0.5 else -1)
+        pts = [P - D, P + D, P + int(m) * perp]
+        z = [z_for_depth(float(rng.uniform(0.1, 0.9))) for _ in range(3)]
+        tris.append([(*clip_pos(*p, W, H), zz) for p, zz in zip(pts, z)])
+        n0 = rng.normal(size=3)
+        nrm.append([n0, -n0, n0])
+    pos = np.asarray(tris, dtype=np.float64).reshape(-1, 3)
+    normal = np.asarray(nrm, dtype=np.float64).reshape(-1, 3)
+    uv = rng.uniform(-2, 3, (pos.shape[0], 2))
+    out = []
+    tex = scenes.random_texture(16, seed, alpha=None)
+    for k in exponents:
+        proj = (np.eye(4) * 2.0 ** k).astype(F32)
+        draws = []
+        for prog in (Program.Dust2LambertFog, Program.Gouraud):
+            d = _draw(pos, _colors(rng, pos.shape[0], 0.7), proj, program=prog, normal=normal, uv=uv,
+                      depth_test=DepthTest.Always, blend=BlendMode.Alpha)
+            d.texture = 0
+            draws.append(d)
+        out.append(scenes.Scene(f"edges_f5_2^{k}_{seed}", W, H, draws, textures=[tex]))
+    return out
+
+
+# ============================================================================ F6: mixed depth tests in one flush
+def f6_mixed_depth_tests(seed=0, W=64, H=64):
+    """F2's ordinary layers (Less + LessEqual: hi-Z allowed) followed, in the same flush, by draws of surfaces BEHIND them
+    (smaller depth) under Greater, Always and Equal, and a last LessEqual layer again: a batch with any of those must not drop
+    pairs by hi-Z (depth_only_grows = 0)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    big = [(-9.0, -7.0), (W + 11.0, -5.0), (W + 7.0, H + 9.0), (-5.0, H + 13.0)]
+    for other in (DepthTest.Greater, DepthTest.Always, DepthTest.Equal):
+        # (Equal passes within 1e-6: a small depth keeps hi-Z's margin below that, so a wrong drop is possible)
+        d0 = float(rng.uniform(0.5, 0.7)) if other != DepthTest.Equal else 0.005
+        draws = _layers("", W, H, big, lambda x, y: d0, DepthTest.LessEqual, rng, 2)
+        draws += _layers("", W, H, big, lambda x, y: d0 + 1e-7 * x / W, DepthTest.Less, rng, 1)
+        behind = d0 - 0.25 if other != DepthTest.Equal else d0 - 6e-7
+        slope = 1e-3 / H if other != DepthTest.Equal else 0.0
+        draws += _layers("", W, H, big, lambda x, y: behind + slope * y, other, rng, 2)
+        draws += _layers("", W, H, big, lambda x, y: d0, DepthTest.LessEqual, rng, 1)
+        out.append(scenes.Scene(f"edges_f6_{other.name}_{seed}", W, H, draws))
+    return out
+
+
+FAMILIES = {"f1": f1_lattice_edges, "f2": f2_hiz_near_ties, "f3": f3_magnitude_ladder, "f4": f4_slivers,
+            "f5": f5_guard_scale, "f6": f6_mixed_depth_tests}
+
+
+def all_scenes(seed=0):
+    return [s for f in FAMILIES.values() for s in f(seed)]
+
+
+# ============================================================================ float32 restatement
+def transform4(v, m):
+    """Vector4.Transform, row-vector convention, the reference's (unfused) sum order."""
+    m = np.asarray(m, dtype=F32)
+    out = np.empty(4, dtype=F32)
+    for j in range(4):
+        r = F32(m[0, j] * v[0])
+        r = F32(r + F32(m[1, j] * v[1]))
+        r = F32(r + F32(m[2, j] * v[2]))
+        r = F32(r + F32(m[3, j] * v[3]))
+        out[j] = r
+    return out
+
+
+def clip_of(draw, i):
+    p = np.array([*draw.vertices["position"][i], 1.0], dtype=F32)
+    return transform4(transform4(transform4(p, draw.model), draw.view), draw.projection)
+
+
+class Tri:
+    """One triangle after DrawTriangle's setup (Rasterizer.cs:367-399) and RasterizeTriangle's (:411-447)."""
+
+    def __init__(self, clips, W, H):
+        self.ok = False
+        self.W, self.H = W, H
+        clips = [clips[2], clips[1], clips[0]]                         # outputs = { v2, v1, v0 } (:367)
+        self.clip_w = np.array([c[3] for c in clips], dtype=F32)
+        if any(c[3] <= 0 for c in clips):
+            raise ValueError("the families never need the near clipper")
+        sx, sy, d = np.zeros(3, F32), np.zeros(3, F32), np.zeros(3, F32)
+        for i, c in enumerate(clips):
+            invW = F32(F32(1.0) / c[3])
+            nx, ny, nz = F32(c[0] * invW), F32(c[1] * invW), F32(c[2] * invW)
+            if not (np.isfinite(nx) and np.isfinite(ny) and np.isfinite(nz)):
+                return
+            sx[i] = F32(F32(F32(nx * F32(0.5)) + F32(0.5)) * F32(W))
+            sy[i] = F32(F32(F32(1.0) - F32(F32(ny * F32(0.5)) + F32(0.5))) * F32(H))
+            d[i] = F32(F32(nz + F32(1.0)) * F32(0.5))
+        self.sx, self.sy, self.d = sx, sy, d
+        area = F32(F32(F32(sx[2] - sx[0]) * F32(sy[1] - sy[0])) - F32(F32(sy[2] - sy[0]) * F32(sx[1] - sx[0])))
+        if not area != 0:                                              # (:396 / :411; NaN passes, as in the reference)
+            return
+        self.area = area
+        self.inv_area = F32(F32(1.0) / area)
+        f2i = lambda f: 0 if f != f else int(max(min(f, 2147483647.0), -2147483648.0))
+        self.minX = max(f2i(np.floor(min(sx[0], sx[1], sx[2]))), 0)
+        self.maxX = min(f2i(np.ceil(max(sx[0], sx[1], sx[2]))), W - 1)
+        self.minY = max(f2i(np.floor(min(sy[0], sy[1], sy[2]))), 0)
+        self.maxY = min(f2i(np.ceil(max(sy[0], sy[1], sy[2]))), H - 1)
+        if np.isnan(sx).any() or np.isnan(sy).any():                   # (MathF.Min/Max propagate NaN -> (int)NaN = 0)
+            return
+        self.ok = self.minX <= self.maxX and self.minY <= self.maxY
+        # edge k: a12/b12 about vertex 1, a20/b20 about vertex 2, a01/b01 about vertex 0 (:445-447, :481-483)
+        self.ea = np.array([sy[1] - sy[2], sy[2] - sy[0], sy[0] - sy[1]], dtype=F32)
+        self.eb = np.array([sx[2] - sx[1], sx[0] - sx[2], sx[1] - sx[0]], dtype=F32)
+        self.rx = np.array([sx[1], sx[2], sx[0]], dtype=F32)
+        self.ry = np.array([sy[1], sy[2], sy[0]], dtype=F32)
+
+    def tiles(self):
+        if not self.ok:
+            return
+        for ty in range(self.minY // TILE, self.maxY // TILE + 1):
+            for tx in range(self.minX // TILE, self.maxX // TILE + 1):
+                r = self.rect(tx, ty)
+                if r is not None:
+                    yield tx, ty, r
+
+    def rect(self, tx, ty):
+        x0, y0 = tx * TILE, ty * TILE
+        sX, eX = max(self.minX, x0), min(self.maxX, min(x0 + TILE - 1, self.W - 1))
+        sY, eY = max(self.minY, y0), min(self.maxY, min(y0 + TILE - 1, self.H - 1))
+        return None if sX > eX or sY > eY else (sX, eX, sY, eY)
+
+    def chain(self, rect):
+        """The three edge values at every sample of rect, exactly as RasterizeTriangle steps them: start value (:481-483), row
+        steps b (:532-534) and column steps a (:527-529), each a float32 running sum in sequence.  Returns (3, rows, cols)."""
+        sX, eX, sY, eY = rect
+        nx, ny = eX - sX + 1, eY - sY + 1
+        out = np.empty((3, ny, nx), dtype=F32)
+        for k in range(3):
+            start = F32(F32(self.ea[k] * F32(F32(sX) - self.rx[k])) + F32(self.eb[k] * F32(F32(sY) - self.ry[k])))
+            col = np.full(ny, self.eb[k], dtype=F32); col[0] = start
+            rows = np.add.accumulate(col, dtype=F32)
+            grid = np.full((ny, nx), self.ea[k], dtype=F32); grid[:, 0] = rows
+            out[k] = np.add.accumulate(grid, axis=1, dtype=F32)
+        return out
+
+    def cover(self, rect):
+        """(inside mask, fragment depth, chain) of rect (:493-494, :496-502)."""
+        w = self.chain(rect)
+        inside = ((w[0] >= 0) & (w[1] >= 0) & (w[2] >= 0)) | ((w[0] <= 0) & (w[1] <= 0) & (w[2] <= 0))
+        wf = w * self.inv_area
+        depth = F32(F32(self.d[0] * wf[0]) + F32(self.d[1] * wf[1])) + F32(self.d[2] * wf[2])
+        return inside, depth.astype(F32), w
+
+    def frame(self):
+        """Coverage and depth of the whole target (one triangle, depth test Always)."""
+        cov = np.zeros((self.H, self.W), dtype=bool)
+        dep = np.full((self.H, self.W), FLOAT_MIN, dtype=F32)
+        for tx, ty, r in self.tiles():
+            inside, depth, _ = self.cover(r)
+            sX, eX, sY, eY = r
+            cov[sY:eY + 1, sX:eX + 1] |= inside
+            dep[sY:eY + 1, sX:eX + 1] = np.where(inside, depth, dep[sY:eY + 1, sX:eX + 1])
+        return cov, dep
+
+    # ---- the kernels' shortcuts, margins as parameters
+    def pair_may_cover(self, rect, margin=64.0):
+        """pair_may_cover (swr_binning.hip.h) with delta = margin * u * M'."""
+        sX, eX, sY, eY = (F32(v) for v in rect)
+        if not (np.abs(self.sx) < 1e15).all() or not (np.abs(self.sy) < 1e15).all():
+            return True
+        any_neg = any_pos = False
+        for k in range(3):
+            a, b = self.ea[k], self.eb[k]
+            dxs, dxe, dys, dye = sX - self.rx[k], eX - self.rx[k], sY - self.ry[k], eY - self.ry[k]
+            axs, axe, bys, bye = a * dxs, a * dxe, b * dys, b * dye
+            emax = F32(max(axs, axe) + max(bys, bye))
+            emin = F32(min(axs, axe) + min(bys, bye))
+            m = F32(F32(abs(a) * max(abs(dxs), abs(dxe))) + F32(abs(b) * max(abs(dys), abs(dye))))
+            delta = F32(m * F32(margin * U))
+            any_neg = any_neg or emax < -delta
+            any_pos = any_pos or emin > delta
+        return not (any_neg and any_pos)
+
+    def hiz_bound(self, rect, margin=64.0, underflow_term=True):
+        """k_cover's bound U (swr_raster_c.hip.h) with margin * u * S; underflow_term=False is the bound before T was added."""
+        sX, eX, sY, eY = (F32(v) for v in rect)
+        c = np.zeros(4, dtype=F32)
+        S = T = F32(0.0)
+        for k in range(3):
+            kk = F32(self.d[k] * self.inv_area)
+            dxs, dxe, dys, dye = sX - self.rx[k], eX - self.rx[k], sY - self.ry[k], eY - self.ry[k]
+            xs, xe, ys, ye = self.ea[k] * dxs, self.ea[k] * dxe, self.eb[k] * dys, self.eb[k] * dye
+            for j, e in enumerate((xs + ys, xe + ys, xs + ye, xe + ye)):
+                c[j] = F32(c[j] + F32(kk * F32(e)))
+            mk = F32(F32(abs(self.ea[k]) * max(abs(dxs), abs(dxe))) + F32(abs(self.eb[k]) * max(abs(dys), abs(dye))))
+            S = F32(S + F32(abs(kk) * mk))
+            T = F32(F32(F32(F32(mk + abs(kk)) + abs(self.d[k])) + F32(1.0)) + T)
+        Ub = F32(F32(max(c.max(), F32(-np.inf))) + F32(S * F32(margin * U)))
+        if underflow_term:
+            Ub = F32(Ub + F32(T * F32(2.0 ** -146)))
+        finite = S < 1e30 and not np.isnan(c).any()
+        return Ub if finite else F32(np.inf)
+
+    def fast_walk(self, rect):
+        """k_cover takes the min/max walk when the nine chain inputs are below 1e30."""
+        sX, _, sY, _ = rect
+        w = self.chain((sX, sX, sY, sY))[:, 0, 0]
+        vals = np.concatenate([self.ea, self.eb, w])
+        return bool((np.abs(vals) < 1e30).all())
+
+
+def triangles(draw, W, H):
+    """Tri objects of every triangle of a draw (index order)."""
+    with np.errstate(all="ignore"):
+        clips = [clip_of(draw, i) for i in range(draw.vertices.shape[0])]
+        idx = draw.indices.reshape(-1, 3)
+        return [Tri([clips[a], clips[b], clips[c]], W, H) for a, b, c in idx]

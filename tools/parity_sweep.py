@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Extended parity sweep (test infrastructure, not part of the suite): random scenes of the four generator families at random
 sizes / states, HIP path against the oracle (depth bit-exact, colour <= 1 ULP, identical counters), for SECONDS of wall time.
-usage: parity_sweep.py [SECONDS=420] [RNG_SEED=7]"""
+--edges adds the adversarial families of tests/edge_scenes.py (scenes at the binning / hi-Z / walk / guard bounds): a random
+family and seed every fifth round.
+usage: parity_sweep.py [--edges] [SECONDS=420] [RNG_SEED=7]"""
 import sys, time
 import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,13 +12,26 @@ import numpy as np
 import test_gpu_parity as T
 from softwarerenderer_amd import Device, scenes
 from softwarerenderer_amd.rasterizer import DepthTest, Program, BlendMode, CullMode
+EDGES = "--edges" in sys.argv
+if EDGES:
+    sys.argv.remove("--edges")
+    import edge_scenes
 dev = Device(0)
 SECONDS = float(sys.argv[1]) if len(sys.argv) > 1 else 420.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
 bad = n = 0; t0 = time.time()
 while time.time() - t0 < SECONDS:
-    kind = n % 4
+    kind = n % 5 if EDGES else n % 4
     seed = int(rng.integers(1, 1 << 30))
+    if kind == 4:
+        fam = list(edge_scenes.FAMILIES)[int(rng.integers(0, len(edge_scenes.FAMILIES)))]
+        for s in edge_scenes.FAMILIES[fam](seed % 100000):
+            try:
+                T.run_both(dev, s)
+            except AssertionError as e:
+                bad += 1; print("MISMATCH", fam, seed % 100000, s.name, str(e)[:300], flush=True)
+        n += 1
+        continue
     W, H = int(rng.integers(100, 900)), int(rng.integers(100, 700))
     if kind == 0:
         s = scenes.cfg2(W, H, int(rng.integers(200, 6000)), seed=seed, min_area=float(rng.uniform(1, 50)), max_area=float(rng.uniform(100, 60000)))
