@@ -299,7 +299,9 @@ def f5_guard_scale(seed=0, W=64, H=64, exponents=F5_EXPONENTS):
     """The same visible triangles drawn with projection 2^k * I for k in `exponents`: the screen positions stay (x 2^k / 2^k is
     exact while nothing underflows), Interpolate's divisors and clip values cross 2^+-40, 2^83 and 2^+-126.  Vertex normals point
     opposite ways, so the interpolated world normal's length passes through 0 (the sqrt core's range, the 1e-6 renormalise
-    threshold).  Dust2LambertFog (fog range 1..25: the fog division sees clip.z * 2^k) and Gouraud."""
+    threshold).  Dust2LambertFog (fog range 1..25: the fog division sees clip.z * 2^k) and Gouraud.
+    (Two programs under DepthTest.Always select the generic k_raster_c: this family exercises shade_fragment's guards only.  The
+    speculate-and-verify shaders of the specialised kernels have their own families in tests/shade_edge_scenes.py.)"""
     rng = np.random.default_rng(seed)
     tris, nrm = [], []
     # a, b symmetric about a pixel sample P, c far out on the perpendicular through P; normals u, -u, u: on the median the
@@ -382,12 +384,14 @@ def clip_of(draw, i):
 class Tri:
     """One triangle after DrawTriangle's setup (Rasterizer.cs:367-399) and RasterizeTriangle's (:411-447)."""
 
-    def __init__(self, clips, W, H):
+    def __init__(self, clips, W, H, clipper_keeps=False):
         self.ok = False
         self.W, self.H = W, H
         clips = [clips[2], clips[1], clips[0]]                         # outputs = { v2, v1, v0 } (:367)
         self.clip_w = np.array([c[3] for c in clips], dtype=F32)
-        if any(c[3] <= 0 for c in clips):
+        # clipper_keeps: the caller has checked that ClipTriangleAgainstNearPlane keeps all three vertices (clip.z >= near * clip.w
+        # for each, :112-113), so the triangle reaches DrawTriangle unchanged although a clip.w is negative (shade_edge_scenes S1)
+        if any(c[3] <= 0 for c in clips) and not clipper_keeps:
             raise ValueError("the families never need the near clipper")
         sx, sy, d = np.zeros(3, F32), np.zeros(3, F32), np.zeros(3, F32)
         for i, c in enumerate(clips):

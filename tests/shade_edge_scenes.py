@@ -1,0 +1,757 @@
+"""Adversarial scene families for the speculate-and-verify shaders (test helper; not part of the package).
+
+shade_dust2_fast and shade_phong4_fast (csrc/swr_raster.hip.h) run Interpolate and the fragment program as one straight-line block
+with every division / reciprocal / sqrt core unconditional, AND the conditions under which each core IS the IEEE operation into
+`safe`, and k_raster_c shades the whole chunk again with the guarded shade_fragment when any shaded lane was unsafe.  They run only
+in the specialised kernels that execute_batch (swr_api.hip) selects when EVERY draw of the batch has one program, BlendMode.Alpha
+and DepthTest.LessEqual.  The families below put fragments on both sides of every `safe` term:
+
+  S1  weights and clip.w: samples on edges and vertices (weight 0), weights below 2^-40, one clip.w of three across 2^-+40,
+      negative clip.w kept by the clipper so that (ra + rb) + rc cancels (to 0, below 2^-40, and with |N|^2 above 1e12)
+  S2  texture seam: constant, slowly varying and integer-crossing UVs at the wrap seam; 1x1, 1xN, Nx1, 37x53, 16x16; bilinear
+  S3  normal length: cancelling normals, zero / NaN / non-unit world normals
+  S4  fog: fog_end - clip_z exactly 0, quotients around 0 and 1, fog ranges across 2^-+40, 0, subnormal, negative, NaN, Inf
+  S5  uniforms and colours: non-finite / huge / subnormal light direction, NaN / Inf / -0 colours, subnormal products, alpha <= 0
+  S6  Phong cores: camera / light on the surface, mirror-opposite light and camera, a zero component, far lights, range, intensity
+  S7  mixed chunks: many triangles of <= 32 samples per tile, alternating safe and unsafe
+  S8  material identity: 70+ materials one bit apart in one batch, decoy representatives (no vertices, frustum-culled)
+
+Every family returns scenes in (pure, diluted) pairs: `pure` has one program with Alpha / LessEqual on every draw, so the
+specialised kernel is selected; `diluted` is the same draws plus one draw of another program whose triangle is entirely off
+screen, which keeps depth_only_grows and every visible word but falls to the generic kernel (predicted_kernel restates the chain).
+
+Geometry: most triangles are `cells`: right triangles with legs of 8 px at integer or quarter-pixel positions inside one
+16 x 16 tile, one per tile.  Their edge values and weights are exact dyadic rationals (area 64), so "exactly on an edge", "exactly
+at a vertex" and "clip_z exactly fog_end" are exact statements, not near misses.  The verification is per CHUNK (k_raster_c ballots
+`safe` over up to 64 consecutive fragments of a tile), so a term is only tested where it is the ONLY one failing in a whole
+triangle: cells that aim at one term sit off the lattice and keep every other operand ordinary.
+
+The second half restates Interpolate (Rasterizer.cs:566-707), fs_dust2 and fs_phong4 (oracle/swr_oracle.c) in numpy float32 and
+every `safe` term of the two fast shaders as a predicate with its threshold as a parameter.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+import edge_scenes as E
+from edge_scenes import F32, TILE, _draw, clip_pos
+from softwarerenderer_amd import scenes
+from softwarerenderer_amd.rasterizer import BlendMode, DepthTest, Program
+
+NAN, INF = float("nan"), float("inf")
+FLT_MAX = 3.4028234663852886e38
+DUST2, PHONG, GOURAUD = Program.Dust2LambertFog, Program.Phong4Point, Program.Gouraud
+LEG = 8
+
+
+# ============================================================================ construction helpers
+def zw_projection(zc):
+    """Row-vector matrix with clip = (x, y, zc, z): clip.w is the vertex's z and clip.z the constant zc, so that a vertex is
+    inside the near plane (clip.z >= near * clip.w) whenever clip.w <= zc / near -- negative clip.w included."""
+    m = np.zeros((4, 4), dtype=F32)
+    m[0, 0] = m[1, 1] = 1.0
+    m[2, 3] = 1.0
+    m[3, 2] = zc
+    return m
+
+
+def phong_uniforms():
+    u = scenes.default_uniforms()
+    u.camera_position[:] = (0.21, -0.13, 2.0)
+    lp = [(-0.6, 0.4, 1.5), (0.7, 0.45, 2.5), (-0.4, -0.5, 3.0), (0.5, -0.3, 1.25)]
+    lc = [(1.0, 0.9, 0.8), (0.6, 0.7, 1.0), (0.9, 0.5, 0.5), (0.5, 1.0, 0.6)]
+    for i in range(4):
+        u.lights[i].position[:] = lp[i]
+        u.lights[i].range = 9.0
+        u.lights[i].color[:] = lc[i]
+        u.lights[i].intensity = 1.5
+    return u
+
+
+def uniforms_for(program):
+    return phong_uniforms() if program == PHONG else scenes.default_uniforms()
+
+
+class Cells:
+    """Collects triangles for one draw.  A cell triangle has its right angle at pixel (16 cx + ox, 16 cy + oy) and legs of `leg`
+    px along +x and +y; `half` (the default) moves it by a quarter of a pixel: no sample lies on an edge, so no weight is 0 and the
+    triangle's chunk is not sent to the exact path by its weights alone (half=False: on the lattice, samples on edges and vertices).
+    Either way the weights are exact dyadic rationals."""
+
+    def __init__(self, W, H, rng, zc=None, model_scale=1.0):
+        self.W, self.H, self.rng, self.zc, self.model_scale = W, H, rng, zc, model_scale
+        self.pos, self.col, self.uv, self.nrm = [], [], [], []
+
+    @property
+    def n_cells(self):
+        return (self.W // TILE) * (self.H // TILE)
+
+    def tri_px(self, pts, z=0.0, cw=(1.0, 1.0, 1.0), uv=None, col=None, nrm=None, alpha=0.7):
+        rng = self.rng
+        z = [z] * 3 if np.isscalar(z) else list(z)
+        for k, (X, Y) in enumerate(pts):
+            nx, ny = clip_pos(X, Y, self.W, self.H)
+            if self.zc is None:
+                self.pos.append((nx, ny, z[k]))
+            else:                                   # clip = (x, y, zc, z): x = nx * w is exact for a power-of-two w
+                self.pos.append((float(F32(F32(nx) * F32(cw[k]))), float(F32(F32(ny) * F32(cw[k]))), cw[k]))
+        self.uv += list(uv) if uv is not None else [tuple(rng.uniform(0.05, 0.95, 2)) for _ in range(3)]
+        self.col += list(col) if col is not None else [(*rng.uniform(0.1, 1.0, 3), alpha) for _ in range(3)]
+        if nrm is None:
+            n = rng.normal(size=(3, 3)) * 0.3 + np.array([0.2, 0.3, 1.0])
+            nrm = [tuple(v) for v in n]
+        self.nrm += list(nrm)
+
+    def cell(self, k, *, leg=LEG, off=(4, 4), half=True, **kw):
+        nx = self.W // TILE
+        x0 = TILE * (k % nx) + off[0] + (0.25 if half else 0.0)
+        y0 = TILE * (k // nx) + off[1] + (0.25 if half else 0.0)
+        self.tri_px([(x0, y0), (x0 + leg, y0), (x0, y0 + leg)], **kw)
+
+    def draw(self, program, uniforms=None, texture=0):
+        with np.errstate(all="ignore"):
+            d = _draw(np.asarray(self.pos, dtype=np.float64), np.asarray(self.col, dtype=np.float64),
+                      None if self.zc is None else zw_projection(self.zc), program=program,
+                      normal=np.asarray(self.nrm, dtype=np.float64), uv=np.asarray(self.uv, dtype=np.float64))
+        if self.model_scale != 1.0:                 # world positions scaled by a power of two, the projection undoes it exactly
+            d.model = np.diag([self.model_scale] * 3 + [1.0]).astype(F32)
+            d.projection = d.projection.copy()
+            for i, j in ((0, 0), (1, 1), (2, 3)):
+                d.projection[i, j] = 1.0 / self.model_scale
+        d.texture = texture
+        d.uniforms = uniforms if uniforms is not None else uniforms_for(program)
+        return d
+
+
+def _texture(w, h, seed, zero_alpha=0.0):
+    rng = np.random.default_rng(seed + 1000 * w + h)
+    t = rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8)
+    t[..., 3] = np.where(rng.uniform(size=(h, w)) < zero_alpha, 0, np.maximum(t[..., 3], 1))
+    return t
+
+
+def _pair(name, W, H, draws, textures, bilinear=False):
+    """(pure, diluted): see the module docstring."""
+    other = DUST2 if draws[0].program == GOURAUD else GOURAUD
+    off = _draw([(5.0, 5.0, 0.0), (6.0, 5.0, 0.0), (5.0, 6.0, 0.0)], [(1.0, 1.0, 1.0, 1.0)] * 3, program=other)
+    off.texture = 0 if (textures and other == DUST2) else None
+    kw = dict(textures=textures, bilinear=bilinear, clear_color=(0.1, 0.2, 0.3, 1.0))
+    return [scenes.Scene(f"shade_{name}_pure", W, H, list(draws), **kw),
+            scenes.Scene(f"shade_{name}_diluted", W, H, list(draws) + [off], **kw)]
+
+
+def predicted_kernel(scene):
+    """execute_batch's selection chain (swr_api.hip) for a frame of built-in programs submitted as one batch, no wireframe."""
+    ds = scene.draws
+    def default(p):
+        return all(d.program == p and d.blend == BlendMode.Alpha and d.depth_test == DepthTest.LessEqual for d in ds)
+    if any(d.program == Program.DebugVaryings for d in ds):
+        return "debug_varyings"
+    if any(d.blend == BlendMode.None_ for d in ds):
+        return "generic_none"
+    if default(PHONG):
+        return "phong_default"
+    if any(d.program == PHONG for d in ds):
+        return "generic_phong"
+    if default(DUST2):
+        return "dust2_default"
+    if default(GOURAUD):
+        return "gouraud_default"
+    return "generic"
+
+
+def _far_apex(c, rng, m, z, nrm=None, lo=3, hi=9):
+    """F5's construction: a, b symmetric about a pixel sample P, the apex m px out on the perpendicular through P."""
+    P = np.array([int(rng.integers(12, c.W - 12)), int(rng.integers(12, c.H - 12))])
+    horizontal = rng.uniform() < 0.5
+    D = np.array([int(rng.integers(lo, hi)), 0]) if horizontal else np.array([0, int(rng.integers(lo, hi))])
+    perp = np.array([D[1], D[0]]) // max(D) * (1 if rng.uniform() < 0.5 else -1)
+    c.tri_px([tuple(P - D), tuple(P + D), tuple(P + m * perp)], z=z, nrm=nrm)
+
+
+# ============================================================================ S1: weights and clip.w
+def s1_weights(seed=0):
+    out = []
+    for program in (DUST2, PHONG):
+        rng = np.random.default_rng(seed)
+        tex = [_texture(16, 16, seed)]
+        # (a) random integer triangles inside a tile: every vertex is a sample (weights exactly 1, 0, 0), many edges hold samples
+        c = Cells(128, 128, rng)
+        for k in range(c.n_cells):
+            while True:
+                p = rng.integers(1, 15, (3, 2))
+                if (p[1, 0] - p[0, 0]) * (p[2, 1] - p[0, 1]) != (p[2, 0] - p[0, 0]) * (p[1, 1] - p[0, 1]):
+                    break
+            nx = c.W // TILE
+            base = np.array([TILE * (k % nx), TILE * (k // nx)])
+            c.tri_px([tuple(base + q) for q in p], z=float(rng.uniform(-0.5, 0.5)))
+        out += _pair(f"s1_lattice_{program.name}_{seed}", 128, 128, [c.draw(program)], tex)
+        # (b) one vertex 1e11..1e15 px away: its weight at the visible samples is (distance to the near edge) / that: around 2^-40
+        c = Cells(64, 64, rng)
+        for m in (1e11, 1e12, 3e12, 1e13, 3e13, 1e14, 1e15):
+            _far_apex(c, rng, m, [float(rng.uniform(-0.5, 0.5)) for _ in range(3)])
+        out += _pair(f"s1_far_{program.name}_{seed}", 64, 64, [c.draw(program)], tex)
+        # (c) ONE clip.w of the three across 2^-40 and 2^40
+        c = Cells(128, 128, rng, zc=0.25)
+        for k, e in enumerate((-42, -41, -40, -39, 39, 40, 41, 42, -127, -126, -100, -90, 90, 100, 126, 127)):
+            for j in range(2):
+                cw = [1.0, 1.0, 1.0]
+                cw[(k + j) % 3] = 2.0 ** e
+                c.cell(2 * k + j, cw=cw)
+        out += _pair(f"s1_perw_{program.name}_{seed}", 128, 128, [c.draw(program)], tex)
+        # (d) a negative clip.w that the clipper keeps (clip.z = 0.25 >= 0.1 * w): ra, rb, rc of mixed sign.  (1, -1, 1): inv_sum
+        # is exactly 0 where the middle weight is 1/2; the others cancel to within 2^-12 .. 2^-24 of it
+        # (the normalised weights are then ~ 1 / inv_sum: with distinct normals |N|^2 passes 1e12 while |inv_sum| >= 2^-40; with
+        # equal normals and every clip.w scaled by 2^20 |inv_sum| is below 2^-40 while |N|^2 stays ordinary)
+        # (world positions are scaled down by 2^-10 and 2^-30 so that the interpolated world position, ~ position / inv_sum, stays
+        # inside the Phong cores' range and these fragments fail no other term; the second draw's clip.z keeps clip.w ~ 2^20 inside)
+        c, cs = Cells(128, 128, rng, zc=0.25, model_scale=2.0 ** -10), Cells(128, 128, rng, zc=2.0 ** 18, model_scale=2.0 ** -30)
+        k = 0
+        # w0 is the right-angle vertex's weight: inv_sum * scale = w0 / wn + (1 - w0) vanishes at w0 = wn / (wn - 1).  On the lattice
+        # with wn = -1 that is w0 = 1/2, exactly; off the lattice w0 takes the values (2 j + 1) / 16 and wn = -(2 j + 1) / (15 - 2 j)
+        # cancels exactly (the division rounds to the dyadic value); times (1 + 2^-21) it leaves about 2^-22
+        e = 1.0 + 2.0 ** -21
+        for wn in (-1.0, -9.0 / 7.0, -9.0 / 7.0 * e, -13.0 / 3.0 * e, -7.0 / 9.0 * e, -5.0 / 11.0 * e, -11.0 / 5.0 * e, -3.0 / 13.0 * e):
+            for scale, equal in ((1.0, False), (1.0, True), (2.0 ** 20, True), (2.0 ** -1, False)):
+                for j in range(2):
+                    cw = [float(F32(wn)) * scale, scale, scale]
+                    (cs if scale > 2.0 else c).cell(k, cw=cw, half=wn != -1.0, nrm=[(0.0, 0.6, 0.8)] * 3 if equal else None)
+                    k += 1
+        out += _pair(f"s1_cancel_{program.name}_{seed}", 128, 128, [c.draw(program), cs.draw(program)], tex)
+    return out
+
+
+# ============================================================================ S2: texture seam
+SEAM = (-0.0, 0.0, -2.0 ** -25, -1e-9, 1.0 - 2.0 ** -24, 1.0, -1.0, 2.0 ** 24 - 1.0, 2.0 ** 24, 1e20, NAN, INF, -INF)
+S2_TEXTURES = ((1, 1), (1, 7), (7, 1), (37, 53), (16, 16))          # (width, height)
+S2_BILINEAR = ((36, 36), (30, 30))                                   # block-linear (multiple of 4) and row-major layouts
+
+
+def _s2_draw(program, rng):
+    c = Cells(128, 128, rng)
+    n = len(SEAM)
+    for k in range(n):                                               # constant u on the seam, ordinary v; and the transpose
+        c.cell(k, uv=[(SEAM[k], 0.3)] * 3)
+        c.cell(n + k, uv=[(0.3, SEAM[k])] * 3)
+        c.cell(2 * n + k, uv=[(SEAM[k], SEAM[(k + 5) % n])] * 3)
+        s = SEAM[k]
+        step = 2.0 ** -30 if s == 0 else abs(s) * 2.0 ** -22          # slowly varying: a few ULP across the triangle
+        c.cell(3 * n + k, uv=[(s, s), (s + step, s - step), (s - step, s + step)])
+    for j, i0 in enumerate((-2, -1, 0, 1, 2, 100, -100, 3, 0, 1, -1, 5)):    # crossing an integer inside the tile
+        c.cell(4 * n + j, uv=[(i0 - 0.2, i0 + 0.3), (i0 + 0.3, i0 - 0.1), (i0 - 0.1, i0 - 0.3)])
+    return c.draw(program)
+
+
+def s2_texture_seam(seed=0):
+    out = []
+    for program in (DUST2, PHONG):
+        for w, h in S2_TEXTURES:
+            rng = np.random.default_rng(seed)
+            out += _pair(f"s2_{w}x{h}_{program.name}_{seed}", 128, 128, [_s2_draw(program, rng)], [_texture(w, h, seed)])
+        for w, h in S2_BILINEAR:
+            rng = np.random.default_rng(seed)
+            out += _pair(f"s2_bilinear{w}_{program.name}_{seed}", 128, 128, [_s2_draw(program, rng)], [_texture(w, h, seed)],
+                         bilinear=True)
+    return out
+
+
+# ============================================================================ S3: normal length
+def s3_normal_length(seed=0):
+    out = []
+    for program in (DUST2, PHONG):
+        rng = np.random.default_rng(seed)
+        tex = [_texture(16, 16, seed)]
+        # F5's construction, pure: normals u, -u, u: |N| runs through 0 along the median
+        c = Cells(64, 64, rng)
+        for m in (1e2, 1e3, 3e4, 1e6, 3e6):
+            n0 = rng.normal(size=3)
+            _far_apex(c, rng, int(m), [float(rng.uniform(-0.8, 0.8)) for _ in range(3)], nrm=[tuple(n0), tuple(-n0), tuple(n0)], hi=12)
+        out += _pair(f"s3_cancel_{program.name}_{seed}", 64, 64, [c.draw(program)], tex)
+        # vertex normals whose normalised world normal is not a unit vector: 1e20 (|n|^2 overflows: n / Inf = 0), 0 (0 / 0 = NaN),
+        # 3e-23 (|n|^2 is a subnormal of one or two bits), a NaN or Inf component; and opposite unit normals in a small cell
+        # (u points against the default light direction: whether a short normal is renormalised decides diffuse = 1 or 0.25)
+        u = tuple(-float(v) for v in scenes.default_uniforms().light_direction)
+        mu = tuple(-v for v in u)
+        special = [[(1e20, 0, 0)] * 3, [(1e20, 0, 0), u, u], [(0, 0, 0)] * 3, [(0, 0, 0), u, u], [(3e-23, 0, 0)] * 3,
+                   [(3e-23, 2e-23, 0), u, u], [(NAN, 1, 0), u, u], [u, (INF, 1, 0), u], [u, mu, u], [u, u, mu], [mu, u, u],
+                   [(1e-3, 0, 0), (-1e-3, 0, 0), (0, 1e-3, 0)], [u, mu, (0.0, 1.0, 0.0)], [(0, 0, 1e19), u, mu],
+                   [(-INF, 0, 0)] * 3, [u, u, u]]
+        # 0 < |N|^2 <= 1e-6 off the lattice: at the sample with weights (10, 11, 11) / 32 the normals -a, R(+t) a, R(-t) a with
+        # 2 cos t = 10 / 11 (1 + eps) sum to (10 eps / 32) a: short, not zero, and along the light (renormalised: diffuse 1, not 0.25)
+        b = np.cross(np.array(u), np.array([0.0, 0.0, 1.0]))
+        b = b / np.linalg.norm(b)
+        for eps in (1e-5, 1e-4, 3e-4, 1e-3):
+            ct = 5.0 / 11.0 * (1.0 + eps)
+            st = np.sqrt(1.0 - ct * ct)
+            special.append([mu, tuple(ct * np.array(u) + st * b), tuple(ct * np.array(u) - st * b)])
+        c = Cells(128, 128, rng)
+        for k, n3 in enumerate(special):
+            c.cell(k, nrm=n3)
+        out += _pair(f"s3_special_{program.name}_{seed}", 128, 128, [c.draw(program)], tex)
+    return out
+
+
+# ============================================================================ S4: fog
+FOG_RANGES = (8.0, 0.0, 2.0 ** -41, -2.0 ** -41, 2.0 ** -40, 2.0 ** 40, 2.0 ** 41, 1e-40, -3.0, NAN, INF)
+
+
+def s4_fog(seed=0):
+    """fog_start = 0 and fog_end = R, so the range fog_end - fog_start is R exactly.  Identity matrices and cell triangles of
+    constant z: the interpolated clip.z is z exactly (dyadic weights), so z = R gives fog_end - clip_z == 0 on every sample, z = 0
+    the quotient 1, z = -R 2^-20 just above 1, z = R (1 + 2^-20) just below 0."""
+    rng = np.random.default_rng(seed)
+    draws = []
+    k = 0
+    for R in FOG_RANGES:
+        c = Cells(128, 128, rng)
+        if np.isfinite(R):
+            zs = [R, 0.0, -R * 2.0 ** -20, R * (1.0 + 2.0 ** -20), R * 0.5]
+        else:
+            zs = [0.0, 1.0, -1.0, 0.5, 2.0]
+        for z in zs:
+            c.cell(k, z=float(F32(z)))
+            k += 1
+        u = scenes.default_uniforms()
+        u.fog_start, u.fog_end = 0.0, R
+        draws.append(c.draw(DUST2, u))
+    return _pair(f"s4_fog_{seed}", 128, 128, draws, [_texture(16, 16, seed)])
+
+
+# ============================================================================ S5: uniforms and colours
+def s5_uniforms_and_colours(seed=0):
+    rng = np.random.default_rng(seed)
+    draws = []
+    k = 0
+    def variant(texture=0, **kw):
+        nonlocal k
+        c = Cells(128, 128, rng)
+        for _ in range(3):
+            c.cell(k, z=float(rng.uniform(0.5, 20.0)))
+            k += 1
+        u = scenes.default_uniforms()
+        for name, v in kw.items():
+            getattr(u, name)[:len(v)] = v
+        draws.append(c.draw(DUST2, u, texture=texture))
+    for ld in ((NAN, -0.5, -0.5), (0.5, INF, -0.5), (0.3, -0.5, -INF), (FLT_MAX, FLT_MAX, -FLT_MAX), (-FLT_MAX, 0.0, 0.0),
+               (1e-40, 1e-41, -1e-39), (-0.0, 0.0, -1.0)):
+        variant(light_direction=ld)
+    for name in ("light_color", "fog_color"):
+        for v in ((NAN, 1.0, 1.0), (1.0, INF, 0.5), (-0.0, 0.5, -0.0)):
+            variant(**{name: v})
+    variant(texture=None)                                             # no texture bound: the per-draw predicate says "exact path"
+    # colours: products with the texel in the subnormal range; alpha subnormal, 0 through the texel, negative, NaN
+    c = Cells(128, 128, rng)
+    g = (0.5, 0.6, 0.7)
+    cols = [[(1e-37, 3e-38, 1e-36, 0.7)] * 3, [(1e-37, 3e-38, 1e-36, 1e-40)] * 3, [(*g, 1e-40), (*g, 0.0), (*g, 1e-45)],
+            [(*g, -0.5)] * 3, [(*g, 0.5), (*g, -0.5), (*g, 0.5)], [(*g, NAN)] * 3, [(*g, 0.5), (*g, NAN), (*g, 0.5)],
+            [(NAN, 0.6, INF, 0.5)] * 3, [(*g, 0.0)] * 3]
+    for col in cols:
+        for uv in ([(0.05, 0.05), (0.9, 0.1), (0.1, 0.9)], None):
+            c.cell(k, col=col, uv=uv, z=float(rng.uniform(0.5, 20.0)))
+            k += 1
+    draws.append(c.draw(DUST2))
+    assert k <= 64
+    return _pair(f"s5_uniforms_{seed}", 128, 128, draws, [_texture(16, 16, seed, zero_alpha=0.3)])
+
+
+# ============================================================================ S6: Phong cores
+def s6_phong_cores(seed=0):
+    """A wall at world z = 0.25 (identity matrices: world position = model position), three cells per draw, one draw per case.
+    P is a sample inside the draw's first cell (off the lattice: no weight is 0), where the interpolated world position is P
+    exactly (dyadic weights and coordinates).  (The
+    "light whose x equals a wall's world x" of a 3-D scene is, for this screen-aligned wall, a light whose z equals the wall's z:
+    the same zero component of the light vector on every fragment.)"""
+    rng = np.random.default_rng(seed)
+    draws = []
+    k = 0
+    WZ = 0.25
+    def variant(fn, texture=0):
+        nonlocal k
+        c = Cells(128, 128, rng)
+        nx = c.W // TILE
+        px, py = clip_pos(TILE * (k % nx) + 6, TILE * (k // nx) + 6, c.W, c.H)
+        for _ in range(3):
+            c.cell(k, z=WZ, nrm=[(0.1, -0.2, 1.0)] * 3 if k % 2 else None)
+            k += 1
+        u = phong_uniforms()
+        fn(u, (px, py, WZ))
+        draws.append(c.draw(PHONG, u, texture=texture))
+    def cam_on_surface(u, P): u.camera_position[:] = P
+    def light_on_surface(u, P): u.lights[0].position[:] = P
+    def mirror(u, P):
+        u.camera_position[:] = (P[0] + 0.125, P[1] + 0.25, P[2] + 0.5)
+        u.lights[1].position[:] = (P[0] - 0.125, P[1] - 0.25, P[2] - 0.5)
+    def light_in_wall_plane(u, P): u.lights[2].position[:] = (0.3, 0.2, WZ)
+    def far_light(u, P):
+        u.lights[3].position[:] = (2.0 ** 21, 0.3, 1.0)
+        u.lights[3].range = 2.0 ** 22
+    def far_camera(u, P): u.camera_position[:] = (0.3, -2.0 ** 22, 1.0)
+    def near_light(u, P): u.lights[0].position[:] = (P[0] + 2.0 ** -22, P[1] + 2.0 ** -23, P[2] + 2.0 ** -22)
+    def nothing(u, P): pass
+    def tiny_light(u, P): u.lights[2].position[:] = (P[0] + 2.0 ** -70, P[1] + 2.0 ** -71, P[2])    # |Ld|^2 is a denormal at P
+    for fn in (cam_on_surface, light_on_surface, mirror, near_light, tiny_light, light_in_wall_plane, far_light, far_camera, nothing):
+        variant(fn)
+    for r in (0.0, 2.0 ** -41, 2.0 ** 41, -4.0, NAN):
+        def set_range(u, P, r=r): u.lights[int(abs(hash(repr(r)))) % 4].range = r
+        variant(set_range)
+    for inten in (NAN, INF):
+        def set_int(u, P, inten=inten): u.lights[1].intensity = inten
+        variant(set_int)
+    variant(nothing, texture=None)
+    assert k <= 64
+    out = _pair(f"s6_cores_{seed}", 128, 128, draws, [_texture(16, 16, seed)])
+    # near-clipped Phong triangles: the clipper's vertices carry their own varyings (not restated on the host: Tri has no clipper)
+    nc = scenes.near_clip_scene(256, 192, n_tris=60, seed=seed + 7, program=PHONG)
+    nc.draws[0].uniforms = phong_uniforms()
+    out += _pair(f"s6_nearclip_{seed}", 256, 192, nc.draws, nc.textures)
+    return out
+
+
+NOT_RESTATED = ("s6_nearclip",)
+
+
+# ============================================================================ S7: mixed chunks
+def s7_mixed_chunks(seed=0, rounds=6):
+    """Per 16 x 16 tile 4 * rounds triangles with legs of 6 px (28 samples), four disjoint ones per round (one per quadrant),
+    rounds stacked so that every fragment passes the depth test.  In turn: on the lattice (the samples on its edges and
+    vertices have a weight of exactly 0 and are unsafe, its interior is safe), off the lattice by half a pixel (all safe), off the
+    lattice with u = -1e-9 (all on the texture seam: unsafe).  k_raster_c packs a tile's fragments into chunks of up to 64 lanes in
+    this order (a chunk ends early at a pixel it already holds), so safe and unsafe lanes share chunks -- certainly inside each
+    lattice triangle, whose 28 fragments are consecutive -- and the re-shade has to replace the safe lanes' values with identical
+    ones.  Chunk membership is not observable from outside: this is a proxy (the host test counts tiles that hold both kinds of
+    fragment of one draw, which is necessary for a mixed chunk, not sufficient)."""
+    out = []
+    for program in (DUST2, PHONG):
+        rng = np.random.default_rng(seed)
+        c = Cells(64, 64, rng)
+        for t in range(c.n_cells):
+            for i in range(4 * rounds):
+                off = (8 * (i % 2) + int(rng.integers(0, 2)), 8 * ((i // 2) % 2) + int(rng.integers(0, 2)))
+                z = 0.5 - 0.01 * (i // 4)                   # (fragment depth is -(z + 1) / 2: a later round passes LessEqual)
+                kind = (i + i // 4) % 3
+                if kind == 0:
+                    c.cell(t, leg=6, off=off, half=False, z=z)
+                elif kind == 1:
+                    c.cell(t, leg=6, off=off, half=True, z=z)
+                else:
+                    c.cell(t, leg=6, off=off, half=True, z=z, uv=[(-1e-9, 0.4)] * 3)
+        out += _pair(f"s7_mixed_{program.name}_{seed}", 64, 64, [c.draw(program)], [_texture(16, 16, seed)])
+    return out
+
+
+FAMILIES = {"s1": s1_weights, "s2": s2_texture_seam, "s3": s3_normal_length, "s4": s4_fog, "s5": s5_uniforms_and_colours,
+            "s6": s6_phong_cores, "s7": s7_mixed_chunks}
+
+
+def all_scenes(seed=0, families=None):
+    return [s for name, f in FAMILIES.items() if families is None or name in families for s in f(seed)]
+
+
+def pairs(seed=0, families=None):
+    sc = all_scenes(seed, families)
+    return list(zip(sc[0::2], sc[1::2]))
+
+
+# ============================================================================ S8: fragment-stage identity (material sharing)
+def _flip(x, bit):
+    """The float32 x with one bit of its pattern flipped."""
+    return float((np.array([x], dtype=F32).view(np.uint32) ^ np.uint32(1 << bit)).view(F32)[0])
+
+
+def material_key(d):
+    """What execute_batch compares before two draws share fragment constants: program, blend, depth test, texture, uniform bytes."""
+    return (int(d.program), int(d.blend), int(d.depth_test), d.texture, bytes(d.uniforms))
+
+
+def s8_material_identity(seed=0, n=72):
+    """One batch of 3 + n + 4 DUST2 draws (Alpha, LessEqual) over the same pixels.  The n materials differ from the defaults in
+    exactly one field by exactly one bit each (fog_start, fog_end, one light colour channel, light direction z with -0.0 or 0.0
+    in x, a fog colour channel, or the other of two textures of equal size and different content plus one bit), n > 64 of them
+    distinct: the list of representatives overflows its cap.  In front of them three draws that must NOT become representatives
+    although their materials equal those of draws 3, 4, 5: a mesh with no vertices, a frustum-culled mesh that is culled (k_vertex
+    never writes its fog_r1 / fog_den) and one that is kept (inside the clip cube, alpha 0).  Behind them repeats of materials from before and after the cap.
+    Draws carry `frustum_cull`; scenes.Scene has no such switch, so the tests submit this family themselves."""
+    rng = np.random.default_rng(seed)
+    W = H = 64
+    textures = [_texture(16, 16, seed), _texture(16, 16, seed + 1)]
+    def material(i):
+        u = scenes.default_uniforms()
+        kind, bit = i % 6, 22 - (i // 6) % 12
+        tex = 0
+        if kind == 0:
+            u.fog_start = _flip(u.fog_start, bit)
+        elif kind == 1:
+            u.fog_end = _flip(u.fog_end, bit)
+        elif kind == 2:
+            u.light_color[(i // 6) % 3] = _flip(1.0, bit)
+        elif kind == 3:
+            u.light_direction[:] = (-0.0 if (i // 6) % 2 else 0.0, 0.0, _flip(-1.0, bit))
+        elif kind == 4:
+            tex = 1
+            u.fog_color[2] = _flip(0.5, bit)
+        else:
+            u.fog_color[1] = _flip(u.fog_color[1], bit)
+        return u, tex
+    def quad(i, u, tex, model=None, cull=False, empty=False, inside=False):
+        c = Cells(W, H, rng)
+        if not empty:
+            z = 16.0 - 0.18 * i                        # inside every material's fog range (a wrong fog_den shows); fragment depth is
+            # -(z + 1) / 2, so every later draw passes LessEqual
+            x0, x1 = 4.25 + (i % 3), 59.5 - (i % 5)
+            col = [(*rng.uniform(0.1, 1.0, 3), 0.5)] * 3
+            if inside:                                              # inside the clip cube (not culled), alpha 0: writes nothing
+                z, col = 0.5, [(0.5, 0.5, 0.5, 0.0)] * 3
+            c.tri_px([(x0, x0), (x1, x0), (x0, x1)], z=z, col=col)
+            c.tri_px([(x1, x0), (x1, x1), (x0, x1)], z=z, col=col)
+            d = c.draw(DUST2, u, texture=tex)
+        else:
+            I = np.eye(4, dtype=F32)
+            d = scenes.Draw(scenes.make_vertices(np.zeros((0, 3))), np.zeros(0, dtype=np.uint16), I, I, I, program=DUST2, uniforms=u,
+                            texture=tex, cull=E.CullMode.None_)
+        if model is not None:
+            d.model = model
+        d.frustum_cull = cull
+        return d
+    far = np.eye(4, dtype=F32)
+    far[3, 0] = 400.0                                               # row-vector translation: outside the clip cube, culled
+    draws = [quad(0, *material(0), empty=True), quad(1, *material(1), model=far, cull=True), quad(2, *material(2), cull=True, inside=True)]
+    draws += [quad(3 + i, *material(i)) for i in range(n)]
+    draws += [quad(3 + n + j, *material(i)) for j, i in enumerate((0, 10, n - 2, n - 1))]
+    return scenes.Scene(f"shade_s8_materials_{seed}", W, H, draws, textures=textures, clear_color=(0.1, 0.2, 0.3, 1.0))
+
+
+# ============================================================================ float32 restatement
+def _f2i(x):
+    """(int)float of .NET 9 on x64: saturating, NaN -> 0."""
+    x = np.asarray(x, dtype=F32)
+    out = np.zeros(x.shape, dtype=np.int64)
+    ok = ~np.isnan(x)
+    out[ok] = np.clip(np.trunc(x[ok].astype(np.float64)), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+    return out
+
+
+def _cmod(a, n):
+    """C's a % n (truncating) followed by the `if (x < 0) x += n` of Texture.Sample."""
+    r = np.fmod(a, n)
+    return np.where(r < 0, r + n, r)
+
+
+def dot3(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def mathf_max(a, b):
+    """MathF.Max(a, b) for a scalar a that is neither NaN nor a zero: NaN in b propagates."""
+    return np.where(np.isnan(b), b, np.maximum(a, b)).astype(F32)
+
+
+def math_clamp(v, lo, hi):
+    return np.where(v < lo, lo, np.where(v > hi, hi, v)).astype(F32)
+
+
+def mathf_max0(b):
+    """MathF.Max(0f, b): NaN propagates, -0 gives +0."""
+    return np.where(np.isnan(b), b, np.where(b > 0, b, F32(0.0))).astype(F32)
+
+
+def vertex_stage(draw):
+    """Per vertex: clip position, world normal = Normalize(TransformNormal(normal, model)), world position (Renderer.cs:830-846)."""
+    n = draw.vertices.shape[0]
+    clip = np.zeros((n, 4), F32); wn = np.zeros((n, 3), F32); wpos = np.zeros((n, 3), F32)
+    m = np.asarray(draw.model, dtype=F32)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            clip[i] = E.clip_of(draw, i)
+            wpos[i] = E.transform4(np.array([*draw.vertices["position"][i], 1.0], dtype=F32), m)[:3]
+            v = draw.vertices["normal"][i].astype(F32)
+            t = np.array([F32(F32(F32(m[0, j] * v[0]) + F32(m[1, j] * v[1])) + F32(m[2, j] * v[2])) for j in range(3)], dtype=F32)
+            ln = np.sqrt(F32(F32(F32(t[0] * t[0]) + F32(t[1] * t[1])) + F32(t[2] * t[2])))
+            wn[i] = t / ln
+    return clip, wn, wpos
+
+
+def texture_nearest(tex, tu, tv):
+    h, w = tex.shape[:2]
+    u = tu - _f2i(tu).astype(F32)
+    v = tv - _f2i(tv).astype(F32)
+    u = u + np.where(u < 0, F32(1), F32(0))
+    v = v + np.where(v < 0, F32(1), F32(0))
+    tx, ty = _f2i(u * F32(w)), _f2i(v * F32(h))                         # what the fast shaders test against the texture's size
+    x, y = _cmod(tx, w), _cmod(ty, h)
+    return tex[y, x].astype(F32) * F32(F32(1.0) / F32(255.0)), tx, ty
+
+
+def texture_bilinear(tex, tu, tv):
+    h, w = tex.shape[:2]
+    x, y = tu * F32(w) - F32(0.5), tv * F32(h) - F32(0.5)
+    x0, y0 = np.floor(x), np.floor(y)
+    fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+    ix0, iy0 = _cmod(_f2i(x0), w), _cmod(_f2i(y0), h)
+    ix1, iy1 = np.where(ix0 + 1 == w, 0, ix0 + 1), np.where(iy0 + 1 == h, 0, iy0 + 1)
+    i255 = F32(F32(1.0) / F32(255.0))
+    c00, c10, c01, c11 = (tex[yy, xx].astype(F32) * i255 for yy, xx in ((iy0, ix0), (iy0, ix1), (iy1, ix0), (iy1, ix1)))
+    one = F32(1.0)
+    top = c00 * (one - fx) + c10 * fx
+    bot = c01 * (one - fx) + c11 * fx
+    return top * (one - fy) + bot * fy
+
+
+def in_range(v, lo=2.0 ** -40, hi=2.0 ** 40):
+    """div_operand_safe (swr_device.h) with its two bounds as parameters."""
+    a = np.abs(v)
+    return (a >= F32(lo)) & (a <= F32(hi))
+
+
+class Shaded:
+    """Interpolate + the fragment program for the covered samples of one (triangle, tile rect), with every intermediate the
+    fast shaders' `safe` terms look at.  A, B, C = outputs[0..2] = vertices v2, v1, v0 of the triangle."""
+
+    def __init__(self, draw, stage, vidx, tri, rect, tex, bilinear):
+        with np.errstate(all="ignore"):
+            self._run(draw, stage, vidx, tri, rect, tex, bilinear)
+
+    def _run(self, draw, stage, vidx, tri, rect, tex, bilinear):
+        clip, wnv, wposv = stage
+        o = [int(vidx[2]), int(vidx[1]), int(vidx[0])]
+        inside, depth, w = tri.cover(rect)
+        self.inside, self.depth = inside, depth
+        wf = (w * tri.inv_area).astype(F32)[:, inside]                    # :498-500
+        self.wf = wf
+        nfrag = wf.shape[1]
+        cw = clip[o, 3]
+        self.cw = cw
+        u = draw.uniforms
+        one = F32(1.0)
+        ra, rb, rc = wf[0] / cw[0], wf[1] / cw[1], wf[2] / cw[2]          # :576-578
+        inv_sum = (ra + rb) + rc
+        w_ = one / inv_sum
+        self.inv_sum = inv_sum
+        def persp(a, b, c):
+            return ((a * ra + b * rb) + c * rc) * w_
+        V = draw.vertices
+        uv, col = V["uv"][o].astype(F32), V["color"][o].astype(F32)
+        tu, tv = persp(uv[0, 0], uv[1, 0], uv[2, 0]), persp(uv[0, 1], uv[1, 1], uv[2, 1])
+        color = np.stack([persp(col[0, i], col[1, i], col[2, i]) for i in range(4)], axis=1)
+        self.clip_z = persp(clip[o[0], 2], clip[o[1], 2], clip[o[2], 2])
+        wa, wb, wc = ra * w_, rb * w_, rc * w_
+        def bary(a, b, c):
+            return (a * wa + b * wb) + c * wc
+        n = [bary(wnv[o[0], i], wnv[o[1], i], wnv[o[2], i]) for i in range(3)]
+        self.len_sq = dot3(n, n)
+        renorm = self.len_sq > F32(1e-6)                                   # :684-688
+        s = one / np.sqrt(self.len_sq)
+        n = [np.where(renorm, c * s, c) for c in n]
+        wp = [bary(wposv[o[0], i], wposv[o[1], i], wposv[o[2], i]) for i in range(3)]
+        self.tx = self.ty = np.zeros(nfrag, np.int64)
+        if tex is None:
+            tc = np.ones((nfrag, 4), F32)
+        elif bilinear:
+            tc = texture_bilinear(tex, tu, tv)
+        else:
+            tc, self.tx, self.ty = texture_nearest(tex, tu, tv)
+        self.tex_w, self.tex_h = (tex.shape[1], tex.shape[0]) if tex is not None else (0, 0)
+        base = color * tc
+        if draw.program == DUST2:
+            ld = [F32(-F32(u.light_direction[i])) for i in range(3)]
+            diffuse = mathf_max(F32(0.25), dot3(n, ld))
+            self.fog_num = F32(u.fog_end) - self.clip_z
+            self.fog_den = F32(F32(u.fog_end) - F32(u.fog_start))
+            fog = math_clamp(self.fog_num / self.fog_den, F32(0.0), one)
+            fog = (fog * fog) * (F32(3.0) - F32(2.0) * fog)
+            sl = F32(0.1) + F32(0.9) * diffuse
+            rgb = []
+            for i in range(3):
+                lit = (base[:, i] * sl) * F32(u.light_color[i])
+                rgb.append(F32(u.fog_color[i]) * (one - fog) + lit * fog)
+            self.color = np.stack(rgb + [base[:, 3]], axis=1).astype(F32)
+        elif draw.program == PHONG:
+            self.units = []                     # (|v|^2, v) of every normalisation, in the order shade_phong4_fast runs them
+            def unit(v):
+                ll = dot3(v, v)
+                ln = np.sqrt(ll)
+                self.units.append((ll, v))
+                return [c / ln for c in v], ln
+            Vd = [F32(u.camera_position[i]) - wp[i] for i in range(3)]
+            Vn, _ = unit(Vd)
+            acc = [F32(0.1) * base[:, i] for i in range(3)]
+            self.ranges = []
+            for l in range(4):
+                L = u.lights[l]
+                Ld = [F32(L.position[i]) - wp[i] for i in range(3)]
+                Ln, dist = unit(Ld)
+                ndotl = mathf_max0(dot3(n, Ln))
+                att = math_clamp(one - dist / F32(L.range), F32(0.0), one)
+                self.ranges.append(F32(L.range))
+                att = att * att
+                Hn, _ = unit([Ln[i] + Vn[i] for i in range(3)])
+                sp = mathf_max0(dot3(n, Hn))
+                sp = sp * sp; sp = sp * sp; sp = sp * sp; sp = sp * sp
+                kk = F32(L.intensity) * att
+                for i in range(3):
+                    acc[i] = acc[i] + (base[:, i] * ndotl + sp) * (F32(L.color[i]) * kk)
+            self.color = np.stack(acc + [base[:, 3]], axis=1).astype(F32)
+        else:
+            self.color = color.astype(F32)
+
+    # ---- the `safe` terms of shade_dust2_fast / shade_phong4_fast, thresholds as parameters
+    def terms(self, program, lo=2.0 ** -40, hi=2.0 ** 40, len_lo=1e-6, len_hi=1e12):
+        n = self.wf.shape[1]
+        with np.errstate(all="ignore"):
+            a = np.abs(self.wf)
+            t = {
+                "fastdiv (three clip.w in range)": np.full(n, bool(in_range(self.cw, lo, hi).all())),
+                "weights in range": (a.min(axis=0) >= F32(lo)) & (((a[0] + a[1]) + a[2]) <= F32(hi)),
+                "|inv_sum| >= 2^-40": np.abs(self.inv_sum) >= F32(lo),
+                "texel index inside the texture": (self.tx >= 0) & (self.tx < self.tex_w) & (self.ty >= 0) & (self.ty < self.tex_h),
+                "len_sq > 1e-6": self.len_sq > F32(len_lo),
+                "len_sq <= 1e12": self.len_sq <= F32(len_hi),
+            }
+            if program == DUST2:
+                t["fog_num in range"] = in_range(self.fog_num, lo, hi)
+            else:
+                ok_ll = np.ones(n, bool); ok_v = np.ones(n, bool)
+                for ll, v in self.units:
+                    ok_ll &= in_range(ll, lo, hi)
+                    ok_v &= in_range(v[0], lo, hi) & in_range(v[1], lo, hi) & in_range(v[2], lo, hi)
+                t["unit(): |v|^2 in range"] = ok_ll
+                t["unit(): components in range"] = ok_v
+                t["light range in range"] = np.full(n, bool(all(in_range(r, lo, hi) for r in self.ranges)))
+        return t
+
+
+def draw_applies(draw, tex, bilinear, lo=2.0 ** -40, hi=2.0 ** 40):
+    """dust2_fast_applies / phong4_fast_applies as named conditions: a nearest texture is bound; and for DUST2 the fog range is in
+    the division core's range (k_vertex's fog_r1 != 0) and the light direction is finite."""
+    t = {"nearest texture bound": tex is not None and not bilinear}
+    if draw.program == DUST2:
+        u = draw.uniforms
+        with np.errstate(all="ignore"):
+            den = F32(F32(u.fog_end) - F32(u.fog_start))
+            ld = np.array(list(u.light_direction), dtype=F32)
+            t["fog range in range (fog_r1 != 0)"] = bool(in_range(den, lo, hi))
+            t["light direction finite"] = bool(np.isfinite(ld).all())
+    return t
+
+
+def shaded_fragments(scene, draw_indices=None):
+    """(draw index, triangle index, Tri, rect, Shaded) for every (triangle, tile) of the scene with a covered sample."""
+    near = F32(scene.near_clip)
+    for j, d in enumerate(scene.draws):
+        if draw_indices is not None and j not in draw_indices:
+            continue
+        stage = vertex_stage(d)
+        tex = scene.textures[d.texture] if d.texture is not None else None
+        for i, vid in enumerate(d.indices.reshape(-1, 3)):
+            cl = [stage[0][int(v)] for v in vid]
+            with np.errstate(all="ignore"):
+                if all(c[3] <= 0 for c in cl):
+                    continue
+                keeps = all(c[2] >= F32(near * c[3]) for c in cl)
+                if any(c[3] <= 0 for c in cl) and not keeps:
+                    raise ValueError("a triangle the near clipper would cut")
+                t = E.Tri(cl, scene.width, scene.height, clipper_keeps=keeps)
+                if not t.ok:
+                    continue
+                rects = [r for _, _, r in t.tiles() if t.cover(r)[0].any()]
+            for r in rects:
+                yield j, i, t, r, Shaded(d, stage, vid, t, r, tex, scene.bilinear)

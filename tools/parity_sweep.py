@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Extended parity sweep (test infrastructure, not part of the suite): random scenes of the four generator families at random
 sizes / states, HIP path against the oracle (depth bit-exact, colour <= 1 ULP, identical counters), for SECONDS of wall time.
---edges adds the adversarial families of tests/edge_scenes.py (scenes at the binning / hi-Z / walk / guard bounds): a random
-family and seed every fifth round.
+--edges adds the adversarial families of tests/edge_scenes.py (scenes at the binning / hi-Z / walk / guard bounds) and of
+tests/shade_edge_scenes.py (scenes at the guards of the speculate-and-verify shaders): a random family and seed every fifth round.
 usage: parity_sweep.py [--edges] [SECONDS=420] [RNG_SEED=7]"""
 import sys, time
 import os
@@ -15,7 +15,8 @@ from softwarerenderer_amd.rasterizer import DepthTest, Program, BlendMode, CullM
 EDGES = "--edges" in sys.argv
 if EDGES:
     sys.argv.remove("--edges")
-    import edge_scenes
+    import edge_scenes, shade_edge_scenes
+    EDGE_FAMILIES = {**edge_scenes.FAMILIES, **shade_edge_scenes.FAMILIES}
 dev = Device(0)
 SECONDS = float(sys.argv[1]) if len(sys.argv) > 1 else 420.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
@@ -24,8 +25,8 @@ while time.time() - t0 < SECONDS:
     kind = n % 5 if EDGES else n % 4
     seed = int(rng.integers(1, 1 << 30))
     if kind == 4:
-        fam = list(edge_scenes.FAMILIES)[int(rng.integers(0, len(edge_scenes.FAMILIES)))]
-        for s in edge_scenes.FAMILIES[fam](seed % 100000):
+        fam = list(EDGE_FAMILIES)[int(rng.integers(0, len(EDGE_FAMILIES)))]
+        for s in EDGE_FAMILIES[fam](seed % 100000):
             try:
                 T.run_both(dev, s)
             except AssertionError as e:
