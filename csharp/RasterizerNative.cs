@@ -155,6 +155,8 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_program_destroy(IntPtr ctx, int programId);
         [DllImport(Lib)] public static extern int swr_program_set_constants(IntPtr ctx, int programId, float* values, int n);
         [DllImport(Lib)] public static extern int swr_program_validate(byte* fragmentSource, byte* log, int logLen);
+        [DllImport(Lib)] public static extern int swr_program_create_vf(IntPtr ctx, byte* vertexSource, byte* fragmentSource, out int programId);
+        [DllImport(Lib)] public static extern int swr_program_validate_vf(byte* vertexSource, byte* fragmentSource, byte* log, int logLen);
     }
 
     // ---------------------------------------------------------------- numerics probe ----
@@ -364,8 +366,8 @@ namespace SoftwareRenderer
     // `input => FragmentShader(input, texture)`, Renderer.cs:450-459,830-860): it is recognised by its methods, and the
     // fields it closes over -- the Renderer's light / fog fields (Renderer.cs:39-44) and the captured Texture -- are read
     // through reflection, so Renderer.cs needs no edit.  A fragment method registered with its C++ restatement (Register, the
-    // porting guide in INTEGRATION.md) resolves to a user program compiled into the raster kernel.  Anything else returns false
-    // (managed path).
+    // porting guide in INTEGRATION.md) resolves to a user program compiled into the raster kernel; a (vertex, fragment) pair registered
+    // with both restatements resolves to a user program with a vertex kernel of its own.  Anything else returns false (managed path).
     public static class ShaderMap
     {
         static readonly BindingFlags Any = BindingFlags.Instance | BindingFlags.Public | BindingFlags.NonPublic;
@@ -387,6 +389,43 @@ namespace SoftwareRenderer
             lock (sources) { sources[method.Method] = source; programs.Remove(method.Method); }
         }
 
+        // A (vertex, fragment) delegate pair restated against the contract of swr.h (swr_vertex + swr_fragment): any Shaders.VertexShader
+        // -- a wind displacement, a billboard, a scrolling UV, a second transform -- with the fragment delegate it is used with.  Both
+        // halves read the same constants; compile errors name their half (vertex.hip:LINE: / fragment.hip:LINE:).  Matched by the two
+        // methods: TryResolve looks for the pair first.
+        static readonly Dictionary<(MethodInfo, MethodInfo), (string, string)> pairSources = new Dictionary<(MethodInfo, MethodInfo), (string, string)>();
+        static readonly Dictionary<(MethodInfo, MethodInfo), int> pairPrograms = new Dictionary<(MethodInfo, MethodInfo), int>();
+
+        public static unsafe void Register(Shaders.VertexShader vertexMethod, Shaders.FragmentShader fragmentMethod, string vertexSource, string fragmentSource)
+        {
+            byte[] vsrc = System.Text.Encoding.UTF8.GetBytes(vertexSource + "\0");
+            byte[] fsrc = System.Text.Encoding.UTF8.GetBytes(fragmentSource + "\0");
+            byte[] log = new byte[16384];
+            int rc;
+            fixed (byte* v = vsrc) fixed (byte* f = fsrc) fixed (byte* l = log) rc = Native.swr_program_validate_vf(v, f, l, log.Length);
+            if (rc == -1) throw new ArgumentException(System.Text.Encoding.UTF8.GetString(log).TrimEnd('\0'));
+            if (rc != 0) throw new NotSupportedException($"swr_program_validate_vf: {rc}");
+            var key = (vertexMethod.Method, fragmentMethod.Method);
+            lock (sources) { pairSources[key] = (vertexSource, fragmentSource); pairPrograms.Remove(key); }
+        }
+
+        static unsafe bool TryUserPair(Shaders.VertexShader vs, Shaders.FragmentShader fs, out int id)
+        {
+            id = 0;
+            if (vs == null || fs == null) return false;
+            lock (sources)
+            {
+                var key = (vs.Method, fs.Method);
+                if (!pairSources.TryGetValue(key, out (string, string) source)) return false;
+                if (pairPrograms.TryGetValue(key, out id)) return true;
+                byte[] vsrc = System.Text.Encoding.UTF8.GetBytes(source.Item1 + "\0");
+                byte[] fsrc = System.Text.Encoding.UTF8.GetBytes(source.Item2 + "\0");
+                fixed (byte* v = vsrc) fixed (byte* f = fsrc) SwrContext.Check(Native.swr_program_create_vf(SwrContext.Handle, v, f, out id));
+                pairPrograms[key] = id;
+                return true;
+            }
+        }
+
         static unsafe bool TryUserProgram(Shaders.FragmentShader fs, out int id)
         {
             id = 0;
@@ -406,6 +445,32 @@ namespace SoftwareRenderer
         public static bool TryResolve(Shaders.VertexShader vs, Shaders.FragmentShader fs, out SwrProgram program, out SwrUniforms uniforms, out IntPtr texture)
         {
             program = SwrProgram.Dust2LambertFog; uniforms = default; texture = IntPtr.Zero;
+            if (TryUserPair(vs, fs, out int pairId))
+            {
+                // a registered (vertex, fragment) pair: whatever the two delegates are.  The uniform block is the Renderer's fields when
+                // one of them belongs to a Renderer (else zeros: such programs take their inputs as constants), the texture the one the
+                // fragment closure captured.
+                program = (SwrProgram)pairId;
+                Renderer owner = vs.Target as Renderer ?? fs.Target as Renderer;
+                Texture tex = null;
+                if (fs.Target != null)
+                    foreach (FieldInfo f in fs.Target.GetType().GetFields(Any))
+                    {
+                        object v = f.GetValue(fs.Target);
+                        if (v is Texture t) tex = t;
+                        if (owner == null && v is Renderer r) owner = r;
+                    }
+                if (owner != null)
+                {
+                    uniforms.LightDirection = Get<Vector3>(owner, "LightDirection");
+                    uniforms.LightColor = Get<Vector4>(owner, "LightColor");
+                    uniforms.FogColor = Get<Vector4>(owner, "FogColor");
+                    uniforms.FogStart = Get<float>(owner, "FogStart");
+                    uniforms.FogEnd = Get<float>(owner, "FogEnd");
+                }
+                texture = tex?.Native?.Handle ?? IntPtr.Zero;
+                return true;
+            }
             if (vs?.Target is not Renderer renderer || vs.Method.Name != "VertexShader") return false;
             bool user = TryUserProgram(fs, out int userId);
             if (user) program = (SwrProgram)userId;                                // ids >= SWR_PROG_USER_BASE (256)

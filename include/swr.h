@@ -71,8 +71,9 @@ enum {
                                      * Rasterizer.Interpolate delivers them -- (ScreenCoords.x + Normal.x, ScreenCoords.y + Normal.y,
                                      * Barycentric.x + Normal.z, Barycentric.y + 0.5); Rasterizer.cs:390,598-613,638 */
 };
-/* USER fragment programs (any Shaders.FragmentShader delegate, restated in C++): swr_program_create compiles one at run time into
- * the raster kernel and returns an id >= SWR_PROG_USER_BASE, which the render calls accept as `program`. */
+/* USER programs (any Shaders.FragmentShader delegate, optionally with any Shaders.VertexShader delegate, restated in C++):
+ * swr_program_create / swr_program_create_vf compile one at run time into the raster kernel (and a vertex kernel) and return an
+ * id >= SWR_PROG_USER_BASE, which the render calls accept as `program`. */
 #define SWR_PROG_USER_BASE 256
 
 /* Shaders.VertexInput, Shaders.cs:10-24 -- 48 bytes, identical memory layout */
@@ -263,7 +264,7 @@ int  swr_render_mesh_culled(swr_context* ctx, const swr_mesh* mesh,
  * porting guide): the text defines
  *     __device__ float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
  * `in` = Shaders.VertexOutput after Rasterizer.Interpolate (Rasterizer.cs:566-640): clip_position, color, tex_coord, normal,
- * screen_coords, barycentric, world_normal (Data["WorldNormal"]); the vertex stage is Renderer.VertexShader (Renderer.cs:830-846,
+ * screen_coords, barycentric, world_normal (Data["WorldNormal"]), data4 (see swr_program_create_vf); the vertex stage is Renderer.VertexShader (Renderer.cs:830-846,
  * Interpolate = true).  `env` = the draw's uniforms, constants[64], the pixel x, y; helpers swr_sample (Texture.Sample), swr_has_texture,
  * swr_dot3, swr_lerp (this library's System.Numerics model), swr_max, swr_clamp (MathF.Max, Math.Clamp), swr_discard() (a null
  * result: W <= 0 or NaN writes nothing, Rasterizer.cs:511).  Compiled with this library's switches and its numerics model; the
@@ -281,6 +282,28 @@ int  swr_program_set_constants(swr_context* ctx, int program_id, const float* va
 /* compile only, without a context or a device: SWR_OK, SWR_ERR_INVALID_ARG (log = compiler messages, NUL-terminated, truncated to
  * log_len) or SWR_ERR_UNSUPPORTED */
 int  swr_program_validate(const char* fragment_source, char* log, int log_len);
+/* User VERTEX programs (any Shaders.VertexShader delegate, restated in C++) --------------------------------------------------------
+ * A user program is a (vertex, fragment) pair.  The vertex text defines
+ *     __device__ void swr_vertex(const swr_vs_in& in, const swr_vs_env& env, swr_vs_out& out);
+ * and is compiled into a vertex kernel of its own in the same code object as the program's raster kernels; it runs in place of the
+ * built-in vertex stage for the draws of this program.  `in` = Shaders.VertexInput (position, uv, normal, color).  `env` = model, view,
+ * projection (16 floats each, row-major as above), the draw's uniforms, and constants[64] -- the SAME constants the fragment half
+ * reads, captured when the draw is recorded.  `out` = new Shaders.VertexOutput(), all zeros: clip_position, color, tex_coord, normal,
+ * world_normal (Data["WorldNormal"], a Vector3 key) and data4, ONE Vector4 key of the program's own, which the fragment half reads as
+ * in.data4 -- lerped in the near-plane clipper like every varying (Shaders.cs:74-75), interpolated as (a * wa + b * wb) + c * wc with
+ * the normalised weights and nothing else (Rasterizer.cs:690-693).  A program without a vertex half reads data4 = (0, 0, 0, 0).
+ * Interpolate is true for every user program; a per-program Interpolate = false is out of scope, and so are further Data keys (a
+ * float or a Vector2 key interpolates like Vector4 components and can ride in data4).
+ * Helpers under this library's System.Numerics model and the context's run-time transform flags (swr_set_transform_fma):
+ * swr_transform(v, m, env) = Vector4.Transform, swr_transform_normal(n, m, env) = Vector3.TransformNormal, swr_normalize(v) =
+ * v / v.Length(), swr_dot3, swr_lerp: a restated Renderer.VertexShader gives the built-in stage's bits in every build and setting.
+ * swr_render_mesh_culled still tests the MESH's bounding sphere (the application's test, Renderer.cs:446-459), whatever the vertex
+ * program does; a draw with a vertex program is never dropped from a multi-GPU band by its bounding box.
+ * Compile errors name the half and the line in the caller's text: `vertex.hip:LINE:` or `fragment.hip:LINE:`.  A vertex text that
+ * does not define swr_vertex is SWR_ERR_INVALID_ARG.  vertex_source == NULL is Renderer.VertexShader, the built-in stage:
+ * swr_program_create(ctx, fs, id) == swr_program_create_vf(ctx, NULL, fs, id). */
+int  swr_program_create_vf(swr_context* ctx, const char* vertex_source, const char* fragment_source, int* program_id);
+int  swr_program_validate_vf(const char* vertex_source, const char* fragment_source, char* log, int log_len);
 
 int  swr_flush(swr_context* ctx);    /* execute recorded draws (asynchronous on the stream) */
 int  swr_sync(swr_context* ctx);     /* flush + wait for the stream */

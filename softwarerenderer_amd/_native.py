@@ -73,6 +73,7 @@ EXPORTS = [
     "swr_render_mesh_arrays", "swr_mesh_bounds", "swr_is_sphere_in_frustum", "swr_render_mesh_culled", "swr_flush", "swr_sync", "swr_interpolate", "swr_get_stats", "swr_reset_stats",
     "swr_profile_enable", "swr_profile_get", "swr_profile_reset", "swr_profile_raster_samples", "swr_device_name", "swr_debug_counters", "swr_selftest_division",
     "swr_program_create", "swr_program_destroy", "swr_program_set_constants", "swr_program_validate",
+    "swr_program_create_vf", "swr_program_validate_vf",
 ]
 
 _libs = {}
@@ -156,6 +157,8 @@ def load(name: str = None) -> C.CDLL:
         "swr_program_destroy": (I, [P, I]),
         "swr_program_set_constants": (I, [P, I, fp, I]),
         "swr_program_validate": (I, [C.c_char_p, C.c_char_p, I]),
+        "swr_program_create_vf": (I, [P, C.c_char_p, C.c_char_p, C.POINTER(I)]),
+        "swr_program_validate_vf": (I, [C.c_char_p, C.c_char_p, C.c_char_p, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

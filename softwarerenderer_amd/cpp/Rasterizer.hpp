@@ -50,6 +50,10 @@ public:
     void ResetStats() const { check(swr_reset_stats(ctx_)); }
     // user fragment programs (contract in swr.h): compile errors throw std::invalid_argument carrying the compiler's log
     int CompileProgram(const std::string& source) const { int id = 0; check(swr_program_create(ctx_, source.c_str(), &id)); return id; }
+    // ... with a vertex half (swr_vertex, include/swr.h): any Shaders.VertexShader restated in C++
+    int CompileProgram(const std::string& vertex_source, const std::string& source) const {
+        int id = 0; check(swr_program_create_vf(ctx_, vertex_source.c_str(), source.c_str(), &id)); return id;
+    }
     void DestroyProgram(int id) const { check(swr_program_destroy(ctx_, id)); }
     void SetProgramConstants(int id, const std::vector<float>& values) const {
         check(swr_program_set_constants(ctx_, id, values.empty() ? nullptr : values.data(), (int)values.size()));
@@ -67,6 +71,10 @@ struct Shaders {
     // any Shaders.FragmentShader restated in C++ against the contract of swr.h, compiled for `dev` (a user program)
     static ShaderProgram Custom(const Device& dev, const std::string& source, const swr_uniforms& uniforms = swr_uniforms{},
                                 const Texture* texture = nullptr, std::vector<float> constants = {});
+    // ... and any (Shaders.VertexShader, Shaders.FragmentShader) pair: the vertex half (swr_vertex) runs as a vertex kernel of its own
+    static ShaderProgram Custom(const Device& dev, const std::string& vertex_source, const std::string& source,
+                                const swr_uniforms& uniforms = swr_uniforms{}, const Texture* texture = nullptr,
+                                std::vector<float> constants = {});
 };
 static_assert(sizeof(Shaders::VertexInput) == 48, "VertexInput must match Shaders.cs:10-24");
 
@@ -100,6 +108,14 @@ inline ShaderProgram Shaders::Custom(const Device& dev, const std::string& sourc
                                      const Texture* texture, std::vector<float> constants) {
     ShaderProgram p;
     p.program = static_cast<Shaders::Program>(dev.CompileProgram(source));
+    p.uniforms = uniforms; p.texture = texture; p.constants = std::move(constants);
+    return p;
+}
+
+inline ShaderProgram Shaders::Custom(const Device& dev, const std::string& vertex_source, const std::string& source,
+                                     const swr_uniforms& uniforms, const Texture* texture, std::vector<float> constants) {
+    ShaderProgram p;
+    p.program = static_cast<Shaders::Program>(dev.CompileProgram(vertex_source, source));
     p.uniforms = uniforms; p.texture = texture; p.constants = std::move(constants);
     return p;
 }

@@ -102,13 +102,15 @@ struct RasterSet {
     bool raster_pending = false;      // raster_done has been recorded and the stream has not been drained since
 };
 
-// A user fragment program loaded on the context's device (swr_program_create): the two k_raster_c<SWR_PROG_CUSTOM> instantiations
-// (with / without BlendMode.None's row early-out) of its run-time compiled code object.  Shared by the context's table and every
+// A user program loaded on the context's device (swr_program_create / _vf): the two k_raster_c<SWR_PROG_CUSTOM> instantiations
+// (with / without BlendMode.None's row early-out) of its run-time compiled code object and, when it has a vertex half, the module's
+// k_vertex_user and the k_setup whose clipper lerps data4.w (swr_geometry.hip.h).  Shared by the context's table and every
 // recorded or in-flight draw that uses it: the module is unloaded when the last of them lets go, and a batch only lets go once its
 // kernels are known to be over (retire_batch / free_garbage).
 struct UserProg {
     hipModule_t mod = nullptr;
     hipFunction_t fn[2] = { nullptr, nullptr };     // [EARLYOUT]
+    hipFunction_t vertex_fn = nullptr, setup_fn = nullptr;   // programs with a vertex half only: launched instead of k_vertex / k_setup
     float constants[64] = {};                        // swr_program_set_constants: copied into each draw when it is recorded
     ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
 };
@@ -269,25 +271,37 @@ const RtcLib& rtc_lib() {
     return lib;
 }
 
-struct RtcCode { std::vector<char> code; std::string names[2]; };   // code object + mangled k_raster_c<SWR_PROG_CUSTOM> names [EARLYOUT]
+// code object + mangled names: k_raster_c<SWR_PROG_CUSTOM> [EARLYOUT], then (vertex half only) k_vertex_user and k_setup
+struct RtcCode { std::vector<char> code; std::string names[4]; bool has_vertex = false; };
 
-// Compiles a user fragment program into a gfx950 code object: SWR_OK, SWR_ERR_INVALID_ARG (log = the compiler's messages) or
-// SWR_ERR_UNSUPPORTED.  In-process cache keyed by the source (the switches are this library's own).
-int rtc_compile(const char* user_src, std::shared_ptr<const RtcCode>& out, std::string& log) {
+// Compiles a user program (vertex_src null: the fragment half alone, over the built-in vertex stage) into a gfx950 code object: SWR_OK,
+// SWR_ERR_INVALID_ARG (log = the compiler's messages, which name the half as vertex.hip:LINE: / fragment.hip:LINE:) or
+// SWR_ERR_UNSUPPORTED.  In-process cache keyed by both texts (the switches are this library's own).
+int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<const RtcCode>& out, std::string& log) {
     const RtcLib& R = rtc_lib();
     if (!R.ok) { log = R.why; return SWR_ERR_UNSUPPORTED; }
 #if defined(SWR_RTC_FLAGS)
     static std::mutex mu;
     static std::map<std::string, std::shared_ptr<const RtcCode>> cache;
-    const std::string key(user_src);
+    // (a fragment-only program's key is its text, so `create(fs)` and `create_vf(NULL, fs)` share an entry; '\1' cannot occur in either half's C++)
+    const std::string key = vertex_src ? std::string(vertex_src) + '\1' + user_src : std::string(user_src);
+    if (vertex_src && !strstr(vertex_src, "swr_vertex")) {
+        log = "vertex.hip: the vertex program must define `__device__ void swr_vertex(const swr_vs_in& in, const swr_vs_env& env, swr_vs_out& out)`";
+        return SWR_ERR_INVALID_ARG;
+    }
     {
         std::lock_guard<std::mutex> g(mu);
         auto it = cache.find(key);
         if (it != cache.end()) { out = it->second; return SWR_OK; }
     }
     // prelude (contract + helpers), the user's text under its own file name, then the kernel
-    const std::string src = std::string("#include \"swr_program.hip.h\"\n#line 1 \"fragment.hip\"\n") + user_src +
-                            "\n#line 1 \"swr_program_kernel\"\n#include \"swr_raster_c.hip.h\"\n";
+    // (with a vertex half: its text first, and behind the raster kernel the geometry header, which under SWR_USER_VERTEX defines
+    // k_vertex_user instead of k_vertex and a k_setup that carries data4.w through the clipper)
+    const std::string src = std::string("#include \"swr_program.hip.h\"\n") +
+                            (vertex_src ? std::string("#line 1 \"vertex.hip\"\n") + vertex_src + "\n" : std::string()) +
+                            "#line 1 \"fragment.hip\"\n" + user_src +
+                            "\n#line 1 \"swr_program_kernel\"\n#include \"swr_raster_c.hip.h\"\n" +
+                            (vertex_src ? "#include \"swr_geometry.hip.h\"\n" : "");
     // the Makefile's code-generation switches, this build's System.Numerics model, and the fenced LDS hand-offs (the unfenced ones are
     // verified per (hipcc, source) pair only, DESIGN.md section 8: a run-time compiled kernel is not that pair)
     std::vector<std::string> opts;
@@ -306,16 +320,19 @@ int rtc_compile(const char* user_src, std::shared_ptr<const RtcCode>& out, std::
     opts.push_back("-DSWR_WAVE_LDS_FENCE=1");
     opts.push_back("-DSWR_NUMERICS_FMA=" SWR_STR(SWR_NUMERICS_FMA));
     opts.push_back("-DSWR_DOT_PAIRWISE=" SWR_STR(SWR_DOT_PAIRWISE));
+    if (vertex_src) opts.push_back("-DSWR_USER_VERTEX=1");
     std::vector<const char*> copts;
     for (auto& o : opts) copts.push_back(o.c_str());
-    const std::string expr[2] = { "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, false>",
-                                  "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, true>" };
+    const std::string expr[4] = { "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, false>",
+                                  "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, true>",
+                                  "swr::k_vertex_user", "swr::k_setup" };
+    const int n_expr = vertex_src ? 4 : 2;
     hiprtcProgram prog = nullptr;
     if (R.create(&prog, src.c_str(), "swr_user_program.hip", k_rtc_n_headers, k_rtc_headers, k_rtc_header_names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return SWR_ERR_UNSUPPORTED;
     }
-    for (auto& e : expr) R.add_name(prog, e.c_str());
+    for (int k = 0; k < n_expr; ++k) R.add_name(prog, expr[k].c_str());
     const hiprtcResult cr = R.compile(prog, (int)copts.size(), copts.data());
     size_t ls = 0;
     log.clear();
@@ -326,7 +343,8 @@ int rtc_compile(const char* user_src, std::shared_ptr<const RtcCode>& out, std::
     }
     auto code = std::make_shared<RtcCode>();
     bool ok = cr == HIPRTC_SUCCESS;
-    for (int k = 0; ok && k < 2; ++k) {
+    code->has_vertex = vertex_src != nullptr;
+    for (int k = 0; ok && k < n_expr; ++k) {
         const char* mangled = nullptr;
         ok = R.lowered(prog, expr[k].c_str(), &mangled) == HIPRTC_SUCCESS && mangled;
         if (ok) code->names[k] = mangled;
@@ -343,14 +361,14 @@ int rtc_compile(const char* user_src, std::shared_ptr<const RtcCode>& out, std::
         }
     }
     if (!ok) {
-        if (log.empty()) log = "the fragment program did not compile";
+        if (log.empty()) log = "the program did not compile";
         return SWR_ERR_INVALID_ARG;
     }
     std::lock_guard<std::mutex> g(mu);
     out = cache.emplace(key, std::shared_ptr<const RtcCode>(code)).first->second;
     return SWR_OK;
 #else
-    (void)user_src; (void)out;
+    (void)vertex_src; (void)user_src; (void)out;
     return SWR_ERR_UNSUPPORTED;
 #endif
 }
@@ -602,6 +620,8 @@ static bool b_needs_vnorm(const Batch& b) {
 }
 static bool b_has_debug_varyings(const Batch& b) { return !b.draws.empty() && b.draws[0].p.program == SWR_PROG_DEBUG_VARYINGS; }
 static bool b_has_user_program(const Batch& b) { return !b.draws.empty() && b.draws[0].p.program >= SWR_PROG_USER_BASE; }
+// ... and that program has a vertex half: its k_vertex_user and k_setup run instead of the library's
+static bool b_has_user_vertex(const Batch& b) { return b_has_user_program(b) && b.draws[0].prog && b.draws[0].prog->vertex_fn; }
 const unsigned long long kMaxPairs = 1ull << 30;       // list entries per round (4 GiB of slot ids)
 
 // pairs every set in use can hold (the optimistic flush is checked against this on the device)
@@ -921,7 +941,7 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
     for (auto& d : b.draws) any_cull = any_cull || d.frustum_cull;
     const size_t off_bp = (off_tb + tblocks.size() * sizeof(BlockMap) + 255) & ~(size_t)255;     // per-draw bounds pointers
     const size_t off_vis = (off_bp + (any_cull ? nd * sizeof(void*) : 0) + 255) & ~(size_t)255;   // per-draw visibility words
-    const bool user = b_has_user_program(b);
+    const bool user = b_has_user_program(b), user_vertex = b_has_user_vertex(b);
     const size_t up_bytes = user ? user_consts_offset(b) + nd * 64 * sizeof(float) : off_vis + (any_cull ? nd * 4 : 0);
     if ((rc = ensure(c, S.d_upload, up_bytes))) return rc;
     if ((rc = ensure(c, S.d_vout, (size_t)(V + 4 * T) * sizeof(VOut)))) return rc;
@@ -982,23 +1002,45 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
     fp.near_clip = b.near_clip;
     if (!vblocks.empty()) {
         ScopedSpan sp(c, ST_VERTEX, F);
-        hipLaunchKernelGGL(k_vertex, dim3((unsigned)vblocks.size()), dim3(SWR_GEOM_BLOCK), 0, F,
-                           d_draws, d_vblocks, S.d_vout.as<VOut>(), d_visible,
-                           reinterpret_cast<float*>((char*)S.d_upload.p + offsetof(DrawParams, fog_r1)),
-                           dbgv ? S.d_vnorm.as<float4>() : (float4*)nullptr, S.d_tile_count.as<uint32_t>(), n_tiles,
-                           reinterpret_cast<uint32_t*>(S.d_order.as<uint4>() + n_tiles) + n_tiles);
-        SWR_HIP(c, hipGetLastError());
+        VOut* a_vout = S.d_vout.as<VOut>();
+        float* a_fog = reinterpret_cast<float*>((char*)S.d_upload.p + offsetof(DrawParams, fog_r1));
+        float4* a_vnorm = dbgv ? S.d_vnorm.as<float4>() : (float4*)nullptr;
+        uint32_t* a_zero = S.d_tile_count.as<uint32_t>();
+        uint32_t a_n_zero = n_tiles;
+        uint32_t* a_hist = reinterpret_cast<uint32_t*>(S.d_order.as<uint4>() + n_tiles) + n_tiles;
+        if (user_vertex) {      // the program's own vertex kernel, on the stream k_vertex would have used (same grid, same duties)
+            const float* a_consts = reinterpret_cast<const float*>((const char*)S.d_upload.p + user_consts_offset(b));
+            void* args[] = { &d_draws, &d_vblocks, &a_vout, &d_visible, &a_fog, &a_vnorm, &a_zero, &a_n_zero, &a_hist, &a_consts };
+            SWR_HIP(c, hipModuleLaunchKernel(b.draws[0].prog->vertex_fn, (unsigned)vblocks.size(), 1, 1, SWR_GEOM_BLOCK, 1, 1, 0, F, args, nullptr));
+        } else {
+            hipLaunchKernelGGL(k_vertex, dim3((unsigned)vblocks.size()), dim3(SWR_GEOM_BLOCK), 0, F,
+                               d_draws, d_vblocks, a_vout, d_visible, a_fog, a_vnorm, a_zero, a_n_zero, a_hist);
+            SWR_HIP(c, hipGetLastError());
+        }
     }
     const bool counts_clear = !vblocks.empty() && n_tiles != 0;      // k_vertex cleared the per-tile counters and the order histogram
     {
         ScopedSpan sp(c, ST_SETUP, F);
-        hipLaunchKernelGGL(k_setup, dim3((unsigned)tblocks.size()), dim3(SWR_GEOM_BLOCK), 0, F,
-                           d_draws, d_tblocks, (const VOut*)S.d_vout.as<VOut>(),
-                           S.d_vout.as<VOut>() + V, (uint32_t)V, S.d_recs.as<TriRec>(),
-                           c->d_slot_tb.as<unsigned long long>(), fp, c->d_counters.as<Counters>(),
-                           (const Ctrl*)c->d_ctrl.as<Ctrl>(), b.seq, count_stats, b.wireframe ? 1 : 0, d_visible,
-                           dbgv ? S.d_vnorm.as<float4>() : (float4*)nullptr);
-        SWR_HIP(c, hipGetLastError());
+        const VOut* a_vout = S.d_vout.as<VOut>();
+        VOut* a_pool = S.d_vout.as<VOut>() + V;
+        uint32_t a_pool_base = (uint32_t)V;
+        TriRec* a_recs = S.d_recs.as<TriRec>();
+        unsigned long long* a_tb = c->d_slot_tb.as<unsigned long long>();
+        Counters* a_counters = c->d_counters.as<Counters>();
+        const Ctrl* a_ctrl = c->d_ctrl.as<Ctrl>();
+        uint32_t a_seq = b.seq;
+        int a_count = count_stats, a_wire = b.wireframe ? 1 : 0;
+        float4* a_vnorm = dbgv ? S.d_vnorm.as<float4>() : (float4*)nullptr;
+        if (user_vertex) {      // the module's k_setup: the same kernel, whose clipper also lerps data4.w
+            void* args[] = { &d_draws, &d_tblocks, &a_vout, &a_pool, &a_pool_base, &a_recs, &a_tb, &fp, &a_counters, &a_ctrl, &a_seq,
+                             &a_count, &a_wire, &d_visible, &a_vnorm };
+            SWR_HIP(c, hipModuleLaunchKernel(b.draws[0].prog->setup_fn, (unsigned)tblocks.size(), 1, 1, SWR_GEOM_BLOCK, 1, 1, 0, F, args, nullptr));
+        } else {
+            hipLaunchKernelGGL(k_setup, dim3((unsigned)tblocks.size()), dim3(SWR_GEOM_BLOCK), 0, F,
+                               d_draws, d_tblocks, a_vout, a_pool, a_pool_base, a_recs, a_tb, fp, a_counters, a_ctrl, a_seq, a_count, a_wire,
+                               d_visible, a_vnorm);
+            SWR_HIP(c, hipGetLastError());
+        }
     }
     rc = bin_and_raster(c, S, F, b, cc, cd, 0, (uint32_t)(spt * T), mode, counts_clear);
     slot_submit(c);
@@ -1079,7 +1121,7 @@ int flush_locked(swr_context* c) {
         // edge's end points, not those two vertices' screen positions, so the program's ScreenCoords term is not available there
         for (auto& d : b.draws) if (d.mesh && d.mesh->transient) c->garbage.push_back(d.mesh);
         c->pend_verts = c->pend_tris = 0;
-        return fail(c, SWR_ERR_UNSUPPORTED, b_has_user_program(b) ? "user fragment programs are not available in DebugMode.Wireframe"
+        return fail(c, SWR_ERR_UNSUPPORTED, b_has_user_program(b) ? "user programs are not available in DebugMode.Wireframe"
                                                                    : "SWR_PROG_DEBUG_VARYINGS is not available in DebugMode.Wireframe");
     }
     b.seq = c->next_seq++;
@@ -1172,7 +1214,7 @@ int record_draw(swr_context* c, swr_mesh* mesh, const float* model, const float*
         auto it = c->progs.find(program);
         if (it == c->progs.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed user program id");
         if (c->debug_mode == SWR_DEBUG_WIREFRAME)
-            return fail(c, SWR_ERR_UNSUPPORTED, "user fragment programs are not available in DebugMode.Wireframe");
+            return fail(c, SWR_ERR_UNSUPPORTED, "user programs are not available in DebugMode.Wireframe");
         uprog = it->second;
     } else if (program < SWR_PROG_FLAT_COLOR || program > SWR_PROG_DEBUG_VARYINGS) {
         return fail(c, SWR_ERR_INVALID_ARG, "unknown program id");
@@ -1184,7 +1226,8 @@ int record_draw(swr_context* c, swr_mesh* mesh, const float* model, const float*
     if (c->W <= 0 || c->H <= 0) return SWR_OK;                      // Rasterizer.cs:176
     const int n_tris = mesh->n_idx / 3;                             // Rasterizer.cs:180
     if (n_tris == 0) return SWR_OK;
-    if (band_rejects(c, mesh, model, view, proj)) return SWR_OK;      // nothing of it can land in this band
+    // (nothing of it can land in this band -- unless a vertex program moves the vertices: the box says nothing then, the draw is kept)
+    if (!(uprog && uprog->vertex_fn) && band_rejects(c, mesh, model, view, proj)) return SWR_OK;
     // one batch holds fewer than 2^26 vertex-stage records (one per vertex + four per triangle for the clipper: k_raster_c addresses
     // them with 32-bit byte offsets); a batch of several draws is flushed in time below, a SINGLE draw beyond it cannot be helped
     if ((uint64_t)mesh->n_verts + 4 * (uint64_t)n_tris >= (1ull << 26))
@@ -1885,11 +1928,13 @@ int swr_is_sphere_in_frustum(swr_context* c, const float center_radius[4], const
     return SWR_OK;
 }
 
-int swr_program_validate(const char* src, char* log, int log_len) {
+int swr_program_validate(const char* src, char* log, int log_len) { return swr_program_validate_vf(nullptr, src, log, log_len); }
+
+int swr_program_validate_vf(const char* vertex_src, const char* src, char* log, int log_len) {
     if (!src) return SWR_ERR_INVALID_ARG;
     std::shared_ptr<const RtcCode> code;
     std::string msg;
-    const int rc = rtc_compile(src, code, msg);
+    const int rc = rtc_compile(vertex_src, src, code, msg);
     if (log && log_len > 0) {
         const size_t n = std::min(msg.size(), (size_t)log_len - 1);
         memcpy(log, msg.data(), n); log[n] = '\0';
@@ -1897,16 +1942,22 @@ int swr_program_validate(const char* src, char* log, int log_len) {
     return rc;
 }
 
-int swr_program_create(swr_context* c, const char* src, int* program_id) {
+int swr_program_create(swr_context* c, const char* src, int* program_id) { return swr_program_create_vf(c, nullptr, src, program_id); }
+
+int swr_program_create_vf(swr_context* c, const char* vertex_src, const char* src, int* program_id) {
     SWR_ENTER(c);
     if (!src || !program_id) return fail(c, SWR_ERR_INVALID_ARG, "null argument to swr_program_create");
     std::shared_ptr<const RtcCode> code;
     std::string log;
-    const int rc = rtc_compile(src, code, log);
+    const int rc = rtc_compile(vertex_src, src, code, log);
     if (rc) { c->err = log; return rc; }
     auto p = std::make_shared<UserProg>();
     SWR_HIP(c, hipModuleLoadData(&p->mod, code->code.data()));
     for (int k = 0; k < 2; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
+    if (code->has_vertex) {
+        SWR_HIP(c, hipModuleGetFunction(&p->vertex_fn, p->mod, code->names[2].c_str()));
+        SWR_HIP(c, hipModuleGetFunction(&p->setup_fn, p->mod, code->names[3].c_str()));
+    }
     const int id = c->next_prog++;
     c->progs[id] = std::move(p);
     *program_id = id;

@@ -19,6 +19,7 @@ namespace swr {
 // so the draw's matrices are wave-uniform (scalar loads)
 struct BlockMap { uint32_t draw; uint32_t first; };
 
+#ifndef SWR_USER_VERTEX
 __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_vertex(const DrawParams* __restrict__ draws,
                                                 const BlockMap* __restrict__ blocks,
                                                 VOut* __restrict__ vout, const uint32_t* __restrict__ visible,
@@ -99,9 +100,94 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_vertex(const DrawParams* __r
         }
     }
 }
+#else   // SWR_USER_VERTEX: the code object of a user program with a vertex half (swr_program_create_vf), compiled at run time
+// k_vertex with the user's swr_vertex (swr_program.hip.h) in place of Renderer.VertexShader: launched instead of k_vertex for the
+// batches of that program (a batch holds the draws of one program).  Every other duty of k_vertex is kept as it is there -- the
+// counters and the tile-order histogram cleared, fog_r1 / fog_den written by the draw's first thread, the visible[] return, the
+// LDS-staged loads and stores -- because the rest of the flush relies on them.  swr_vs_out::data4 leaves in VOut::wpos (xyz: user
+// programs have no Data["WorldPos"]) and in .w of the Normal side array, which user batches always carry: no new buffer, no wider
+// record, and the clipper's lerp of wpos is already Vector4.Lerp of three of its components.
+__global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_vertex_user(const DrawParams* __restrict__ draws,
+                                                const BlockMap* __restrict__ blocks,
+                                                VOut* __restrict__ vout, const uint32_t* __restrict__ visible,
+                                                float* __restrict__ fog_r1_of_draw0,
+                                                float4* __restrict__ vnorm /* never null here */,
+                                                uint32_t* __restrict__ zero_words, uint32_t n_zero,
+                                                uint32_t* __restrict__ zero_hist,
+                                                const float* __restrict__ user_consts /* 64 captured constants per draw */) {
+    SWR_FRONT_ENTER();
+    for (uint32_t i = blockIdx.x * (uint32_t)SWR_GEOM_BLOCK + threadIdx.x; i < n_zero; i += gridDim.x * (uint32_t)SWR_GEOM_BLOCK) zero_words[i] = 0u;
+    if (blockIdx.x == 0) for (uint32_t i = threadIdx.x; i < 512u; i += (uint32_t)SWR_GEOM_BLOCK) zero_hist[i] = 0u;
+    const BlockMap bm = blocks[blockIdx.x];
+    if (visible && !visible[bm.draw]) return;
+    const DrawParams* __restrict__ dp = draws + bm.draw;
+    const uint32_t local = bm.first + threadIdx.x;
+    __shared__ float4 s_out[SWR_GEOM_BLOCK / 64][256];      // (see k_vertex: three 1 KB loads and four 1 KB stores per wave)
+    static_assert(sizeof(s_out) <= SWR_FRONT_MAX_LDS, "k_vertex_user must fit beside the raster kernel (swr_device.h)");
+    float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0, o2 = o0, o3 = o0;
+    const bool live = local < dp->n_verts;
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t first = bm.first + wv * 64u;                // first vertex of the wave
+    const uint32_t n_live = dp->n_verts > first ? min(dp->n_verts - first, 64u) : 0u;
+    float4* sw = &s_out[wv][0];
+    {
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(dp->verts + first);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t e = (uint32_t)k * 64u + lane;
+            if (e < 3u * n_live) sw[e] = src[e];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (live) {
+        if (local == 0u) {
+            const float den = dp->u.fog_end - dp->u.fog_start;
+            fog_r1_of_draw0[(size_t)bm.draw * (sizeof(DrawParams) / sizeof(float))] = div_operand_safe(den) ? rcp_refined(den) : 0.0f;
+            fog_r1_of_draw0[(size_t)bm.draw * (sizeof(DrawParams) / sizeof(float)) + 3] = den;      // DrawParams::fog_den
+        }
+        const float4 q0 = sw[3 * lane], q1 = sw[3 * lane + 1], q2 = sw[3 * lane + 2];   // pos.xyz uv.x | uv.y normal.xyz | color
+        swr_vs_in in;
+        in.position = make_float3(q0.x, q0.y, q0.z);
+        in.uv = make_float2(q0.w, q1.x);
+        in.normal = make_float3(q1.y, q1.z, q1.w);
+        in.color = q2;
+        // all uniform over the block: the matrices, the uniform block and the constants are read with scalar loads
+        const swr_vs_env env = { dp->model, dp->view, dp->proj, dp->u, user_consts + 64u * bm.draw, dp->nm_flags };
+        swr_vs_out out;
+        out.clip_position = make_float4(0.f, 0.f, 0.f, 0.f); out.color = make_float4(0.f, 0.f, 0.f, 0.f);
+        out.tex_coord = make_float2(0.f, 0.f); out.normal = make_float3(0.f, 0.f, 0.f);
+        out.world_normal = make_float3(0.f, 0.f, 0.f); out.data4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        swr_vertex(in, env, out);
+        o0 = out.clip_position;
+        o1 = out.color;
+        o2 = make_float4(out.tex_coord.x, out.tex_coord.y, out.world_normal.x, out.world_normal.y);
+        o3 = make_float4(out.world_normal.z, out.data4.x, out.data4.y, out.data4.z);
+        vnorm[dp->vert_base + local] = make_float4(out.normal.x, out.normal.y, out.normal.z, out.data4.w);
+    }
+    {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (the input vertices above have been read by every lane)
+        __builtin_amdgcn_wave_barrier();
+        sw[4 * lane + 0] = o0; sw[4 * lane + 1] = o1; sw[4 * lane + 2] = o2; sw[4 * lane + 3] = o3;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // one wave: its own LDS accesses complete in order
+        __builtin_amdgcn_wave_barrier();
+        float4* dst = reinterpret_cast<float4*>(vout + dp->vert_base + first);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t e = (uint32_t)k * 64u + lane;
+            if ((e >> 2) < n_live) dst[e] = sw[e];
+        }
+    }
+}
+#endif
 
 // a vertex moving through clip + setup: the stored varyings plus the Interpolate flag
-struct SVert { VOut v; bool interp; float nrm[3]; /* VertexOutput.Normal: carried only when the batch stores it (vnorm) */ };
+struct SVert {
+    VOut v; bool interp; float nrm[3]; /* VertexOutput.Normal: carried only when the batch stores it (vnorm) */
+#ifdef SWR_USER_VERTEX
+    float d4w;      // swr_vs_out::data4.w (.w of the vnorm entry; data4.xyz is v.wpos): only in the k_setup of a program with a vertex half
+#endif
+};
 
 __device__ __forceinline__ void svert_lerp(const SVert& a, const SVert& b, float t, SVert& r) {
     // Shaders.Lerp(a, b, t, interpolate: true), Shaders.cs:50-95 (the clipper always passes true)
@@ -117,6 +203,9 @@ __device__ __forceinline__ void svert_lerp(const SVert& a, const SVert& b, float
     for (int i = 0; i < 3; ++i) r.v.wpos[i] = nm_lerp(a.v.wpos[i], b.v.wpos[i], t);
 #pragma unroll
     for (int i = 0; i < 3; ++i) r.nrm[i] = nm_lerp(a.nrm[i], b.nrm[i], t);           // Vector3.Lerp(a.Normal, b.Normal, t), Shaders.cs:55
+#ifdef SWR_USER_VERTEX
+    r.d4w = nm_lerp(a.d4w, b.d4w, t);       // Vector4.Lerp of the user's key, Shaders.cs:74-75 (its xyz: wpos above)
+#endif
     r.interp = true;
 }
 
@@ -284,8 +373,14 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_setup(const DrawParams* __re
                     v[0].nrm[0] = n0.x; v[0].nrm[1] = n0.y; v[0].nrm[2] = n0.z;
                     v[1].nrm[0] = n1.x; v[1].nrm[1] = n1.y; v[1].nrm[2] = n1.z;
                     v[2].nrm[0] = n2.x; v[2].nrm[1] = n2.y; v[2].nrm[2] = n2.z;
+#ifdef SWR_USER_VERTEX
+                    v[0].d4w = n0.w; v[1].d4w = n1.w; v[2].d4w = n2.w;
+#endif
                 } else {
                     for (int i = 0; i < 3; ++i) v[i].nrm[0] = v[i].nrm[1] = v[i].nrm[2] = 0.0f;
+#ifdef SWR_USER_VERTEX
+                    for (int i = 0; i < 3; ++i) v[i].d4w = 0.0f;
+#endif
                 }
                 // ClipTriangleAgainstNearPlane, Rasterizer.cs:95-160
                 SVert poly[4];
@@ -315,7 +410,11 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_setup(const DrawParams* __re
                     VOut* pool = clip_pool + 4ull * gt;
                     const uint32_t pbase = clip_pool_base + 4u * gt;
                     for (int k = 0; k < n; ++k) store_vout(pool + k, poly[k].v);
+#ifdef SWR_USER_VERTEX
+                    if (vnorm) for (int k = 0; k < n; ++k) vnorm[pbase + (uint32_t)k] = make_float4(poly[k].nrm[0], poly[k].nrm[1], poly[k].nrm[2], poly[k].d4w);
+#else
                     if (vnorm) for (int k = 0; k < n; ++k) vnorm[pbase + (uint32_t)k] = make_float4(poly[k].nrm[0], poly[k].nrm[1], poly[k].nrm[2], 0.0f);
+#endif
                     // fan (0, k, k+1), Rasterizer.cs:154-157
                     n_setup += setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), poly[0], poly[1], poly[2],
                                               pbase, pbase + 1, pbase + 2, recs + slot, &tbs[0], wireframe != 0);

@@ -1,13 +1,18 @@
-// swr_program.hip.h -- the source contract of USER fragment programs (swr_program_create, include/swr.h).  Compiled only at run
-// time (hiprtc, SWR_RTC_PROGRAM defined): the library embeds this header and the kernel headers, the prelude below comes first,
-// then the user's text, then k_raster_c.  The product library never includes it.
+// swr_program.hip.h -- the source contract of USER programs (swr_program_create / swr_program_create_vf, include/swr.h).  Compiled
+// only at run time (hiprtc, SWR_RTC_PROGRAM defined): the library embeds this header and the kernel headers, the prelude below comes
+// first, then the user's text(s), then k_raster_c (and, for a program with a vertex half, k_vertex_user and its k_setup).  The product
+// library never includes it.
 //
-// The user defines one function:
+// The user defines the fragment half:
 //     __device__ float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
-// `in` is Shaders.VertexOutput after Rasterizer.Interpolate (Rasterizer.cs:566-640) with Interpolate = true -- the vertex stage is
-// Renderer.VertexShader (Renderer.cs:830-846), as for SWR_PROG_DUST2_LAMBERT_FOG -- computed with the arithmetic the built-in
-// programs use.  The function is inlined into the raster kernel, so varyings it never reads are never interpolated (or loaded).
-// A result with W <= 0 or NaN writes nothing (Rasterizer.cs:511): swr_discard() is such a result.
+// `in` is Shaders.VertexOutput after Rasterizer.Interpolate (Rasterizer.cs:566-640) with Interpolate = true, computed with the
+// arithmetic the built-in programs use.  The function is inlined into the raster kernel, so varyings it never reads are never
+// interpolated (or loaded).  A result with W <= 0 or NaN writes nothing (Rasterizer.cs:511): swr_discard() is such a result.
+//
+// ... and, optionally (SWR_USER_VERTEX defined), the vertex half -- any Shaders.VertexShader delegate:
+//     __device__ void swr_vertex(const swr_vs_in& in, const swr_vs_env& env, swr_vs_out& out);
+// `out` is `new Shaders.VertexOutput()`, all zeros, Interpolate = true.  Without a vertex half the vertex stage is Renderer.VertexShader
+// (Renderer.cs:830-846, k_vertex), as for SWR_PROG_DUST2_LAMBERT_FOG, and swr_fs_in::data4 reads (0, 0, 0, 0).
 #pragma once
 
 #ifdef __HIPCC_RTC__
@@ -25,7 +30,15 @@ typedef __UINTPTR_TYPE__ uintptr_t;
 #endif
 #endif
 
+// include/swr.h calls the 48-byte input vertex `swr_vertex`, the name the contract gives the user's vertex function: in the code
+// object of a program with a vertex half the record goes by another name (only DrawParams::verts refers to it)
+#ifdef SWR_USER_VERTEX
+#define swr_vertex swr_vertex_record
+#endif
 #include "swr_raster.hip.h"
+#ifdef SWR_USER_VERTEX
+#undef swr_vertex
+#endif
 
 // Shaders.VertexOutput after Interpolate
 struct swr_fs_in {
@@ -36,6 +49,8 @@ struct swr_fs_in {
     float2 screen_coords;        // ScreenCoords (pixel position / (width - 1, height - 1) at the vertices, Rasterizer.cs:390)
     float3 barycentric;          // Barycentric (the perspective-correct weights wa, wb, wc, Rasterizer.cs:583-585,638)
     float3 world_normal;         // Data["WorldNormal"]: weighted sum renormalised (Rasterizer.cs:680-688)
+    float4 data4;                // the user's own Vector4 key of VertexOutput.Data (swr_vs_out::data4): weighted sum with the normalised
+                                 // weights, nothing else (Rasterizer.cs:690-693); zeros when the program has no vertex half
 };
 
 // what a fragment program closes over: the draw's uniform block, its captured constants, the pixel
@@ -69,13 +84,63 @@ __device__ __forceinline__ float4 swr_discard() { return make_float4(0.0f, 0.0f,
 // the user's program (always inlined into the raster kernel)
 __device__ __attribute__((always_inline)) float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
 
+#ifdef SWR_USER_VERTEX
+// Shaders.VertexInput (Shaders.cs:10-24)
+struct swr_vs_in {
+    float3 position;
+    float2 uv;
+    float3 normal;
+    float4 color;
+};
+// what a vertex delegate receives and closes over.  Everything here is uniform over the draw: the kernel reads it with scalar loads.
+struct swr_vs_env {
+    const float* model;          // 16 floats each, row-major M11..M44 as include/swr.h lays them out
+    const float* view;
+    const float* projection;
+    const swr_uniforms& uniforms;
+    const float* constants;      // constants[0..63]: the SAME captured constants the fragment half reads
+    uint32_t nm_flags;           // the context's System.Numerics model of Transform / TransformNormal (swr_set_transform_fma) when the
+                                 // draw was recorded: the helpers below read it
+};
+// new Shaders.VertexOutput() (Shaders.cs:26-47): zero-initialised before swr_vertex is called, Interpolate = true
+struct swr_vs_out {
+    float4 clip_position;        // ClipPosition
+    float4 color;                // Color
+    float2 tex_coord;            // TexCoord
+    float3 normal;               // Normal
+    float3 world_normal;         // Data["WorldNormal"] (Vector3 key: the raster stage renormalises its weighted sum)
+    float4 data4;                // one Vector4 key of the user's own: lerped in the clipper, weighted sum in the raster stage
+};
+// Vector4.Transform(v, M), Vector3.TransformNormal(n, M), Vector3.Normalize(v) = v / v.Length(): the functions k_vertex calls, under
+// the draw's run-time flags, so a restated Renderer.VertexShader gives k_vertex's bits in every library build and flag setting
+__device__ __forceinline__ float4 swr_transform(float4 v, const float* m, const swr_vs_env& env) {
+    const float p[4] = { v.x, v.y, v.z, v.w };
+    float o[4];
+    swr::vec4_transform(p, m, o, (env.nm_flags & SWR_NM_TRANSFORM_FMA) != 0u);
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+__device__ __forceinline__ float3 swr_transform_normal(float3 n, const float* m, const swr_vs_env& env) {
+    const float p[3] = { n.x, n.y, n.z };
+    float o[3];
+    swr::vec3_transform_normal(p, m, o, (env.nm_flags & SWR_NM_TRANSFORM_NORMAL_FMA) != 0u);
+    return make_float3(o[0], o[1], o[2]);
+}
+__device__ __forceinline__ float3 swr_normalize(float3 v) {
+    const float len = sqrtf(swr::dot3(v.x, v.y, v.z, v.x, v.y, v.z));
+    return make_float3(v.x / len, v.y / len, v.z / len);
+}
+// the user's vertex program (always inlined into k_vertex_user, swr_geometry.hip.h)
+__device__ __attribute__((always_inline)) void swr_vertex(const swr_vs_in& in, const swr_vs_env& env, swr_vs_out& out);
+#endif
+
 namespace swr {
 
 // Rasterizer.Interpolate (Interpolate = true) of everything swr_fs_in holds, from the three outputs as the raster kernel loads them:
 // clip / colour / uv + wn.xy / wn.z rows of VOut, Normal from the side array, the screen positions from the TriRec.  The divisions
-// are the IEEE ones (shade_fragment's division cores return the same quotients), the sums in the reference's order.
+// are the IEEE ones (shade_fragment's division cores return the same quotients), the sums in the reference's order.  d4 = the user
+// vertex program's data4 at the three outputs (zeros without a vertex half).
 __device__ __forceinline__ swr_fs_in interpolate_fs_in(float w0f, float w1f, float w2f, const float4 clip[3], const float4 col[3],
-                                                       const float4 uvn[3], const float wnz[3], const float4 nrm[3], const float sx[3],
+                                                       const float4 uvn[3], const float wnz[3], const float4 nrm[3], const float4 d4[3], const float sx[3],
                                                        const float sy[3], float inv_width, float inv_height) {
     const float ra = w0f / clip[0].w, rb = w1f / clip[1].w, rc = w2f / clip[2].w;        // :576-578
     const float inv_sum = (ra + rb) + rc;                                                 // :579
@@ -104,6 +169,9 @@ __device__ __forceinline__ swr_fs_in interpolate_fs_in(float w0f, float w1f, flo
         n0 = n0 * s; n1 = n1 * s; n2 = n2 * s;
     }
     in.world_normal = make_float3(n0, n1, n2);
+    // InterpolateData, Vector4 key: (a * wa + b * wb) + c * wc, no division and no renormalisation (:690-693)
+    in.data4 = make_float4((d4[0].x * wa + d4[1].x * wb) + d4[2].x * wc, (d4[0].y * wa + d4[1].y * wb) + d4[2].y * wc,
+                           (d4[0].z * wa + d4[1].z * wb) + d4[2].z * wc, (d4[0].w * wa + d4[1].w * wb) + d4[2].w * wc);
     return in;
 }
 

@@ -565,19 +565,25 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
             };
             const float4 q4 = L.stage[4][t], q6 = L.stage[6][t];
             const uint32_t off[3] = { __float_as_uint(q4.x), __float_as_uint(q4.y), __float_as_uint(q4.z) };
-            float4 clip[3], col[3], uvn[3], nrm[3];
+            float4 clip[3], col[3], uvn[3], nrm[3], d4[3];
             float wnz[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 clip[k] = ld4(vout_rsrc, off[k]); col[k] = ld4(vout_rsrc, off[k] + 16u); uvn[k] = ld4(vout_rsrc, off[k] + 32u);
-                wnz[k] = ld4(vout_rsrc, off[k] + 48u).x;
+                const float4 r3 = ld4(vout_rsrc, off[k] + 48u);
+                wnz[k] = r3.x;
                 nrm[k] = ld4(nrm_rsrc, off[k] >> 2);
+#ifdef SWR_USER_VERTEX      // swr_vs_out::data4 rides in VOut::wpos and in .w of the Normal side array (k_vertex_user, swr_geometry.hip.h)
+                d4[k] = make_float4(r3.y, r3.z, r3.w, nrm[k].w);
+#else                       // (k_vertex keeps Data["WorldPos"] there: not a varying of user programs)
+                d4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
             }
             const uint32_t ro = __float_as_uint(q6.x);
             const float4 r0 = ld4(rec_rsrc, ro), r1 = ld4(rec_rsrc, ro + 16u);
             const float sx[3] = { r0.x, r0.y, r0.z }, sy[3] = { r0.w, r1.x, r1.y };
             const float inv_w = 1.0f / (float)(a.fp.width - 1), inv_h = 1.0f / (float)(a.fp.height - 1);      // Rasterizer.cs:362-363
-            const swr_fs_in in = interpolate_fs_in(w0f, w1f, w2f, clip, col, uvn, wnz, nrm, sx, sy, inv_w, inv_h);
+            const swr_fs_in in = interpolate_fs_in(w0f, w1f, w2f, clip, col, uvn, wnz, nrm, d4, sx, sy, inv_w, inv_h);
             const swr_fs_env env = { a.draws[draw].u, a.user_consts + 64u * draw, px, py, dc.tex, dc.tex_w, dc.tex_h };
             return swr_fragment(in, env);
         }

@@ -212,11 +212,13 @@ class Device:
         self._ck(self._lib.swr_get_pipelining(self._ctx, C.byref(m)))
         return int(m.value)
 
-    def compile_program(self, source: str) -> int:
-        """swr_program_create: compile a user fragment program (C++ defining `swr_fragment`, contract in include/swr.h) for this
-        device; returns its id (>= SWR_PROG_USER_BASE).  A compile error raises SwrError(SWR_ERR_INVALID_ARG) with the log."""
+    def compile_program(self, source: str, vertex_source: Optional[str] = None) -> int:
+        """swr_program_create_vf: compile a user program for this device -- C++ defining `swr_fragment` and, with `vertex_source`,
+        `swr_vertex` (contract in include/swr.h); without it the vertex stage is Renderer.VertexShader.  Returns its id
+        (>= SWR_PROG_USER_BASE).  A compile error raises SwrError(SWR_ERR_INVALID_ARG) with the log."""
         pid = C.c_int(0)
-        self._ck(self._lib.swr_program_create(self._ctx, source.encode(), C.byref(pid)))
+        vs = vertex_source.encode() if vertex_source is not None else None
+        self._ck(self._lib.swr_program_create_vf(self._ctx, vs, source.encode(), C.byref(pid)))
         return pid.value
 
     def destroy_program(self, program_id: int):
@@ -294,19 +296,22 @@ class ShaderProgram:
 
 
 class CustomProgram(ShaderProgram):
-    """A user fragment program given as source (Shaders.Custom): compiled once per Device on first use; `constants` (up to 64
-    floats, the fields the C# closure captures) are set before every draw, so each draw renders with the values it was given."""
+    """A user program given as source (Shaders.Custom): the fragment half and, optionally, the vertex half; compiled once per Device
+    on first use; `constants` (up to 64 floats, the fields the C# closures capture, read by both halves) are set before every draw,
+    so each draw renders with the values it was given."""
 
-    def __init__(self, source: str, uniforms: Optional[N.Uniforms] = None, texture: Optional[Texture] = None, constants=None):
+    def __init__(self, source: str, uniforms: Optional[N.Uniforms] = None, texture: Optional[Texture] = None, constants=None,
+                 vertex_source: Optional[str] = None):
         super().__init__(Program.FlatColor, uniforms, texture)
         self.source = source
+        self.vertex_source = vertex_source
         self.constants = constants
         self._ids = {}          # id(Device) -> (Device, program id)
 
     def _program_for(self, dev: "Device") -> int:
         hit = self._ids.get(id(dev))
         if hit is None or hit[0] is not dev:
-            hit = (dev, dev.compile_program(self.source))
+            hit = (dev, dev.compile_program(self.source, self.vertex_source))
             self._ids[id(dev)] = hit
         pid = hit[1]
         dev.set_program_constants(pid, self.constants)
@@ -338,9 +343,10 @@ class Shaders:
         return ShaderProgram(Program.Phong4Point, uniforms, texture)
 
     @staticmethod
-    def Custom(source: str, uniforms=None, texture=None, constants=None):
-        """Any Shaders.FragmentShader restated in C++ against the contract of include/swr.h (swr_program_create)."""
-        return CustomProgram(source, uniforms, texture, constants)
+    def Custom(source: str, uniforms=None, texture=None, constants=None, vertex_source=None):
+        """Any Shaders.FragmentShader -- with `vertex_source`, any (Shaders.VertexShader, Shaders.FragmentShader) pair -- restated in
+        C++ against the contract of include/swr.h (swr_program_create_vf)."""
+        return CustomProgram(source, uniforms, texture, constants, vertex_source)
 
 
 class MainWindow:
