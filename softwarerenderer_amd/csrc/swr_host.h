@@ -1,0 +1,350 @@
+// swr_host.h -- host side of libswr_hip.so: the context and batch types, device buffers, the frame-slot ring, band geometry,
+// timing spans and the front stream.  Included by swr_api.hip only (the library's one translation unit).
+#pragma once
+
+struct swr_mesh {
+    float4* d_bounds = nullptr;               // Mesh.SphereBounds (ModelLoader.cs:291), computed on first use
+    bool bounds_ready = false;
+    swr_vertex* d_verts = nullptr;
+    uint16_t* d_idx = nullptr;
+    int n_verts = 0, n_idx = 0;
+    size_t cap_verts = 0, cap_idx = 0;        // bytes allocated behind d_verts / d_idx (a recycled transient mesh may hold more than it uses)
+    bool transient = false;
+    float box_lo[3] = { 0, 0, 0 }, box_hi[3] = { 0, 0, 0 };   // exact model-space AABB of the vertices (host, at creation)
+    bool has_box = false;
+};
+struct swr_texture {
+    uint8_t* d_rgba = nullptr;
+    uint8_t* d_blocked = nullptr;             // block-linear copy (4 x 4-texel blocks of 64 B) for the bilinear filter, made when it is first switched on
+    int w = 0, h = 0;
+    bool bilinear = false;                    // build-defined extension; the reference's Texture.Sample is nearest
+};
+
+namespace {
+
+thread_local std::string g_create_error;
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+enum Stage { ST_VERTEX = 0, ST_SETUP, ST_BIN, ST_SORT, ST_COVER, ST_RASTER, ST_CLEAR, ST_COUNT };
+
+struct EventSpan { int stage; hipEvent_t a, b; };
+
+#ifndef SWR_TIMING_EVENT_FLAGS
+#define SWR_TIMING_EVENT_FLAGS hipEventDisableSystemFence
+#endif
+#ifndef SWR_HANDOVER_EVENT_FLAGS
+#define SWR_HANDOVER_EVENT_FLAGS hipEventDisableTiming
+#endif
+#define SWR_SLOTS 3
+struct FrameSlot { void* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
+
+// Everything of a batch that its raster kernel reads (or that a front-end kernel and the raster kernel share).  With frames
+// pipelined two sets alternate per flush, so the front end of flush N+1 never writes what the raster kernel of flush N reads;
+// with pipelining off only set 0 is used.  Buffers only the front end touches (slot_tb, want, tile_list, pair_tile, the scan's
+// totals) are single: front ends run in order on one stream.
+struct RasterSet {
+    DevBuf d_upload;         // draws | vertex block map | triangle block map [| bounds pointers | visibility words] of the batch
+    DevBuf d_vout, d_vnorm, d_recs;
+    DevBuf d_masks, d_pcounts, d_pair_refs;
+    DevBuf d_tile_count, d_tile_start;
+    DevBuf d_order;          // [tile_order n_tiles] uint4 {tile, list start, pairs, -}, [tile_work n_tiles][hist 256][cursor 256] u32, [tile_bucket n_tiles] u8: heaviest-first raster order
+    uint32_t hist_tiles = 0; // tile count the fragment history in d_order (tile_work) belongs to (0: none yet)
+    hipEvent_t front_done = nullptr, raster_done = nullptr;
+    bool raster_pending = false;      // raster_done has been recorded and the stream has not been drained since
+};
+
+// A user program loaded on the context's device (swr_program_create / _vf): the two k_raster_c<SWR_PROG_CUSTOM> instantiations
+// (with / without BlendMode.None's row early-out) of its run-time compiled code object and, when it has a vertex half, the module's
+// k_vertex_user and the k_setup whose clipper lerps data4.w (swr_geometry.hip.h).  Shared by the context's table and every
+// recorded or in-flight draw that uses it: the module is unloaded when the last of them lets go, and a batch only lets go once its
+// kernels are known to be over (retire_batch / free_garbage).
+struct UserProg {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn[2] = { nullptr, nullptr };     // [EARLYOUT]
+    hipFunction_t vertex_fn = nullptr, setup_fn = nullptr;   // programs with a vertex half only: launched instead of k_vertex / k_setup
+    float constants[64] = {};                        // swr_program_set_constants: copied into each draw when it is recorded
+    ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
+};
+
+struct DrawCmd {
+    DrawParams p;
+    swr_mesh* mesh;
+    bool frustum_cull = false;                 // render only if IsSphereInFrustum(mesh bounds, model, view, proj)
+    std::shared_ptr<UserProg> prog;            // user programs only: the program ...
+    std::shared_ptr<const std::vector<float>> uconsts;   // ... and its 64 constants as they were when the draw was recorded
+};
+
+// one flush = one batch; kept until the host has seen that it fitted (optimistic execution, see swr::Ctrl)
+struct Batch {
+    std::vector<DrawCmd> draws;
+    bool clear_color = false, clear_depth = false;
+    float clear_rgba[4] = { 0, 0, 0, 0 };
+    float near_clip = 0.1f;
+    bool wireframe = false;                    // Rasterizer.RenderDebugMode == Wireframe for the whole batch
+    uint32_t seq = 0;
+    float4* color = nullptr;                   // the framebuffer bound when the batch was flushed: a replay (validate_locked) must
+    float* depth = nullptr;                    // hit the same buffers even if the caller has bound others since (double buffering)
+};
+
+}  // namespace
+
+struct swr_context {
+    int device = 0;
+    std::mutex mu;
+    std::string err;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipStream_t front_stream = nullptr;    // front ends of pipelined flushes (and mesh uploads, which only front-end kernels read)
+    int pipelining = 1;                    // swr_set_pipelining: 0 off, 1 every batch (default), 2 small frames / small batches only (see execute_batch)
+    uint32_t pipeline_max_tris = 1u << 17; // mode 2: a batch is pipelined when it has at most this many triangles ...
+    uint32_t pipeline_max_tiles = 1u << 15;   // ... or the band at most this many tiles (8 raster waves per wave slot of the chip)
+    hipEvent_t f_tail_ev = nullptr, r_front_ev = nullptr;
+    bool f_tail_pending = false;           // the front stream carries work (a front end, a mesh upload) the raster stream has not been ordered behind
+    bool r_front_pending = false;          // an unpipelined batch ran its front end on the raster stream since the front stream last waited for it
+    RasterSet sets[2];
+    uint32_t raster_span_no = 0;           // profiling mode 3: raster launches seen since swr_profile_enable
+    char dev_name[256] = { 0 };
+
+    int W = 0, H = 0, tiles_x = 0, tiles_y = 0;
+    bool geometry_applied = false;            // swr_resize has run at least once (a second call with the same size is a no-op)
+    bool band_set = false;
+    int band_first = 0, band_count = 0;       // as requested by swr_set_band
+    int band_ty0 = 0, band_ty1 = 0;           // effective
+    int il_k = 0, il_world = 1, il_rank = 0;  // swr_set_band_interleaved: stripes of il_k tile rows, stripe s belongs to rank s % il_world
+    int band_tile_rows = 0;                   // tile rows this context stores (contiguous band or stripes)
+    float4* color = nullptr;                  // band storage in use (own or external)
+    float* depth = nullptr;
+    DevBuf own_color, own_depth;
+    void* ext_color = nullptr; void* ext_depth = nullptr;
+
+    uint32_t nm_flags = SWR_NUMERICS_FMA ? (SWR_NM_TRANSFORM_FMA | SWR_NM_TRANSFORM_NORMAL_FMA) : 0u;   // swr_set_transform_fma
+    float near_clip = 0.1f, far_clip = 1000.0f;   // Rasterizer.cs:20-21
+    int debug_mode = SWR_DEBUG_NONE;               // Rasterizer.cs:22
+
+    bool pend_clear_color = false, pend_clear_depth = false;
+    float clear_rgba[4] = { 0, 0, 0, 0 };
+
+    std::vector<DrawCmd> draws;
+    uint64_t pend_verts = 0, pend_tris = 0;
+    std::vector<swr_mesh*> garbage;           // transient meshes no recorded draw needs any more, possibly still read by kernels in flight
+    std::map<int, std::shared_ptr<UserProg>> progs;     // live user programs by id (swr_program_create / _destroy)
+    int next_prog = SWR_PROG_USER_BASE;
+    std::vector<std::shared_ptr<UserProg>> prog_garbage; // programs of retired batches whose kernels may still run (see garbage)
+    std::vector<swr_mesh*> mesh_pool;         // transient meshes whose batches are KNOWN to be complete: their device buffers are handed to the
+    size_t mesh_pool_bytes = 0;               // next swr_render_mesh_arrays call instead of hipFree / hipMalloc (both synchronise the device)
+    uint64_t stale_dropped[2] = { 0, 0 };     // present tickets dropped by back-pressure whose pixels predate a replay (swr_present_wait reports them)
+    std::vector<Batch> inflight;              // launched optimistically, not yet validated
+    uint32_t next_seq = 1;
+    bool sync_flush = false;                  // SWR_SYNC_FLUSH=1: read the pair total back in every flush
+    uint32_t debug_fill_capacity = 0;         // SWR_DEBUG_FILL_CAPACITY=n: k_bin<FILL> of optimistic flushes sees a list of n entries (tests)
+
+    DevBuf d_slot_tb;        // (the vertex-stage output, the records and the upload block live in the RasterSets)
+    FrameSlot slots[SWR_SLOTS];
+    uint32_t slot_next = 0;
+    DevBuf d_pair_tile, d_ctrl;
+    uint32_t* host_poison = nullptr;           // pinned, device-visible copy of Ctrl::poison
+    DevBuf d_tile_list, d_tile_stats, d_counters, d_total, d_scratch;
+    DevBuf d_want;           // 1 byte per slot: COUNT's pair_may_cover decisions, replayed by FILL
+    size_t tile_stats_tiles = 0;
+    swr_stats totals = {};
+    unsigned long long host_tile_pairs = 0;   // rounds sized on the host (MODE_SYNC)
+    unsigned long long replays = 0;           // times an optimistic batch did not fit and was replayed
+    unsigned long long host_syncs = 0;        // times an entry point made the host wait for the stream (swr_sync_count)
+    // asynchronous present (swr_present_rgb_async): two device staging buffers alternate; the flatten runs on `stream`, the copy to
+    // the host on `copy_stream`, so the next frame renders while this one crosses PCIe
+    hipStream_t copy_stream = nullptr;
+    DevBuf present_buf[2];
+    hipEvent_t present_flat[2] = { nullptr, nullptr }, present_done[2] = { nullptr, nullptr };
+    uint64_t present_ticket[2] = { 0, 0 };    // ticket whose copy the slot carries (0 = none pending)
+    uint32_t present_seq[2] = { 0, 0 };       // last batch flushed before that present: retired when the copy is known to be over
+    uint64_t next_ticket = 0;
+
+    int profiling = 0;                         // 0 off, 1 every stage, 2 only the raster kernel (2 events per flush)
+    std::vector<EventSpan> spans;
+    std::vector<float> raster_samples;         // duration of every raster launch that carried an event pair since swr_profile_reset (<= 65,536)
+    std::vector<hipEvent_t> event_pool;
+    swr_profile prof = {};
+};
+
+namespace {
+
+#define SWR_HIP(ctx, call)                                                                        \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            char b_[512];                                                                         \
+            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            (ctx)->err = b_;                                                                      \
+            return e_ == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;                         \
+        }                                                                                         \
+    } while (0)
+
+int fail(swr_context* c, int code, const char* msg) { c->err = msg; return code; }
+
+int ensure(swr_context* c, DevBuf& b, size_t bytes, bool zero_new = false) {
+    if (bytes <= b.cap) return SWR_OK;
+    size_t want = std::max(bytes, b.cap + b.cap / 2);
+    if (b.p) { SWR_HIP(c, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    SWR_HIP(c, hipMalloc(&b.p, want));
+    b.cap = want;
+    if (zero_new) SWR_HIP(c, hipMemsetAsync(b.p, 0, want, c->stream));
+    return SWR_OK;
+}
+
+void release(DevBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+
+// Frame-slot ring: a batch takes the next slot = {pinned staging block for its upload, completion event}.
+// Taking a slot first waits for the batch that used it SWR_SLOTS flushes ago, which (a) makes the pinned block
+// safe to overwrite and (b) bounds how far the host runs ahead of the GPU (pageable uploads and unbounded
+// queue depth both serialise the stream on some HIP runtimes).
+void* slot_acquire(swr_context* c, size_t bytes) {
+    FrameSlot& fs = c->slots[c->slot_next % SWR_SLOTS];
+    if (fs.busy) { (void)hipEventSynchronize(fs.done); fs.busy = false; }
+    if (fs.cap < bytes) {
+        if (fs.host) (void)hipHostFree(fs.host);
+        fs.host = nullptr; fs.cap = 0;
+        size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
+        if (hipHostMalloc(&fs.host, cap, hipHostMallocDefault) != hipSuccess) { fs.host = nullptr; return nullptr; }
+        fs.cap = cap;
+    }
+    return fs.host;
+}
+void slot_submit(swr_context* c) {            // call after the batch's last launch
+    FrameSlot& fs = c->slots[c->slot_next % SWR_SLOTS];
+    if (!fs.done) (void)hipEventCreateWithFlags(&fs.done, hipEventDisableTiming);
+    if (fs.done && hipEventRecord(fs.done, c->stream) == hipSuccess) fs.busy = true;
+    c->slot_next++;
+}
+
+BandMap host_band_map(const swr_context* c) {
+    BandMap b; b.ty0 = c->band_ty0; b.ty1 = c->band_ty1; b.il_k = c->il_k; b.il_world = c->il_world; b.il_rank = c->il_rank;
+    return b;
+}
+int band_y0(const swr_context* c) { return c->band_ty0 * SWR_TILE; }     // contiguous band only
+// pixel rows stored: the band's tile rows, 16 pixel rows each, the frame's last tile row possibly partial
+int band_rows(const swr_context* c) {
+    if (c->band_tile_rows <= 0) return 0;
+    const int last_global = band_global_row(host_band_map(c), c->band_tile_rows - 1);
+    const int last_rows = std::min(SWR_TILE, c->H - last_global * SWR_TILE);
+    return (c->band_tile_rows - 1) * SWR_TILE + std::max(0, last_rows);
+}
+// row of pixel row y in the band's buffers, -1 if the band does not hold it
+int band_local_pixel_row(const swr_context* c, int y) {
+    if (y < 0 || y >= c->H) return -1;
+    const int lr = band_local_row(host_band_map(c), y / SWR_TILE);
+    return lr < 0 ? -1 : lr * SWR_TILE + y % SWR_TILE;
+}
+size_t band_pixels(const swr_context* c) { return (size_t)std::max(0, c->W) * (size_t)band_rows(c); }
+
+int apply_geometry(swr_context* c) {
+    c->tiles_x = c->W > 0 ? (c->W + SWR_TILE - 1) / SWR_TILE : 0;     // Rasterizer.cs:76-77
+    c->tiles_y = c->H > 0 ? (c->H + SWR_TILE - 1) / SWR_TILE : 0;
+    if (c->il_k > 0) {
+        c->band_ty0 = 0; c->band_ty1 = c->tiles_y;                     // ownership is decided row by row (BandMap)
+        int rows = 0;
+        for (int ty = 0; ty < c->tiles_y; ++ty) rows += band_local_row(host_band_map(c), ty) >= 0 ? 1 : 0;
+        c->band_tile_rows = rows;
+    } else {
+        if (c->band_set) {
+            c->band_ty0 = std::min(std::max(c->band_first, 0), c->tiles_y);
+            c->band_ty1 = std::min(c->band_ty0 + std::max(c->band_count, 0), c->tiles_y);
+        } else {
+            c->band_ty0 = 0; c->band_ty1 = c->tiles_y;
+        }
+        c->band_tile_rows = c->band_ty1 - c->band_ty0;
+    }
+    size_t n = band_pixels(c);
+    if (c->ext_color) {
+        c->color = (float4*)c->ext_color; c->depth = (float*)c->ext_depth;
+    } else {
+        int rc;
+        if ((rc = ensure(c, c->own_color, std::max<size_t>(n, 1) * sizeof(float4), false))) return rc;
+        if ((rc = ensure(c, c->own_depth, std::max<size_t>(n, 1) * sizeof(float), false))) return rc;
+        c->color = c->own_color.as<float4>(); c->depth = c->own_depth.as<float>();
+    }
+    return SWR_OK;
+}
+
+FrameParams frame_params(const swr_context* c, float near_clip) {      // (a batch keeps the NearClip it was recorded under)
+    FrameParams fp;
+    fp.width = c->W; fp.height = c->H; fp.tiles_x = c->tiles_x; fp.tiles_y = c->tiles_y;
+    fp.band_ty0 = c->band_ty0; fp.band_ty1 = c->band_ty1;
+    fp.band_y0 = band_y0(c); fp.band_rows = band_rows(c);
+    fp.il_k = c->il_k; fp.il_world = c->il_world; fp.il_rank = c->il_rank; fp.band_tile_rows = c->band_tile_rows;
+    fp.near_clip = near_clip;
+    return fp;
+}
+
+hipEvent_t get_event(swr_context* c) {
+    if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
+    hipEvent_t e = nullptr;
+    // timing only, never ordering: no system-scope fence (the default event's cache write-back / invalidation would hit the OTHER
+    // stream's kernels when frames are in flight -- measured: 20 timed frames 0.651 ms with default events, see SWR_EVENT_FLAGS)
+    if (hipEventCreateWithFlags(&e, SWR_TIMING_EVENT_FLAGS) != hipSuccess) (void)hipEventCreate(&e);
+    return e;
+}
+struct ScopedSpan {
+    swr_context* c; int stage; hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t s;
+    bool on = false;
+    ScopedSpan(swr_context* c_, int st, hipStream_t s_ = nullptr) : c(c_), stage(st), s(s_ ? s_ : c_->stream) {
+        // 1: every stage; 2: the raster kernel of every flush; 3: the raster kernel of every 4th flush (an event pair costs
+        // about 10 us of stream time: sampling keeps a timed region within 0.5 % of its unobserved rate)
+        on = c->profiling == 1 || (st == ST_RASTER && (c->profiling == 2 || (c->profiling == 3 && (c->raster_span_no++ & 3u) == 0u)));
+        if (on) { a = get_event(c); b = get_event(c); (void)hipEventRecord(a, s); }
+    }
+    ~ScopedSpan() {
+        if (on) { (void)hipEventRecord(b, s); c->spans.push_back({ stage, a, b }); }
+    }
+};
+
+void collect_spans(swr_context* c) {      // stream must be idle
+    for (auto& s : c->spans) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) {
+            switch (s.stage) {
+            case ST_VERTEX: c->prof.vertex_ms += ms; break;
+            case ST_SETUP:  c->prof.setup_ms += ms; break;
+            case ST_BIN:    c->prof.bin_ms += ms; break;
+            case ST_SORT:   c->prof.sort_ms += ms; break;
+            case ST_COVER:  c->prof.cover_ms += ms; break;
+            case ST_RASTER: c->prof.raster_ms += ms; c->prof.raster_launches++;
+                            if (c->raster_samples.size() < 65536) c->raster_samples.push_back(ms);
+                            break;
+            case ST_CLEAR:  c->prof.clear_ms += ms; break;
+            }
+            c->prof.total_ms += ms;
+        }
+        c->event_pool.push_back(s.a); c->event_pool.push_back(s.b);
+    }
+    c->spans.clear();
+}
+
+// the stream mesh uploads and front-end-only work go to: the front stream while frames are pipelined, else the context's stream
+// (and notes that the front stream now carries work the raster stream has not been ordered behind)
+hipStream_t use_front_stream(swr_context* c) {
+    if (c->pipelining && c->front_stream) { c->f_tail_pending = true; return c->front_stream; }
+    return c->stream;
+}
+
+// creates the front stream (once) and the hand-over events
+int ensure_front_stream(swr_context* c) {
+    if (!c->pipelining || c->front_stream) return SWR_OK;
+    int least = 0, greatest = 0;
+    SWR_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    // high priority: the front end's short kernels go first wherever a slot frees up, the raster kernel (65,536 one-wave workgroups)
+    // fills the rest (default priority measured the same within noise, profiles/r04_frames_in_flight.md)
+    SWR_HIP(c, hipStreamCreateWithPriority(&c->front_stream, hipStreamNonBlocking, greatest));
+    SWR_HIP(c, hipEventCreateWithFlags(&c->f_tail_ev, hipEventDisableTiming));
+    SWR_HIP(c, hipEventCreateWithFlags(&c->r_front_ev, hipEventDisableTiming));
+    for (auto& s : c->sets) {
+        if (!s.front_done) SWR_HIP(c, hipEventCreateWithFlags(&s.front_done, SWR_HANDOVER_EVENT_FLAGS));
+        if (!s.raster_done) SWR_HIP(c, hipEventCreateWithFlags(&s.raster_done, SWR_HANDOVER_EVENT_FLAGS));
+    }
+    return SWR_OK;
+}
+}  // namespace

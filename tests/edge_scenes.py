@@ -3,7 +3,7 @@
 Three places in the kernels skip work on the strength of a hand-written error bound instead of repeating the reference's
 arithmetic: the tile rejection of binning (pair_may_cover, swr_binning.hip.h), the hierarchical-Z pair drop (k_cover's bound,
 k_raster_c's drop, swr_raster_c.hip.h) and k_cover's fast coverage walk.  Others depend on where inputs fall: the run select of
-pairs flagged SWR_INFO_SIMPLE, the division / reciprocal / sqrt cores (swr_device.h) and depth_only_grows (swr_api.hip).  Random
+pairs flagged SWR_INFO_SIMPLE, the division / reciprocal / sqrt cores (swr_device.h) and depth_only_grows (swr_raster_select.h).  Random
 scenes almost never land within rounding distance of those bounds; the families below are built to:
 
   F1  lattice edges: edges through integer pixel samples at tile corners, vertices 1e2..4e6 px away (the chain rounds)

@@ -3,8 +3,8 @@
 shade_dust2_fast and shade_phong4_fast (csrc/swr_raster.hip.h) run Interpolate and the fragment program as one straight-line block
 with every division / reciprocal / sqrt core unconditional, AND the conditions under which each core IS the IEEE operation into
 `safe`, and k_raster_c shades the whole chunk again with the guarded shade_fragment when any shaded lane was unsafe.  They run only
-in the specialised kernels that execute_batch (swr_api.hip) selects when EVERY draw of the batch has one program, BlendMode.Alpha
-and DepthTest.LessEqual.  The families below put fragments on both sides of every `safe` term:
+in the specialised kernels that the flush path (select_raster_kernel, csrc/swr_raster_select.h) picks when EVERY draw of the batch has
+one program, BlendMode.Alpha and DepthTest.LessEqual.  The families below put fragments on both sides of every `safe` term:
 
   S1  weights and clip.w: samples on edges and vertices (weight 0), weights below 2^-40, one clip.w of three across 2^-+40,
       negative clip.w kept by the clipper so that (ra + rb) + rc cancels (to 0, below 2^-40, and with |N|^2 above 1e12)
@@ -18,7 +18,8 @@ and DepthTest.LessEqual.  The families below put fragments on both sides of ever
 
 Every family returns scenes in (pure, diluted) pairs: `pure` has one program with Alpha / LessEqual on every draw, so the
 specialised kernel is selected; `diluted` is the same draws plus one draw of another program whose triangle is entirely off
-screen, which keeps depth_only_grows and every visible word but falls to the generic kernel (predicted_kernel restates the chain).
+screen, which keeps depth_only_grows and every visible word but falls to the generic kernel (predicted_kernel restates the chain;
+test_raster_select_host.py holds the restatement against the library's own function).
 
 Geometry: most triangles are `cells`: right triangles with legs of 8 px at integer or quarter-pixel positions inside one
 16 x 16 tile, one per tile.  Their edge values and weights are exact dyadic rationals (area 64), so "exactly on an edge", "exactly
@@ -141,7 +142,7 @@ def _pair(name, W, H, draws, textures, bilinear=False):
 
 
 def predicted_kernel(scene):
-    """execute_batch's selection chain (swr_api.hip) for a frame of built-in programs submitted as one batch, no wireframe."""
+    """select_raster_kernel (csrc/swr_raster_select.h) restated for a frame of built-in programs submitted as one batch, no wireframe."""
     ds = scene.draws
     def default(p):
         return all(d.program == p and d.blend == BlendMode.Alpha and d.depth_test == DepthTest.LessEqual for d in ds)
@@ -459,7 +460,7 @@ def _flip(x, bit):
 
 
 def material_key(d):
-    """What execute_batch compares before two draws share fragment constants: program, blend, depth test, texture, uniform bytes."""
+    """What batch_geometry (csrc/swr_flush.h) compares before two draws share fragment constants: program, blend, depth test, texture, uniform bytes."""
     return (int(d.program), int(d.blend), int(d.depth_test), d.texture, bytes(d.uniforms))
 
 

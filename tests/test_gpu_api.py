@@ -150,7 +150,7 @@ def test_tile_row_bands_union_is_the_single_gpu_frame(device, world):
     c, d = np.concatenate(cols, axis=0), np.concatenate(deps, axis=0)
     assert_frame_parity(c, d, rc, rd, 1, f"bands{world}")
     assert frag == render_oracle(scene)[2]["fragments_written"]
-    # meshes whose bounding box projects outside a band are not even recorded there (band_rejects, swr_api.hip)
+    # meshes whose bounding box projects outside a band are not even recorded there (band_rejects, swr_flush.h)
     if world >= 3:
         assert min(tris) < scene.n_triangles and max(tris) <= scene.n_triangles
 
