@@ -4,6 +4,8 @@
 // (Rasterizer.cs:449-476) and the per-pixel result depends on the ORDER triangles reach a
 // pixel (depth ties under `>=`, blending).  The oracle of record is the serial order, so each
 // tile's list must hold its triangles in ascending slot order:
+//   k_setup       : per slot, the tile bbox word slot_tb[] and -- for a slot of <= 8 tiles -- the byte want[]: which of them are binned
+//                   (swr_geometry.hip.h; the decision and the order of its bits: small_want_mask / SmallTileWalk in swr_device.h)
 //   k_bin<COUNT>  : tile_count[tile] += 1 per pair               (integer atomics, order-free)
 //   k_scan        : exclusive scan -> tile_start, total pairs (k_scan_sums + k_scan_apply)
 //   k_bin<FILL>   : list[tile_start + atomic cursor] = slot       (arbitrary order inside a tile)
@@ -22,12 +24,13 @@ namespace swr {
 struct BinArgs {
     const unsigned long long* __restrict__ slot_tb;
     const TriRec* __restrict__ recs;
+    uint32_t odd_base;                   // where the record of a slot is: rec_index(slot, odd_base), swr_device.h
     uint32_t slot_lo, slot_hi;           // slots [lo, hi) are binned in this round
     uint32_t spt;                        // slots per thread = slots per triangle (2 filled, 6 wireframe): the odd
                                          // fan slots are almost always empty, so a thread walks its triangle's slots
     int tiles_x;
-    int band_ty0, band_ty1;              // tile rows binned: the contiguous band, or [0, tiles_y) with `band` deciding row by row
-    BandMap band;                        // tile-row ownership (contiguous band or interleaved stripes)
+    BandMap band;                        // tile-row ownership: rows [ty0, ty1) are binned -- the contiguous band, or [0, tiles_y) with
+                                         // the stripes deciding row by row (slot_tiles / band_local_row, swr_device.h)
     int width, height;
     uint32_t* __restrict__ tile_count;   // COUNT: incremented; FILL: used as cursor (zeroed again before)
     const uint32_t* __restrict__ tile_start;
@@ -38,7 +41,8 @@ struct BinArgs {
     uint32_t seq;                        // sequence number of the batch (what a list overflow reports in Ctrl::first_bad)
     uint32_t replayable;                 // 1: optimistic flush -- a list overflow poisons the batch (see bin_overflow)
     const unsigned long long* __restrict__ total;
-    uint8_t* __restrict__ want;          // per slot: which of its (<= 8) tiles passed pair_may_cover -- written by COUNT, read by FILL
+    const uint8_t* __restrict__ want;    // per slot: which of its (<= 8) tiles are binned -- written by k_setup (small_want_mask,
+                                         // swr_device.h), replayed by COUNT and by FILL
     uint32_t tpw;                        // triangles per wave: 64, or fewer for small batches (a wave works through its big
                                          // triangles one after the other: with few triangles more, emptier waves finish sooner)
     // FILL only: blocks [bin_blocks, gridDim.x) place the tiles in the raster kernel's dispatch order (tile_place_block)
@@ -50,53 +54,8 @@ struct BinArgs {
     uint4* __restrict__ tile_order;             // per dispatch position: {tile, first list entry, pairs, -} (tile_place_block)
 };
 
-// Can triangle (sx, sy, pixel bbox) cover ANY pixel of tile (tx, ty)?  Conservative: returns false only when
-// provably no pixel of bbox /\ tile can pass the reference's coverage test (all three incrementally stepped
-// float32 edge values >= 0, or all three <= 0; Rasterizer.cs:481-494).  The reference visits such tiles and
-// finds nothing, so dropping the pair changes no pixel and no counter.
-//
-// Proof sketch.  Let R be the pixel rectangle bbox /\ tile and, for edge k with float coefficients (a, b) and
-// reference vertex (rx, ry), E(x,y) = a*(x-rx) + b*(y-ry) in real arithmetic; u = 2^-24.  Every value the
-// reference's float chain takes is fl-arithmetic on points of R: the start value costs <= 5 roundings of
-// quantities bounded by M = |a|*max|x-rx| + |b|*max|y-ry| over R, and each of the <= 30 chain adds rounds a value
-// of magnitude <= M(1+tiny); so |W - E| <= 35uM(1+tiny) at every pixel of R.  E is linear, so its extrema over R
-// are at corners; evaluating them in float32 as below costs <= 3 roundings per term, |Efl - E| <= 6uM, and the
-// float M' satisfies M' >= M(1-4u).  With delta = 64uM':
-//   Efl_max < -delta  =>  W <= E_max + 35uM <= Efl_max + 41uM < -64uM(1-4u) + 41uM < 0 on all of R  (kills "all >= 0")
-//   Efl_min >  delta  =>  W > 0 on all of R                                                          (kills "all <= 0")
-// The analysis needs every product and sum finite: screen coordinates below 1e15 in magnitude (tested once per triangle, not
-// per tile and edge as in round 2) bound every term by 1e31; anything else (NaN / Inf included) means "keep".
-__device__ __forceinline__ bool pair_may_cover(const float sx[3], const float sy[3], int minX, int maxX, int minY, int maxY,
-                                               int tx, int ty, int width, int height, bool is_line) {
-    if (is_line) return true;         // DrawLine edges: keep every tile of the line's bbox (the test below is for triangles)
-    const int x0 = tx * SWR_TILE, y0 = ty * SWR_TILE;
-    const int startX = max(minX, x0), endX = min(maxX, min(x0 + SWR_TILE - 1, width - 1));
-    const int startY = max(minY, y0), endY = min(maxY, min(y0 + SWR_TILE - 1, height - 1));
-    if (startX > endX || startY > endY) return false;                 // Rasterizer.cs:476: nothing visited
-    // edge k: coefficients exactly as RasterizeTriangle forms them (Rasterizer.cs:445-447), reference vertex :481-483
-    const float ea[3] = { sy[1] - sy[2], sy[2] - sy[0], sy[0] - sy[1] };   // a12, a20, a01
-    const float eb[3] = { sx[2] - sx[1], sx[0] - sx[2], sx[1] - sx[0] };   // b12, b20, b01
-    const float rx[3] = { sx[1], sx[2], sx[0] };
-    const float ry[3] = { sy[1], sy[2], sy[0] };
-    const float fxs = (float)startX, fxe = (float)endX, fys = (float)startY, fye = (float)endY;
-    const float lim = 1.0e15f;
-    const bool tame = fabsf(sx[0]) < lim && fabsf(sx[1]) < lim && fabsf(sx[2]) < lim && fabsf(sy[0]) < lim && fabsf(sy[1]) < lim && fabsf(sy[2]) < lim;
-    if (!tame) return true;
-    bool any_neg = false, any_pos = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float a = ea[k], b = eb[k];
-        const float dxs = fxs - rx[k], dxe = fxe - rx[k], dys = fys - ry[k], dye = fye - ry[k];
-        const float ax_s = a * dxs, ax_e = a * dxe, by_s = b * dys, by_e = b * dye;
-        const float emax = fmaxf(ax_s, ax_e) + fmaxf(by_s, by_e);
-        const float emin = fminf(ax_s, ax_e) + fminf(by_s, by_e);
-        const float m = fabsf(a) * fmaxf(fabsf(dxs), fabsf(dxe)) + fabsf(b) * fmaxf(fabsf(dys), fabsf(dye));
-        const float delta = m * (64.0f / 16777216.0f);
-        any_neg = any_neg || emax < -delta;
-        any_pos = any_pos || emin > delta;
-    }
-    return !(any_neg && any_pos);
-}
+// (pair_may_cover -- can a triangle cover any pixel of a tile? -- and the clamp / walk / byte of the small slots live in swr_device.h:
+// k_setup, which decides, is also compiled at run time for user vertex programs, against that header.)
 
 // A FILL position beyond the list capacity.  k_scan_apply already refuses batches whose COUNT total does not fit, so this
 // means COUNT and FILL disagreed (a bug) or a debug capacity (SWR_DEBUG_FILL_CAPACITY) -- either way the pair must not be
@@ -182,35 +141,21 @@ __device__ __forceinline__ void tile_place_block(const BinArgs& a, uint32_t bloc
 // what binning needs to know about one primitive slot
 struct SlotData {
     int tminx, tminy, nx, ny;            // tile bbox clamped to the band (nx = ny = 0: nothing to bin)
-    float sx[3], sy[3];
+    float sx[3], sy[3];                  // the rest: big slots only (bin_big)
     int minX, maxX, minY, maxY;          // pixel bbox
     bool is_line;
 };
-__device__ __forceinline__ SlotData slot_none() {
+// tb = a.slot_tb[slot] (SWR_TB_INVALID for a slot outside the round): the caller fetches it one slot ahead.  The record is read only
+// for a slot of more than SWR_SMALL_TILES tiles; a small one is binned from its want byte alone.
+__device__ __forceinline__ SlotData slot_load(const BinArgs& a, uint32_t slot, unsigned long long tb) {
     SlotData s;
-    s.tminx = s.tminy = s.nx = s.ny = 0;
     s.sx[0] = s.sx[1] = s.sx[2] = s.sy[0] = s.sy[1] = s.sy[2] = 0.f;
     s.minX = s.minY = 0; s.maxX = s.maxY = -1; s.is_line = false;
-    return s;
-}
-// tile bbox word (k_setup) -> clamped to the band; false when the slot has nothing in this band
-__device__ __forceinline__ bool slot_tiles(const BinArgs& a, unsigned long long tb, SlotData& s) {
-    if (tb == SWR_TB_INVALID) return false;
-    s.tminx = (int)(tb & 0xffff);
-    const int tmaxx = (int)((tb >> 16) & 0xffff);
-    s.tminy = max((int)((tb >> 32) & 0xffff), a.band_ty0);
-    const int tmaxy = min((int)((tb >> 48) & 0xffff), a.band_ty1 - 1);
-    s.nx = tmaxx - s.tminx + 1;
-    s.ny = tmaxy - s.tminy + 1;
-    if (s.ny <= 0) { s.nx = 0; s.ny = 0; return false; }
-    return true;
-}
-// with_rec = false: only the tile bbox (FILL of a small triangle replays COUNT's decisions from a.want)
-// tb = a.slot_tb[slot] (SWR_TB_INVALID for a slot outside the round): the caller fetches it one slot ahead
-__device__ __forceinline__ SlotData slot_load(const BinArgs& a, uint32_t slot, unsigned long long tb, bool with_rec_small) {
-    SlotData s = slot_none();
-    if (slot_tiles(a, tb, s) && (with_rec_small || s.nx * s.ny > 8)) {
-        const float4* __restrict__ rq = reinterpret_cast<const float4*>(a.recs + slot);
+    SlotTiles st;
+    slot_tiles(a.band, tb, st);
+    s.tminx = st.tminx; s.tminy = st.tminy; s.nx = st.nx; s.ny = st.ny;
+    if (s.nx * s.ny > SWR_SMALL_TILES) {
+        const float4* __restrict__ rq = reinterpret_cast<const float4*>(a.recs + rec_index(slot, a.odd_base));
         const float4 r0 = rq[0], r1 = rq[1], r3 = rq[3];
         s.sx[0] = r0.x; s.sx[1] = r0.y; s.sx[2] = r0.z; s.sy[0] = r0.w; s.sy[1] = r1.x; s.sy[2] = r1.y;
         const uint32_t bbx = __float_as_uint(r3.y), bby = __float_as_uint(r3.z);
@@ -302,7 +247,8 @@ __device__ __forceinline__ void bin_big(const BinArgs& a, const SlotData& sd, ui
 }
 
 // Thread per submitted triangle, walking its `spt` slots (the odd fan slots are almost always empty).
-// Triangles of <= 8 tiles (nearly all): the block's (tile, slot) pairs are first combined in an LDS hash table
+// Triangles of <= 8 tiles (nearly all): which of them are binned was decided by k_setup (the byte want[slot]); COUNT and FILL both
+// replay it and differ only in what they do with the atomics' results.  The block's (tile, slot) pairs are first combined in an LDS hash table
 // keyed by tile -- neighbouring triangles share tiles, so 256 triangles touch few distinct ones -- and only one
 // global atomic per distinct tile leaves the block; FILL gets each pair's rank from the LDS add and the tile's base
 // from that one global atomic.  The order inside a tile's list is irrelevant here (k_sort_tiles restores it).
@@ -312,29 +258,24 @@ __device__ __forceinline__ void bin_big(const BinArgs& a, const SlotData& sd, ui
 // one slot per thread of a 256-thread block (tb = its tile bbox word, SWR_TB_INVALID: nothing); every thread of the block must call
 template <bool FILL>
 __device__ __forceinline__ void bin_block_slots(const BinArgs& a, uint32_t slot, unsigned long long tb, uint32_t want_in, uint32_t* s_key, uint32_t* s_val) {
-    const SlotData sd = slot_load(a, slot, tb, !FILL);
+    const SlotData sd = slot_load(a, slot, tb);
     const int nt = sd.nx * sd.ny;
-    const bool big = nt > 8;
+    const bool big = nt > SWR_SMALL_TILES;
     const int nt_small = big ? 0 : nt;
     if (!__syncthreads_or(nt != 0)) return;                    // block-uniform (also orders the table's reuse)
     for (int e = threadIdx.x; e < SWR_BIN_TABLE; e += 256) { s_key[e] = 0u; s_val[e] = 0u; }
     __syncthreads();
     // phase 1: every wanted (tile, slot) pair into the table; packed[i] = entry | rank << 12 | wanted << 31
-    uint32_t packed[8];
-    int wtx = sd.tminx, wty = sd.tminy;                         // row-major walk of the tile bbox without integer division
-    uint32_t wmask = (FILL && nt_small) ? want_in : 0u;            // FILL: COUNT's decisions (a.want[slot], fetched with tb)
+    uint32_t packed[SWR_SMALL_TILES];
+    SlotTiles st; st.tminx = sd.tminx; st.tminy = sd.tminy; st.nx = sd.nx; st.ny = sd.ny;
+    SmallTileWalk w(st);                                        // the walk k_setup numbered the bits by
+    const uint32_t wmask = nt_small ? want_in : 0u;             // k_setup's decisions (a.want[slot], fetched with tb)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < SWR_SMALL_TILES; ++i) {
         packed[i] = 0u;
         if (i < nt_small) {
-            bool want;
-            if (FILL) want = ((wmask >> i) & 1u) != 0u;
-            else {
-                want = band_local_row(a.band, wty) >= 0 && pair_may_cover(sd.sx, sd.sy, sd.minX, sd.maxX, sd.minY, sd.maxY, wtx, wty, a.width, a.height, sd.is_line);
-                wmask |= want ? (1u << i) : 0u;
-            }
-            if (want) {
-                const uint32_t tile = (uint32_t)(band_local_row(a.band, wty) * a.tiles_x + wtx);
+            if ((wmask >> i) & 1u) {
+                const uint32_t tile = (uint32_t)(band_local_row(a.band, w.ty) * a.tiles_x + w.tx);
                 uint32_t e = (tile * 0x9E3779B1u) >> (32 - SWR_BIN_TABLE_LOG2);
                 bool placed = false;
                 for (int probe = 0; probe < 16; ++probe) {
@@ -353,11 +294,9 @@ __device__ __forceinline__ void bin_block_slots(const BinArgs& a, uint32_t slot,
                     atomicAdd(&a.tile_count[tile], 1u);
                 }
             }
-            ++wtx;
-            if (wtx >= sd.tminx + sd.nx) { wtx = sd.tminx; ++wty; }
+            w.next();
         }
     }
-    if (!FILL && nt_small) a.want[slot] = (uint8_t)wmask;
     __syncthreads();
     // phase 2: one global atomic per distinct tile of the block
     for (int e = threadIdx.x; e < SWR_BIN_TABLE; e += 256) {
@@ -372,7 +311,7 @@ __device__ __forceinline__ void bin_block_slots(const BinArgs& a, uint32_t slot,
         __syncthreads();
         // phase 3: list position = the tile's base for this block + the pair's rank in the block
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < SWR_SMALL_TILES; ++i) {
             if (packed[i] & 0x80000000u) {
                 const uint32_t at = s_val[packed[i] & 0xfffu] + ((packed[i] >> 12) & 0x7ffffu);
                 if (at < a.list_capacity) a.tile_list[at] = slot;
@@ -401,7 +340,7 @@ __global__ __launch_bounds__(256) void k_bin(BinArgs a) {
     // barriers: this takes one round trip out of every slot but the first)
     auto in_round = [&](uint32_t si) { return has_tri && si < a.spt && first + si < a.slot_hi; };
     auto tb_of = [&](uint32_t si) { return in_round(si) ? a.slot_tb[first + si] : SWR_TB_INVALID; };
-    auto want_of = [&](uint32_t si) { return (FILL && in_round(si)) ? (uint32_t)a.want[first + si] : 0u; };   // (a byte of a slot COUNT never wrote is never used)
+    auto want_of = [&](uint32_t si) { return in_round(si) ? (uint32_t)a.want[first + si] : 0u; };   // (a byte k_setup never wrote belongs to an invalid slot and is never used)
     unsigned long long tb = tb_of(0);
     uint32_t wm = want_of(0);
     for (uint32_t si = 0; si < a.spt; ++si) {

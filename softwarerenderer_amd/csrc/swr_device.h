@@ -171,6 +171,120 @@ __host__ __device__ __forceinline__ BandMap band_map(const FrameParams& fp) {
     return b;
 }
 
+// ---------------------------------------------------------------- slots, records and the binning decisions ----
+// A batch numbers its primitives by SLOT in submission order (k_setup): `spt` slots per submitted triangle -- filled mode 2 (slot 2t =
+// the triangle, or the first fan triangle of its near-clipped polygon; slot 2t+1 = the second fan triangle, which exists only where the
+// near plane cuts a triangle into a quad), wireframe 6 (three DrawLine edges per fan triangle).  slot_tb[] (tile bbox word) and want[]
+// (below) are indexed by slot, and the slot is the key by which k_sort_tiles restores submission order.
+//
+// WHERE THE RECORD OF A SLOT IS: the single definition.  Filled batches store the records densely -- odd slots are almost always
+// empty, and records indexed by slot would sit 128 B apart with a dead 64 B between them --: even slots at s >> 1, odd slots in a
+// second region at odd_base + (s >> 1), odd_base = the batch's triangle count rounded up to a whole 128 B line (record_odd_base).
+// odd_base == 0 is the identity (wireframe batches).  Batch-uniform: an argument of k_setup, k_bin and k_cover; the raster kernel never
+// sees slots -- k_cover hands it the record index in refs[].x.
+__host__ __device__ __forceinline__ uint32_t rec_index(uint32_t slot, uint32_t odd_base) {
+    if (odd_base == 0u) return slot;
+    return (slot & 1u) ? odd_base + (slot >> 1) : (slot >> 1);
+}
+__host__ __device__ __forceinline__ uint32_t record_odd_base(uint64_t triangles) { return (uint32_t)((triangles + 1u) & ~(uint64_t)1u); }
+
+// Can triangle (sx, sy, pixel bbox) cover ANY pixel of tile (tx, ty)?  Conservative: returns false only when
+// provably no pixel of bbox /\ tile can pass the reference's coverage test (all three incrementally stepped
+// float32 edge values >= 0, or all three <= 0; Rasterizer.cs:481-494).  The reference visits such tiles and
+// finds nothing, so dropping the pair changes no pixel and no counter.
+//
+// Proof sketch.  Let R be the pixel rectangle bbox /\ tile and, for edge k with float coefficients (a, b) and
+// reference vertex (rx, ry), E(x,y) = a*(x-rx) + b*(y-ry) in real arithmetic; u = 2^-24.  Every value the
+// reference's float chain takes is fl-arithmetic on points of R: the start value costs <= 5 roundings of
+// quantities bounded by M = |a|*max|x-rx| + |b|*max|y-ry| over R, and each of the <= 30 chain adds rounds a value
+// of magnitude <= M(1+tiny); so |W - E| <= 35uM(1+tiny) at every pixel of R.  E is linear, so its extrema over R
+// are at corners; evaluating them in float32 as below costs <= 3 roundings per term, |Efl - E| <= 6uM, and the
+// float M' satisfies M' >= M(1-4u).  With delta = 64uM':
+//   Efl_max < -delta  =>  W <= E_max + 35uM <= Efl_max + 41uM < -64uM(1-4u) + 41uM < 0 on all of R  (kills "all >= 0")
+//   Efl_min >  delta  =>  W > 0 on all of R                                                          (kills "all <= 0")
+// The analysis needs every product and sum finite: screen coordinates below 1e15 in magnitude (tested once per triangle, not
+// per tile and edge as in round 2) bound every term by 1e31; anything else (NaN / Inf included) means "keep".
+__device__ __forceinline__ bool pair_may_cover(const float sx[3], const float sy[3], int minX, int maxX, int minY, int maxY,
+                                               int tx, int ty, int width, int height, bool is_line) {
+    if (is_line) return true;         // DrawLine edges: keep every tile of the line's bbox (the test below is for triangles)
+    const int x0 = tx * SWR_TILE, y0 = ty * SWR_TILE;
+    const int startX = max(minX, x0), endX = min(maxX, min(x0 + SWR_TILE - 1, width - 1));
+    const int startY = max(minY, y0), endY = min(maxY, min(y0 + SWR_TILE - 1, height - 1));
+    if (startX > endX || startY > endY) return false;                 // Rasterizer.cs:476: nothing visited
+    // edge k: coefficients exactly as RasterizeTriangle forms them (Rasterizer.cs:445-447), reference vertex :481-483
+    const float ea[3] = { sy[1] - sy[2], sy[2] - sy[0], sy[0] - sy[1] };   // a12, a20, a01
+    const float eb[3] = { sx[2] - sx[1], sx[0] - sx[2], sx[1] - sx[0] };   // b12, b20, b01
+    const float rx[3] = { sx[1], sx[2], sx[0] };
+    const float ry[3] = { sy[1], sy[2], sy[0] };
+    const float fxs = (float)startX, fxe = (float)endX, fys = (float)startY, fye = (float)endY;
+    const float lim = 1.0e15f;
+    const bool tame = fabsf(sx[0]) < lim && fabsf(sx[1]) < lim && fabsf(sx[2]) < lim && fabsf(sy[0]) < lim && fabsf(sy[1]) < lim && fabsf(sy[2]) < lim;
+    if (!tame) return true;
+    bool any_neg = false, any_pos = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float a = ea[k], b = eb[k];
+        const float dxs = fxs - rx[k], dxe = fxe - rx[k], dys = fys - ry[k], dye = fye - ry[k];
+        const float ax_s = a * dxs, ax_e = a * dxe, by_s = b * dys, by_e = b * dye;
+        const float emax = fmaxf(ax_s, ax_e) + fmaxf(by_s, by_e);
+        const float emin = fminf(ax_s, ax_e) + fminf(by_s, by_e);
+        const float m = fabsf(a) * fmaxf(fabsf(dxs), fabsf(dxe)) + fabsf(b) * fmaxf(fabsf(dys), fabsf(dye));
+        const float delta = m * (64.0f / 16777216.0f);
+        any_neg = any_neg || emax < -delta;
+        any_pos = any_pos || emin > delta;
+    }
+    return !(any_neg && any_pos);
+}
+
+// The tile bbox word of a slot (k_setup: tminx | tmaxx << 16 | tminy << 32 | tmaxy << 48), clamped to the tile rows the context bins:
+// [band.ty0, band.ty1) -- the contiguous band, or the whole frame under interleaved stripes, where band_local_row decides row by row.
+// false (and nx = ny = 0) when the slot has nothing there.  One definition for k_setup, which writes want[], and k_bin, which reads it.
+struct SlotTiles { int tminx, tminy, nx, ny; };
+__device__ __forceinline__ bool slot_tiles(const BandMap& band, unsigned long long tb, SlotTiles& s) {
+    s.tminx = s.tminy = s.nx = s.ny = 0;
+    if (tb == SWR_TB_INVALID) return false;
+    s.tminx = (int)(tb & 0xffff);
+    const int tmaxx = (int)((tb >> 16) & 0xffff);
+    s.tminy = max((int)((tb >> 32) & 0xffff), band.ty0);
+    const int tmaxy = min((int)((tb >> 48) & 0xffff), band.ty1 - 1);
+    s.nx = tmaxx - s.tminx + 1;
+    s.ny = tmaxy - s.tminy + 1;
+    if (s.ny <= 0) { s.nx = 0; s.ny = 0; return false; }
+    return true;
+}
+// A slot of at most SWR_SMALL_TILES clamped tiles is SMALL (nearly all are): bit i of its byte want[slot] says whether its i-th tile,
+// in the row-major order of SmallTileWalk, is binned -- the row is this context's and pair_may_cover holds.  k_setup decides that where
+// it has the triangle in registers (small_want_mask); both k_bin passes replay the byte and read no record of a small slot.  Writer
+// and readers walk the tiles with the same SmallTileWalk over the same slot_tiles() clamp: a disagreement would drop or duplicate a pair.
+#define SWR_SMALL_TILES 8
+struct SmallTileWalk {              // row-major over the clamped tile bbox, without integer division
+    int tx, ty, x_lo, x_end;
+    __device__ __forceinline__ explicit SmallTileWalk(const SlotTiles& s) : tx(s.tminx), ty(s.tminy), x_lo(s.tminx), x_end(s.tminx + s.nx) {}
+    __device__ __forceinline__ void next() { ++tx; if (tx >= x_end) { tx = x_lo; ++ty; } }
+};
+__device__ __forceinline__ uint32_t small_want_mask(const BandMap& band, unsigned long long tb, const float sx[3], const float sy[3],
+                                                    int minX, int maxX, int minY, int maxY, int width, int height, bool is_line) {
+    SlotTiles st;
+    if (!slot_tiles(band, tb, st)) return 0u;
+    const int nt = st.nx * st.ny;
+    if (nt > SWR_SMALL_TILES) return 0u;                    // big: k_bin spreads it over a wave and tests there (bin_big)
+    uint32_t mask = 0u;
+    SmallTileWalk w(st);
+    // two tiles per trip: their tests are independent chains, and in a small batch (one wave per SIMD) k_setup's time is the length
+    // of that chain (cfg2: -0.7 us against one tile per trip; four and eight measured no better, profiles/r07_front_end_records.md)
+#pragma unroll 1
+    for (int i0 = 0; i0 < nt; i0 += 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int i = i0 + j;
+            const bool want = i < nt && band_local_row(band, w.ty) >= 0 && pair_may_cover(sx, sy, minX, maxX, minY, maxY, w.tx, w.ty, width, height, is_line);
+            mask |= want ? (1u << i) : 0u;
+            w.next();
+        }
+    }
+    return mask;
+}
+
 // ---------------------------------------------------------------- .NET scalar semantics ----
 __device__ __forceinline__ bool is_neg_bits(float f) { return (__float_as_uint(f) >> 31) != 0u; }
 __device__ __forceinline__ bool is_nan(float f) { return f != f; }

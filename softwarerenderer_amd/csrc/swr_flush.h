@@ -97,6 +97,7 @@ struct Pass {
     int mode;
     bool cc, cd;           // clears still owed: the first raster kernel pays them, or run_clear
     UploadLayout up = {};
+    uint32_t odd_base = 0;  // the batch's record layout (rec_index, swr_device.h): filled batches dense, wireframe 0 = one record per slot
 };
 
 // the batch's fragment program reads VertexOutput.Normal (DEBUG_VARYINGS, every user program): k_vertex and the clipper store it
@@ -104,6 +105,9 @@ static bool b_needs_vnorm(const Batch& b) { return !b.draws.empty() && kernel_cl
 static bool b_has_user_program(const Batch& b) { return !b.draws.empty() && b.draws[0].p.program >= SWR_PROG_USER_BASE; }
 // ... and that program has a vertex half: its k_vertex_user and k_setup run instead of the library's
 static bool b_has_user_vertex(const Batch& b) { return b_has_user_program(b) && b.draws[0].prog && b.draws[0].prog->vertex_fn; }
+#ifndef SWR_DENSE_RECORDS
+#define SWR_DENSE_RECORDS 1     // 0: records indexed by slot in filled batches too (A/B switch of profiles/r07_front_end_records.md)
+#endif
 const unsigned long long kMaxPairs = 1ull << 30;       // list entries per round (4 GiB of slot ids)
 
 // pairs every set in use can hold (the optimistic flush is checked against this on the device)
@@ -160,11 +164,12 @@ int bin_and_raster(swr_context* c, Pass& P, uint32_t lo, uint32_t hi, bool count
     BinArgs ba;
     ba.slot_tb = c->d_slot_tb.as<unsigned long long>();
     ba.recs = S.d_recs.as<TriRec>();
+    ba.odd_base = P.odd_base;
     ba.slot_lo = lo; ba.slot_hi = hi;
     ba.spt = b.wireframe ? 6u : 2u;
     ba.width = c->W; ba.height = c->H;
-    ba.tiles_x = c->tiles_x; ba.band_ty0 = c->band_ty0; ba.band_ty1 = c->band_ty1;
-    ba.band = host_band_map(c);
+    ba.tiles_x = c->tiles_x;
+    ba.band = host_band_map(c);               // (the same context fields frame_params() hands k_setup, which decided `want` by them)
     ba.tile_count = S.d_tile_count.as<uint32_t>();
     ba.tile_start = S.d_tile_start.as<uint32_t>();
     ba.tile_list = c->d_tile_list.as<uint32_t>();
@@ -241,6 +246,7 @@ int bin_and_raster(swr_context* c, Pass& P, uint32_t lo, uint32_t hi, bool count
         ScopedSpan sp(c, ST_COVER, F);
         CoverArgs ca;
         ca.recs = S.d_recs.as<TriRec>();
+        ca.odd_base = P.odd_base;
         ca.tile_list = c->d_tile_list.as<uint32_t>();
         ca.pair_tile = c->d_pair_tile.as<uint32_t>();
         ca.masks = S.d_masks.as<uint4>();
@@ -410,12 +416,14 @@ int launch_geometry(swr_context* c, const Pass& P, const BatchGeometry& g, uint3
         VOut* a_pool = S.d_vout.as<VOut>() + g.V;
         uint32_t a_pool_base = (uint32_t)g.V;
         TriRec* a_recs = S.d_recs.as<TriRec>();
+        uint32_t a_odd_base = P.odd_base;
         unsigned long long* a_tb = c->d_slot_tb.as<unsigned long long>();
+        uint8_t* a_want = c->d_want.as<uint8_t>();
         Counters* a_counters = c->d_counters.as<Counters>();
         const Ctrl* a_ctrl = c->d_ctrl.as<Ctrl>();
         uint32_t a_seq = b.seq;
         int a_count = count_stats, a_wire = b.wireframe ? 1 : 0;
-        void* args[] = { &d_draws, &d_tblocks, &a_vout, &a_pool, &a_pool_base, &a_recs, &a_tb, &fp, &a_counters, &a_ctrl, &a_seq,
+        void* args[] = { &d_draws, &d_tblocks, &a_vout, &a_pool, &a_pool_base, &a_recs, &a_odd_base, &a_tb, &a_want, &fp, &a_counters, &a_ctrl, &a_seq,
                          &a_count, &a_wire, &d_visible, &a_vnorm };
         SWR_HIP(c, launch(vprog ? vprog->setup_fn : nullptr, (const void*)k_setup, g.tblocks.size(), args));
     }
@@ -467,7 +475,10 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
     if ((rc = ensure(c, S.d_upload, P.up.bytes))) return rc;
     if ((rc = ensure(c, S.d_vout, (size_t)(V + 4 * T) * sizeof(VOut)))) return rc;
     if (b_needs_vnorm(b) && (rc = ensure(c, S.d_vnorm, S.d_vout.cap / 4))) return rc;        // one float4 per VOut entry
-    if ((rc = ensure(c, S.d_recs, (size_t)(spt * T) * sizeof(TriRec)))) return rc;
+    // filled batches keep their records densely (rec_index, swr_device.h): T even-slot records, then from a whole line on the T records of
+    // the odd slots (second fan triangles of near-clipped quads: almost never touched); wireframe batches one record per slot
+    P.odd_base = (b.wireframe || !SWR_DENSE_RECORDS) ? 0u : record_odd_base(T);
+    if ((rc = ensure(c, S.d_recs, (size_t)(spt * T + 2) * sizeof(TriRec)))) return rc;
     if ((rc = ensure(c, c->d_slot_tb, (size_t)(spt * T) * 8))) return rc;
     if ((rc = ensure(c, c->d_want, (size_t)(spt * T) + 64))) return rc;
     if ((rc = ensure(c, S.d_tile_count, (size_t)n_tiles * 4))) return rc;

@@ -226,14 +226,16 @@ __device__ __forceinline__ void load_vout(const VOut* __restrict__ src, VOut& v)
 }
 
 // DrawTriangle + RasterizeTriangle prologue for one (possibly clipped) triangle.
-// v0,v1,v2 in submission order; r0,r1,r2 their VOut indices.  Fills rec[0] / tb[0] and returns 1 when the
-// triangle reaches the tile loop.  In DebugMode.Wireframe (Rasterizer.cs:419-425) it emits instead up to three
+// v0,v1,v2 in submission order; r0,r1,r2 their VOut indices.  Fills rec[0] / tb[0] / wnt[0] (the slot's record, its tile bbox
+// word and, while the triangle is in registers, which of its tiles binning takes: small_want_mask, swr_device.h) and returns 1 when
+// the triangle reaches the tile loop.  In DebugMode.Wireframe (Rasterizer.cs:419-425) it emits instead up to three
 // DrawLine records rec[0..2] (edges s0-s1, s1-s2, s2-s0, each with depths[0..1] and outputs[0..1] of the
 // TRIANGLE, as the reference passes them) and returns 0 (the oracle's triangles_setup counts filled triangles only).
 __device__ __forceinline__ int setup_triangle(const FrameParams& fp, int cull, uint32_t draw,
                                               const SVert& v0, const SVert& v1, const SVert& v2,
                                               uint32_t r0, uint32_t r1, uint32_t r2,
-                                              TriRec* __restrict__ rec, unsigned long long* __restrict__ tb, bool wireframe,
+                                              TriRec* __restrict__ rec, unsigned long long* __restrict__ tb, uint32_t* __restrict__ wnt,
+                                              bool wireframe,
                                               float4* __restrict__ rec_regs = nullptr /* filled mode: the record goes here instead of to
                                                                                          memory (k_setup stores a wave's records together) */) {
     const int rw = fp.width, rh = fp.height;
@@ -277,6 +279,7 @@ __device__ __forceinline__ int setup_triangle(const FrameParams& fp, int cull, u
                                  __uint_as_float(flags | SWR_FLAG_LINE));
             tb[e] = (unsigned long long)(minX / SWR_TILE) | ((unsigned long long)(maxX / SWR_TILE) << 16) |
                     ((unsigned long long)(minY / SWR_TILE) << 32) | ((unsigned long long)(maxY / SWR_TILE) << 48);
+            wnt[e] = small_want_mask(band_map(fp), tb[e], sx, sy, minX, maxX, minY, maxY, rw, rh, true);
         }
         return 0;
     }
@@ -305,6 +308,7 @@ __device__ __forceinline__ int setup_triangle(const FrameParams& fp, int cull, u
     // tile bbox (Rasterizer.cs:449-452), 16 bits each: tminx | tmaxx<<16 | tminy<<32 | tmaxy<<48
     tb[0] = (unsigned long long)(minX / SWR_TILE) | ((unsigned long long)(maxX / SWR_TILE) << 16) |
             ((unsigned long long)(minY / SWR_TILE) << 32) | ((unsigned long long)(maxY / SWR_TILE) << 48);
+    wnt[0] = small_want_mask(band_map(fp), tb[0], sx, sy, minX, maxX, minY, maxY, rw, rh, false);
     return 1;
 }
 
@@ -318,7 +322,9 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_setup(const DrawParams* __re
                                                VOut* __restrict__ clip_pool,     // 4 VOut per triangle, indexed by global triangle
                                                uint32_t clip_pool_base,          // VOut index of clip_pool[0]
                                                TriRec* __restrict__ recs,
+                                               uint32_t odd_base,                // where the record of a slot is: rec_index(), swr_device.h
                                                unsigned long long* __restrict__ slot_tb,
+                                               uint8_t* __restrict__ want,       // per slot: the tiles binning takes (small_want_mask)
                                                FrameParams fp,
                                                Counters* __restrict__ counters /* 64 replicas */,
                                                const Ctrl* __restrict__ ctrl, uint32_t seq, int count_stats, int wireframe,
@@ -346,6 +352,7 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_setup(const DrawParams* __re
         const uint32_t per_fan = wireframe ? 3u : 1u;
         const uint32_t slot = 2u * per_fan * gt;
         unsigned long long tbs[6] = { SWR_TB_INVALID, SWR_TB_INVALID, SWR_TB_INVALID, SWR_TB_INVALID, SWR_TB_INVALID, SWR_TB_INVALID };
+        uint32_t wnt[6] = { 0u, 0u, 0u, 0u, 0u, 0u };
 
         const uint16_t* __restrict__ ip = dp->idx + 3u * local;
         const uint32_t r0 = dp->vert_base + ip[0], r1 = dp->vert_base + ip[1], r2 = dp->vert_base + ip[2];
@@ -417,28 +424,30 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_setup(const DrawParams* __re
 #endif
                     // fan (0, k, k+1), Rasterizer.cs:154-157
                     n_setup += setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), poly[0], poly[1], poly[2],
-                                              pbase, pbase + 1, pbase + 2, recs + slot, &tbs[0], wireframe != 0);
+                                              pbase, pbase + 1, pbase + 2, recs + rec_index(slot, odd_base), &tbs[0], &wnt[0], wireframe != 0);
                     if (n == 4) n_setup += setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), poly[0], poly[2], poly[3],
-                                                          pbase, pbase + 2, pbase + 3, recs + slot + per_fan, &tbs[3], wireframe != 0);
+                                                          pbase, pbase + 2, pbase + 3, recs + rec_index(slot + per_fan, odd_base), &tbs[3], &wnt[3], wireframe != 0);
                 }
             } else {
                 if (!wireframe) {
-                    rec_valid = setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), v[0], v[1], v[2], r0, r1, r2, recs + slot, &tbs[0], false, rec_q) != 0;
+                    rec_valid = setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), v[0], v[1], v[2], r0, r1, r2, nullptr, &tbs[0], &wnt[0], false, rec_q) != 0;
                     n_setup += rec_valid ? 1u : 0u;
                 } else
-                n_setup += setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), v[0], v[1], v[2], r0, r1, r2, recs + slot, &tbs[0], wireframe != 0);
+                n_setup += setup_triangle(fp, dp->cull, SWR_FRAG_DRAW(dp, bm), v[0], v[1], v[2], r0, r1, r2, recs + rec_index(slot, odd_base), &tbs[0], &wnt[0], wireframe != 0);
             }
         }
         if (wireframe) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) slot_tb[slot + k] = tbs[k];
+            for (int k = 0; k < 6; ++k) { slot_tb[slot + k] = tbs[k]; want[slot + k] = (uint8_t)wnt[k]; }
         } else {
             *reinterpret_cast<ulonglong2*>(slot_tb + slot) = make_ulonglong2(tbs[0], tbs[3]);      // slot is even: one 16-byte store
+            *reinterpret_cast<uint16_t*>(want + slot) = (uint16_t)(wnt[0] | (wnt[3] << 8));          // ... and one 2-byte store
         }
     }
 
-    // A lane's 64-byte TriRec would leave as four 16-byte stores, 128 bytes apart from its neighbour's (256 partial line writes per
-    // wave: 16 of the kernel's 37 us).  The wave's records go through LDS and leave as four stores of sixteen whole records each.
+    // A lane's 64-byte TriRec would leave as four 16-byte stores (256 partial line writes per wave: 16 of the kernel's 37 us).  The
+    // wave's records go through LDS and leave as four stores of sixteen whole records each -- with the dense record layout (rec_index)
+    // consecutive lanes' records are consecutive in memory: 4 KB contiguous per wave.
     {
         __shared__ float4 s_rec[SWR_GEOM_BLOCK / 64][256];
         static_assert(sizeof(s_rec) + 16 <= SWR_FRONT_MAX_LDS, "k_setup must fit beside the raster kernel (swr_device.h)");
@@ -449,12 +458,13 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_setup(const DrawParams* __re
             sw[4 * lane + 0] = rec_q[0]; sw[4 * lane + 1] = rec_q[1]; sw[4 * lane + 2] = rec_q[2]; sw[4 * lane + 3] = rec_q[3];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // one wave: its own LDS accesses complete in order
             __builtin_amdgcn_wave_barrier();
-            // lane j's triangle is dp->tri_base + bm.first + 64 wv + j, its record slot twice that (filled mode: two slots per triangle)
-            float4* dst = reinterpret_cast<float4*>(recs + 2u * (size_t)(dp->tri_base + bm.first + wv * 64u));
+            // lane j's triangle is dp->tri_base + bm.first + 64 wv + j, its slot twice that (filled mode: two slots per triangle)
+            const uint32_t slot0 = 2u * (dp->tri_base + bm.first + wv * 64u);
+            float4* dst = reinterpret_cast<float4*>(recs);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t e = (uint32_t)k * 64u + lane, j = e >> 2;
-                if ((vmask >> j) & 1ull) dst[8u * j + (e & 3u)] = sw[e];
+                if ((vmask >> j) & 1ull) dst[4u * (size_t)rec_index(slot0 + 2u * j, odd_base) + (e & 3u)] = sw[e];
             }
         }
     }

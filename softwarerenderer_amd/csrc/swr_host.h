@@ -148,7 +148,7 @@ struct swr_context {
     DevBuf d_pair_tile, d_ctrl;
     uint32_t* host_poison = nullptr;           // pinned, device-visible copy of Ctrl::poison
     DevBuf d_tile_list, d_tile_stats, d_counters, d_total, d_scratch;
-    DevBuf d_want;           // 1 byte per slot: COUNT's pair_may_cover decisions, replayed by FILL
+    DevBuf d_want;           // 1 byte per slot: which tiles of a small slot are binned -- written by k_setup, replayed by both k_bin passes
     size_t tile_stats_tiles = 0;
     swr_stats totals = {};
     unsigned long long host_tile_pairs = 0;   // rounds sized on the host (MODE_SYNC)

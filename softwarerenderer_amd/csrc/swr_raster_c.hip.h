@@ -89,12 +89,13 @@ __device__ __forceinline__ float wave_min(float x) {
 
 struct CoverArgs {
     const TriRec* __restrict__ recs;
+    uint32_t odd_base;                        // where the record of a slot is: rec_index(slot, odd_base), swr_device.h
     const uint32_t* __restrict__ tile_list;   // sorted: slot id per pair
     const uint32_t* __restrict__ pair_tile;   // band-local tile index per pair
     uint4* __restrict__ masks;                // 2 x uint4 per pair: row r -> bits (r & 1) * 16 .. of word r >> 1
     uint2* __restrict__ info;                 // {popcount of the mask, hi-Z bound: an upper bound of the pair's fragment depths
                                               //  over bbox /\ tile as float bits (+inf = no bound)}: one load in the raster kernel's window
-    uint4* __restrict__ refs;                 // {slot, vertex references of outputs[0..2]}: the raster kernel's batch set-up
+    uint4* __restrict__ refs;                 // {record index, vertex references of outputs[0..2]}: the raster kernel's batch set-up
                                               // then needs no load that depends on another load
     const unsigned long long* __restrict__ n_pairs;   // device-resident pair total of this batch
     const Ctrl* __restrict__ ctrl;
@@ -156,10 +157,12 @@ __global__ __launch_bounds__(SWR_COVER_BLOCK) void k_cover(CoverArgs a) {
             s_rows[threadIdx.x][2] = (uint16_t)tile; s_rows[threadIdx.x][3] = (uint16_t)(tile >> 16);
             const int tx = (int)(tile % (uint32_t)a.fp.tiles_x), ty = band_global_row(band_map(a.fp), (int)(tile / (uint32_t)a.fp.tiles_x));
             const int x0 = tx * SWR_TILE, y0 = ty * SWR_TILE;
-            const float4 r3 = reinterpret_cast<const float4*>(a.recs + slot)[3];
-            {   // {slot, vertex references of outputs[0..2]}: words 10, 11, 12 of the TriRec
-                const float2 r2zw = reinterpret_cast<const float2*>(a.recs + slot)[5];
-                a.refs[p_own] = make_uint4(slot, __float_as_uint(r2zw.x), __float_as_uint(r2zw.y), __float_as_uint(r3.x));
+            const uint32_t ri = rec_index(slot, a.odd_base);
+            const float4 r3 = reinterpret_cast<const float4*>(a.recs + ri)[3];
+            {   // {record index, vertex references of outputs[0..2]}: words 10, 11, 12 of the TriRec.  The raster kernel knows the
+                // record by this index only (a.recs + ref.x), never the slot: the record layout (rec_index) ends here
+                const float2 r2zw = reinterpret_cast<const float2*>(a.recs + ri)[5];
+                a.refs[p_own] = make_uint4(ri, __float_as_uint(r2zw.x), __float_as_uint(r2zw.y), __float_as_uint(r3.x));
             }
             const uint32_t bbx = __float_as_uint(r3.y), bby = __float_as_uint(r3.z);
             const int w = min((int)(bbx >> 16), min(x0 + SWR_TILE - 1, a.fp.width - 1)) - max((int)(bbx & 0xffffu), x0) + 1;
@@ -224,7 +227,7 @@ __global__ __launch_bounds__(SWR_COVER_BLOCK) void k_cover(CoverArgs a) {
         const int tx = (int)(tile % (uint32_t)a.fp.tiles_x), ty = band_global_row(band_map(a.fp), (int)(tile / (uint32_t)a.fp.tiles_x));
         const int x0 = tx * SWR_TILE, y0 = ty * SWR_TILE;
         const int tile_end_x = min(x0 + SWR_TILE - 1, a.fp.width - 1), tile_end_y = min(y0 + SWR_TILE - 1, a.fp.height - 1);
-        const float4* __restrict__ rq = reinterpret_cast<const float4*>(a.recs + slot);
+        const float4* __restrict__ rq = reinterpret_cast<const float4*>(a.recs + rec_index(slot, a.odd_base));
         const float4 r0 = rq[0], r1 = rq[1], r2 = rq[2], r3 = rq[3];      // (r3 through LDS as well: no change, measured)
         const float s0x = r0.x, s1x = r0.y, s2x = r0.z, s0y = r0.w, s1y = r1.x, s2y = r1.y;
         const uint32_t bbx = __float_as_uint(r3.y), bby = __float_as_uint(r3.z);
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(SWR_COVER_BLOCK) void k_cover(CoverArgs a) {
         // Hierarchical-Z bound for the raster kernel (used there only under Less / LessEqual, where stored depth only
         // grows): U >= every fragment depth of this pair.  Proof (u = 2^-24, R = bbox /\ tile, M_i as in
         // pair_may_cover, S = sum |d_i invArea| M_i): every edge value of the reference's chain is within 35uM_i of the
-        // exact edge function (swr_binning.hip.h), so the fragment's float depth (two products, two sums) is within
+        // exact edge function (pair_may_cover, swr_device.h), so the fragment's float depth (two products, two sums) is within
         // 39.3uS of the exact affine depth; that is maximal at a corner of R; the corners evaluated in float below are
         // within 7.3uS; margin used: 64uS.  Those are relative errors; a product that underflows errs by up to 2^-150
         // absolutely instead, whatever its size.  That happens for huge triangles with small depths (d_k * invArea is
