@@ -70,6 +70,8 @@ def load(fma: bool = False, variant: str = None) -> C.CDLL:
     lib.oswr_interpolate.argtypes = [C.POINTER(OVertexOutput)] * 3 + [F, F, F, I, C.POINTER(OVertexOutput)]
     lib.oswr_lerp.restype = None
     lib.oswr_lerp.argtypes = [C.POINTER(OVertexOutput)] * 2 + [F, I, C.POINTER(OVertexOutput)]
+    lib.oswr_clip_triangle.restype = I
+    lib.oswr_clip_triangle.argtypes = [F, C.POINTER(OVertexOutput), C.POINTER(OVertexOutput)]
     lib.oswr_vertex_shader.restype = None
     lib.oswr_vertex_shader.argtypes = [P, P, P, P, I, C.POINTER(OVertexOutput)]
     lib.oswr_blend.restype = None; lib.oswr_blend.argtypes = [P, P, I, P]

@@ -744,6 +744,14 @@ static int clip_near(const oswr_context* c, const oswr_vertex_output in[3], oswr
     return n;
 }
 
+/* the clipper alone, for unit tests (tests/geometry_edge_scenes.py): only near_clip of a context is read */
+int oswr_clip_triangle(float near_clip, const oswr_vertex_output in[3], oswr_vertex_output out[4]) {
+    oswr_context c;
+    memset(&c, 0, sizeof(c));
+    c.near_clip = near_clip;
+    return clip_near(&c, in, out);
+}
+
 /* one triangle of RenderMesh's Parallel.For body, Rasterizer.cs:200-229 */
 static void process_triangle(draw_state* ds, const oswr_vertex_input* vertices, const uint16_t* indices, int i,
                              const float* model, const float* view, const float* proj) {

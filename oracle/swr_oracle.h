@@ -130,6 +130,8 @@ void  oswr_interpolate(const oswr_vertex_output* a, const oswr_vertex_output* b,
                        float w0, float w1, float w2, int interpolate, oswr_vertex_output* out);
 void  oswr_lerp(const oswr_vertex_output* a, const oswr_vertex_output* b, float t, int interpolate,
                 oswr_vertex_output* out);
+/* ClipTriangleAgainstNearPlane, Rasterizer.cs:95-160: the polygon (0..4 vertices) of one triangle; returns its vertex count */
+int   oswr_clip_triangle(float near_clip, const oswr_vertex_output in[3], oswr_vertex_output out[4]);
 void  oswr_texture_sample(const uint8_t* rgba8, int w, int h, const float uv[2], float out[4]);
 /* BUILD-DEFINED bilinear filter with wrap (no reference semantics: Texture.Sample is nearest) */
 void  oswr_texture_sample_bilinear(const uint8_t* rgba8, int w, int h, const float uv[2], float out[4]);

@@ -2,7 +2,8 @@
 """Extended parity sweep (test infrastructure, not part of the suite): random scenes of the four generator families at random
 sizes / states, HIP path against the oracle (depth bit-exact, colour <= 1 ULP, identical counters), for SECONDS of wall time.
 --edges adds the adversarial families of tests/edge_scenes.py (scenes at the binning / hi-Z / walk / guard bounds) and of
-tests/shade_edge_scenes.py (scenes at the guards of the speculate-and-verify shaders): a random family and seed every fifth round.
+tests/shade_edge_scenes.py (scenes at the guards of the speculate-and-verify shaders) and of tests/geometry_edge_scenes.py (scenes
+at the branches of the near clipper, the fan and the setup discards): a random family and seed every fifth round.
 usage: parity_sweep.py [--edges] [SECONDS=420] [RNG_SEED=7]"""
 import sys, time
 import os
@@ -15,8 +16,8 @@ from softwarerenderer_amd.rasterizer import DepthTest, Program, BlendMode, CullM
 EDGES = "--edges" in sys.argv
 if EDGES:
     sys.argv.remove("--edges")
-    import edge_scenes, shade_edge_scenes
-    EDGE_FAMILIES = {**edge_scenes.FAMILIES, **shade_edge_scenes.FAMILIES}
+    import edge_scenes, shade_edge_scenes, geometry_edge_scenes
+    EDGE_FAMILIES = {**edge_scenes.FAMILIES, **shade_edge_scenes.FAMILIES, **geometry_edge_scenes.FAMILIES}
 dev = Device(0)
 SECONDS = float(sys.argv[1]) if len(sys.argv) > 1 else 420.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
