@@ -14,8 +14,8 @@
 namespace swr {
 
 __device__ __forceinline__ float dist_sq3(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;     // Vector3.DistanceSquared
-    return (dx * dx + dy * dy) + dz * dz;
+    const float dx = ax - bx, dy = ay - by, dz = az - bz;     // Vector3.DistanceSquared / Distance (:78,101,128) = Dot(d, d):
+    return dot3(dx, dy, dz, dx, dy, dz);                      // sums in the order of SWR_DOT_PAIRWISE, like every Vector3.Dot
 }
 
 // block-wide max of a 64-bit key (1024 threads)
