@@ -11,6 +11,10 @@
 // exact signature and defaults, and the one shader pair the application uses (Renderer.VertexShader / FragmentShader,
 // Renderer.cs:830-860) is recognised and mapped to SWR_PROG_DUST2_LAMBERT_FOG with its closed-over fields as uniforms.
 //
+// Physics.Raycast (Physics.cs:19-52) gets an overload on a retained Mesh (PhysicsNative below): CharacterController.cs and
+// Renderer.Shoot can call it with `mesh` instead of `mesh.Vertices.ToArray(), mesh.Indices.ToArray()`, or batch a whole slide attempt
+// into one RaycastNearest (INTEGRATION.md).  Like the rest of this file it was written by reading the reference, not compiled.
+//
 // There is no .NET toolchain in the build image, so this file is NOT compiled there; tests/test_abi.py parses it and
 // checks it mechanically against include/swr.h and the ctypes binding (every entry point present with the right arity,
 // struct field order and sizes).  The compiled, tested callers of the same ABI are softwarerenderer_amd/rasterizer.py
@@ -83,9 +87,35 @@ namespace SoftwareRenderer
         public ulong Flushes;
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrRay                   // swr_ray, 24 bytes
+    {
+        public Vector3 Origin;
+        public Vector3 Direction;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrRayTarget             // swr_ray_target, 136 bytes
+    {
+        public IntPtr Mesh;
+        public Matrix4x4 Model;
+        public Matrix4x4 NormalMatrix;     // Matrix4x4.Transpose(invModel), Physics.cs:38
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrRayHit                // swr_ray_hit, 40 bytes
+    {
+        public int Found;
+        public int Target;
+        public int Triangle;
+        public float Distance;
+        public Vector3 Point;
+        public Vector3 Normal;
+    }
+
     public enum SwrProgram { FlatColor = 0, Gouraud = 1, Dust2LambertFog = 2, Phong4Point = 3, DebugVaryings = 4 }
 
-    // ---------------------------------------------------------------- the 63 entry points ----
+    // ---------------------------------------------------------------- the 65 entry points ----
     // Shaders.VertexInput (Shaders.cs:10-24) IS swr_vertex: four sequential System.Numerics fields, 48 bytes, blittable.
     // Matrix4x4 is 16 sequential floats M11..M44 (row-major, row-vector convention): passed by address, no marshalling.
     internal static unsafe class Native
@@ -157,6 +187,8 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_program_validate(byte* fragmentSource, byte* log, int logLen);
         [DllImport(Lib)] public static extern int swr_program_create_vf(IntPtr ctx, byte* vertexSource, byte* fragmentSource, out int programId);
         [DllImport(Lib)] public static extern int swr_program_validate_vf(byte* vertexSource, byte* fragmentSource, byte* log, int logLen);
+        [DllImport(Lib)] public static extern int swr_raycast(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
+        [DllImport(Lib)] public static extern int swr_raycast_nearest(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
     }
 
     // ---------------------------------------------------------------- numerics probe ----
@@ -181,6 +213,11 @@ namespace SoftwareRenderer
         static readonly uint[] DotZeroA = { 0x80000000u, 0x80000000u, 0x80000000u }, DotZeroB = { 0x3F800000u, 0x3F800000u, 0x3F800000u };
         const uint DotZeroSequential = 0x80000000u, DotZeroDpps = 0x00000000u;
         // </generated>
+
+        // Vector3.Cross (Physics.cs:153,170): x = a.Y * b.Z - a.Z * b.Y with two rounded products, or fma(-a.Z, b.Y, a.Y * b.Z) -- the
+        // operands were found by a seeded search (exact rational arithmetic); the flag goes into every raycast call (SWR_RAY_CROSS_FUSED)
+        static readonly uint[] CrossA = { 0xC07D4DDEu, 0x4024780Du, 0x4018197Cu }, CrossB = { 0xBE8356A4u, 0xBFC9B1DEu, 0xBFE2E465u };
+        const uint CrossUnfused = 0xBF4F7838u, CrossFused = 0xBF4F7839u;
 
         static volatile uint salt = 0;      // read at run time, so that the JIT cannot fold the probe expressions at compile time
         static float F(uint bits) => BitConverter.UInt32BitsToSingle(bits ^ salt);
@@ -209,6 +246,15 @@ namespace SoftwareRenderer
             else order = -1;
             if (order < 0) throw new NotSupportedException($"System.Numerics model not built: Dot -> 0x{dot:X8} / 0x{dz:X8} (see csharp/numerics_probe.json)");
             return (lerpFused, trFused, tnFused, order);
+        }
+
+        /// SWR_RAY_CROSS_FUSED (0x100) when the running Vector3.Cross fuses its second product, 0 when it rounds both, -1 when the
+        /// bits are neither model's (PhysicsNative then refuses to run: only ray queries depend on it).
+        [MethodImpl(MethodImplOptions.NoInlining)]
+        public static int ObserveCrossFlag()
+        {
+            uint cross = B(Vector3.Cross(new Vector3(F(CrossA[0]), F(CrossA[1]), F(CrossA[2])), new Vector3(F(CrossB[0]), F(CrossB[1]), F(CrossB[2]))).X);
+            return cross == CrossFused ? 0x100 : cross == CrossUnfused ? 0 : -1;
         }
 
         /// File name of the build that models the running System.Numerics' Lerp and Dot (six builds: every combination exists).
@@ -289,6 +335,22 @@ namespace SoftwareRenderer
             ~MeshHandle() { if (Ptr != IntPtr.Zero) Native.swr_mesh_destroy(SwrContext.Handle, Ptr); }
         }
 
+        /// The device copy of a ModelLoader mesh, uploaded on first use (draws and PhysicsNative's ray queries share it).
+        internal static unsafe IntPtr Retain(Mesh mesh)
+        {
+            IntPtr ctx = SwrContext.Handle;
+            return retained.GetValue(mesh, m =>
+            {
+                var va = m.Vertices.ToArray();
+                var ia = m.Indices.ToArray();
+                var mh = new MeshHandle();
+                fixed (Shaders.VertexInput* v = va)
+                fixed (ushort* idx = ia)
+                    SwrContext.Check(Native.swr_mesh_create(ctx, v, va.Length, idx, ia.Length, out mh.Ptr));
+                return mh;
+            }).Ptr;
+        }
+
         /// Rasterizer.RenderMesh with the reference's exact signature and defaults (Rasterizer.cs:163-174).
         public static unsafe void RenderMesh(
             MainWindow window,
@@ -344,21 +406,68 @@ namespace SoftwareRenderer
                 return;
             }
             IntPtr ctx = SwrContext.Handle;
-            MeshHandle h = retained.GetValue(mesh, m =>
-            {
-                var va = m.Vertices.ToArray();
-                var ia = m.Indices.ToArray();
-                var mh = new MeshHandle();
-                fixed (Shaders.VertexInput* v = va)
-                fixed (ushort* idx = ia)
-                    SwrContext.Check(Native.swr_mesh_create(ctx, v, va.Length, idx, ia.Length, out mh.Ptr));
-                return mh;
-            });
+            IntPtr h = Retain(mesh);
             SwrContext.Check(Native.swr_set_state(ctx, NearClip, FarClip, (int)RenderDebugMode));
             int rc = frustumCull
-                ? Native.swr_render_mesh_culled(ctx, h.Ptr, &model, &view, &projection, (int)program, &uniforms, texture, (int)cullMode, (int)depthTest, (int)blendMode)
-                : Native.swr_render_mesh(ctx, h.Ptr, &model, &view, &projection, (int)program, &uniforms, texture, (int)cullMode, (int)depthTest, (int)blendMode);
+                ? Native.swr_render_mesh_culled(ctx, h, &model, &view, &projection, (int)program, &uniforms, texture, (int)cullMode, (int)depthTest, (int)blendMode)
+                : Native.swr_render_mesh(ctx, h, &model, &view, &projection, (int)program, &uniforms, texture, (int)cullMode, (int)depthTest, (int)blendMode);
             SwrContext.Check(rc);
+        }
+    }
+
+    // ---------------------------------------------------------------- Physics ----
+    // Physics.Raycast on retained meshes (Physics.cs:19-179).  The reference copies the mesh, transforms every vertex and normal
+    // and walks every triangle PER CALL; here the mesh stays in HBM and a call carries rays and matrices only.  Matrix4x4.Invert stays
+    // on this side (its numerics are .NET's own): a model that does not invert is the reference's `return false`.
+    public static class PhysicsNative
+    {
+        static int crossFlag = -1;
+        static int CrossFlag
+        {
+            get
+            {
+                if (crossFlag < 0 && (crossFlag = NumericsProbe.ObserveCrossFlag()) < 0)
+                    throw new NotSupportedException("System.Numerics model not built: Vector3.Cross is neither of the two modelled forms (DESIGN.md section 3)");
+                return crossFlag;
+            }
+        }
+
+        /// Physics.Raycast(rayOrigin, rayDirection, mesh.Vertices.ToArray(), mesh.Indices.ToArray(), model, out ..., faceMask) without the copies.
+        public static unsafe bool Raycast(Vector3 rayOrigin, Vector3 rayDirection, Mesh mesh, Matrix4x4 model,
+                                          out float hitDistance, out Vector3 hitPoint, out Vector3 hitNormal,
+                                          RaycastFaceMask faceMask = RaycastFaceMask.IgnoreBackfaces)
+        {
+            hitDistance = float.MaxValue; hitPoint = Vector3.Zero; hitNormal = Vector3.Zero;
+            if (!Matrix4x4.Invert(model, out var invModel)) return false;                       // Physics.cs:30-36
+            var ray = new SwrRay { Origin = rayOrigin, Direction = rayDirection };
+            var target = new SwrRayTarget { Mesh = Rasterizer.Retain(mesh), Model = model, NormalMatrix = Matrix4x4.Transpose(invModel) };
+            SwrRayHit hit;
+            SwrContext.Check(Native.swr_raycast(SwrContext.Handle, &ray, 1, &target, 1, (int)faceMask | CrossFlag, &hit));
+            if (hit.Found == 0) return false;
+            hitDistance = hit.Distance; hitPoint = hit.Point; hitNormal = hit.Normal;
+            return true;
+        }
+
+        /// One call for a whole loop nest of the callers (CharacterController.MoveWithSlide, :308-389: every ray of a slide attempt
+        /// against every mesh of every collision model): hits[i] = the nearest hit of rays[i] over `targets` in their order under
+        /// `if (hit && distance < best)`; hits[i].Found == 0 where it misses everything.  Targets whose model does not invert are
+        /// left out by the caller (MakeTarget returns false).
+        public static unsafe void RaycastNearest(SwrRay[] rays, SwrRayTarget[] targets, SwrRayHit[] hits,
+                                                 RaycastFaceMask faceMask = RaycastFaceMask.IgnoreBackfaces)
+        {
+            if (hits.Length < rays.Length) throw new ArgumentException("hits is shorter than rays");
+            fixed (SwrRay* r = rays)
+            fixed (SwrRayTarget* t = targets)
+            fixed (SwrRayHit* h = hits)
+                SwrContext.Check(Native.swr_raycast_nearest(SwrContext.Handle, r, rays.Length, t, targets.Length, (int)faceMask | CrossFlag, h));
+        }
+
+        public static bool MakeTarget(Mesh mesh, Matrix4x4 model, out SwrRayTarget target)
+        {
+            target = default;
+            if (!Matrix4x4.Invert(model, out var invModel)) return false;
+            target = new SwrRayTarget { Mesh = Rasterizer.Retain(mesh), Model = model, NormalMatrix = Matrix4x4.Transpose(invModel) };
+            return true;
         }
     }
 

@@ -259,6 +259,35 @@ int  swr_render_mesh_culled(swr_context* ctx, const swr_mesh* mesh,
                             const float model[16], const float view[16], const float projection[16],
                             int program, const swr_uniforms* uniforms, const swr_texture* texture,
                             int cull_mode, int depth_test, int blend_mode);
+/* Physics.cs on the GPU: batched ray queries against retained meshes -------------------------------------------------------------
+ * Physics.RaycastFaceMask (Physics.cs:8-14) in the low bits of `flags`; SWR_RAY_CROSS_FUSED selects the other model of
+ * Vector3.Cross: default (a.y*b.z) - (a.z*b.y) with two rounded products, fused fma(-a.z, b.y, a.y*b.z) (one more System.Numerics
+ * switch nothing pins; csharp/RasterizerNative.cs probes it at start-up). */
+enum { SWR_RAY_FACES_ALL = 0, SWR_RAY_IGNORE_BACKFACES = 1, SWR_RAY_IGNORE_FRONTFACES = 2, SWR_RAY_CROSS_FUSED = 0x100 };
+typedef struct swr_ray { float origin[3]; float direction[3]; } swr_ray;                       /* 24 B; the direction need not be normalised (Physics.cs:69) */
+/* one mesh of a collision model: normal_matrix = Transpose(Invert(model)), computed by the CALLER with its own Matrix4x4.Invert
+ * (Physics.cs:30-38); a model that does not invert is the caller's `return false`: leave the target out */
+typedef struct swr_ray_target { const swr_mesh* mesh; float model[16]; float normal_matrix[16]; } swr_ray_target;   /* 136 B */
+/* a hit: found = 1, distance, point, normal as Physics.Raycast's out parameters; a miss: found = 0, distance = float.MaxValue, point and
+ * normal zero, triangle = -1 (Physics.cs:65-67).  target = index into `targets`; triangle = the winning triangle (build-defined) */
+typedef struct swr_ray_hit { int32_t found, target, triangle; float distance, point[3], normal[3]; } swr_ray_hit;   /* 40 B */
+/* Physics.Raycast(origin, direction, mesh.Vertices, mesh.Indices, model, out d, out p, out n, mask) (Physics.cs:19-179) for every
+ * (ray, target) pair in the reference's serial schedule: the nearest hit under float `<` among distances below float.MaxValue, the
+ * lowest triangle index on ties (-0.0 and +0.0 tie; the winner's own word is returned), bit for bit under this library's
+ * System.Numerics model and the context's Transform flag (swr_set_transform_fma).  out[ray * n_targets + target].
+ * Reads retained mesh data only: recorded draws are neither flushed nor waited for, and the query runs on a stream of its own, so
+ * it does not queue behind a frame in flight.  n_rays == 0 or n_targets == 0: SWR_OK, nothing written.  NULL pointers, negative
+ * counts, a NULL mesh, unknown flag bits: SWR_ERR_INVALID_ARG.  LIMITS: n_rays <= 2^20, n_targets <= 65535, n_rays * n_targets <= 2^24
+ * pairs per call, beyond which SWR_ERR_UNSUPPORTED (split the rays).  A mesh without triangles misses. */
+int  swr_raycast(swr_context* ctx, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets,
+                 int flags, swr_ray_hit* out /* n_rays * n_targets, ray-major */);
+/* the same, reduced over the targets on the device in target order under `if (hit && distance < best)` starting from "not found" -- the
+ * serial schedule of the callers' lock blocks (CharacterController.cs:260-301,308-389, Renderer.cs:172-216): the first of equally near
+ * targets wins; a ray that misses every target gives the miss record with target = -1.  Only n_rays records cross PCIe.  A caller's
+ * own distance limit (maxDistance, moveDistance) stays on the caller's side. */
+int  swr_raycast_nearest(swr_context* ctx, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets,
+                         int flags, swr_ray_hit* out /* n_rays */);
+
 /* User fragment programs --------------------------------------------------------------------------------------------------------
  * Source contract (softwarerenderer_amd/csrc/swr_program.hip.h is the prelude compiled in front of the text; INTEGRATION.md has a
  * porting guide): the text defines

@@ -63,6 +63,21 @@ class Profile(C.Structure):
                [("raster_launches", C.c_uint64), ("flushes", C.c_uint64)]
 
 
+class Ray(C.Structure):  # swr_ray (24 bytes): Physics.Raycast's rayOrigin, rayDirection
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3)]
+
+
+class RayTarget(C.Structure):  # swr_ray_target (136 bytes): a retained mesh, its model matrix and Transpose(Invert(model))
+    _fields_ = [("mesh", C.c_void_p), ("model", C.c_float * 16), ("normal_matrix", C.c_float * 16)]
+
+
+class RayHit(C.Structure):  # swr_ray_hit (40 bytes)
+    _fields_ = [("found", C.c_int32), ("target", C.c_int32), ("triangle", C.c_int32), ("distance", C.c_float),
+                ("point", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+SWR_RAY_FACES_ALL, SWR_RAY_IGNORE_BACKFACES, SWR_RAY_IGNORE_FRONTFACES, SWR_RAY_CROSS_FUSED = 0, 1, 2, 0x100
+
 # every symbol include/swr.h declares; tests/test_abi.py checks the library exports all of them
 EXPORTS = [
     "swr_abi_version", "swr_build_info", "swr_numerics_mode", "swr_set_transform_fma", "swr_get_transform_fma", "swr_set_pipelining", "swr_get_pipelining", "swr_last_error", "swr_create", "swr_destroy", "swr_resize", "swr_set_band", "swr_set_band_interleaved",
@@ -74,6 +89,7 @@ EXPORTS = [
     "swr_profile_enable", "swr_profile_get", "swr_profile_reset", "swr_profile_raster_samples", "swr_device_name", "swr_debug_counters", "swr_selftest_division",
     "swr_program_create", "swr_program_destroy", "swr_program_set_constants", "swr_program_validate",
     "swr_program_create_vf", "swr_program_validate_vf",
+    "swr_raycast", "swr_raycast_nearest",
 ]
 
 _libs = {}
@@ -159,6 +175,8 @@ def load(name: str = None) -> C.CDLL:
         "swr_program_validate": (I, [C.c_char_p, C.c_char_p, I]),
         "swr_program_create_vf": (I, [P, C.c_char_p, C.c_char_p, C.POINTER(I)]),
         "swr_program_validate_vf": (I, [C.c_char_p, C.c_char_p, C.c_char_p, I]),
+        "swr_raycast": (I, [P, P, I, P, I, I, P]),
+        "swr_raycast_nearest": (I, [P, P, I, P, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -40,6 +40,7 @@
 #include "swr_raster.hip.h"
 #include "swr_raster_c.hip.h"
 #include "swr_cull.hip.h"
+#include "swr_raycast.hip.h"
 
 using namespace swr;
 
@@ -91,6 +92,78 @@ int pixel_transfer(swr_context* c, int x, int y, void* plane, size_t bytes, void
     if (to_host) SWR_HIP(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     else SWR_HIP(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
     return sync_locked(c);
+}
+
+// swr_raycast / swr_raycast_nearest.  Everything runs on the context's ray stream, which is idle between calls (the call waits for
+// its own result under the context mutex): rays and targets go up in one copy, k_ray_cast and k_ray_finish run, the records come
+// back in one copy.  No allocation in the steady state (hipMalloc / hipFree would wait for the frame in flight).
+int raycast(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets, int flags, swr_ray_hit* out, bool nearest) {
+    if (n_rays < 0 || n_targets < 0) return fail(c, SWR_ERR_INVALID_ARG, "negative ray or target count");
+    if (flags & ~(SWR_RAY_IGNORE_BACKFACES | SWR_RAY_IGNORE_FRONTFACES | SWR_RAY_CROSS_FUSED)) return fail(c, SWR_ERR_INVALID_ARG, "unknown raycast flag bits");
+    if (n_rays == 0 || n_targets == 0) return SWR_OK;
+    if (!rays || !targets || !out) return fail(c, SWR_ERR_INVALID_ARG, "null argument to raycast");
+    if (n_rays > (1 << 20) || n_targets > 65535 || (uint64_t)n_rays * (uint64_t)n_targets > (1ull << 24))
+        return fail(c, SWR_ERR_UNSUPPORTED, "raycast: at most 2^20 rays, 65535 targets and 2^24 (ray, target) pairs per call: split the rays");
+    for (int t = 0; t < n_targets; ++t) if (!targets[t].mesh) return fail(c, SWR_ERR_INVALID_ARG, "raycast target without a mesh");
+    if (!c->ray_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->ray_stream, hipStreamNonBlocking));
+    const size_t pairs = (size_t)n_rays * (size_t)n_targets, n_out = nearest ? (size_t)n_rays : pairs;
+    const size_t off_t = ((size_t)n_rays * sizeof(swr_ray) + 15) & ~(size_t)15;
+    const size_t up_bytes = off_t + (((size_t)n_targets * sizeof(RayTarget) + 15) & ~(size_t)15), down_bytes = n_out * sizeof(swr_ray_hit);
+    int rc = ensure(c, c->d_ray, up_bytes + down_bytes); if (rc) return rc;
+    if (c->d_ray_best.cap < pairs * 8) {
+        if ((rc = ensure(c, c->d_ray_best, pairs * 8))) return rc;
+        SWR_HIP(c, hipMemsetAsync(c->d_ray_best.p, 0xff, c->d_ray_best.cap, c->ray_stream));      // from here on k_ray_finish keeps it clean
+    }
+    // small queries (a slide attempt: 111 rays x 11 meshes, 4.4 KB each way) go through one pinned block; large ones use the caller's memory
+    const bool staged = up_bytes + down_bytes <= ((size_t)1 << 20);
+    if (staged && c->ray_host_cap < up_bytes + down_bytes) {
+        if (c->ray_host) (void)hipHostFree(c->ray_host);
+        c->ray_host = nullptr; c->ray_host_cap = 0;
+        const size_t cap = std::max<size_t>(up_bytes + down_bytes, (size_t)1 << 16);
+        SWR_HIP(c, hipHostMalloc(&c->ray_host, cap, hipHostMallocDefault));
+        c->ray_host_cap = cap;
+    }
+    std::vector<char> pageable;
+    if (!staged) pageable.resize(up_bytes);
+    char* up = staged ? static_cast<char*>(c->ray_host) : pageable.data();
+    memcpy(up, rays, (size_t)n_rays * sizeof(swr_ray));
+    RayTarget* ht = reinterpret_cast<RayTarget*>(up + off_t);
+    uint32_t max_tris = 0;
+    for (int t = 0; t < n_targets; ++t) {
+        swr_mesh* m = const_cast<swr_mesh*>(targets[t].mesh);
+        if (m->uploaded && !m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
+        ht[t].verts = m->d_verts; ht[t].idx = m->d_idx; ht[t].n_tris = (uint32_t)(m->n_idx / 3); ht[t].pad = 0u;
+        memcpy(ht[t].model, targets[t].model, 64); memcpy(ht[t].normal_matrix, targets[t].normal_matrix, 64);
+        max_tris = std::max(max_tris, ht[t].n_tris);
+    }
+    char* base = static_cast<char*>(c->d_ray.p);
+    const swr_ray* d_rays = reinterpret_cast<const swr_ray*>(base);
+    const RayTarget* d_targets = reinterpret_cast<const RayTarget*>(base + off_t);
+    swr_ray_hit* d_out = reinterpret_cast<swr_ray_hit*>(base + up_bytes);
+    unsigned long long* d_best = c->d_ray_best.as<unsigned long long>();
+    const uint32_t mask = (uint32_t)flags & 3u, nr = (uint32_t)n_rays, nt = (uint32_t)n_targets;
+    const bool fused = (flags & SWR_RAY_CROSS_FUSED) != 0;
+    SWR_HIP(c, hipMemcpyAsync(base, up, up_bytes, hipMemcpyHostToDevice, c->ray_stream));
+    if (max_tris) {
+        const dim3 grid((max_tris + SWR_RAY_BLOCK - 1) / SWR_RAY_BLOCK, (nr + SWR_RAY_CHUNK - 1) / SWR_RAY_CHUNK, nt);
+        if (fused) hipLaunchKernelGGL(k_ray_cast<true>, grid, dim3(SWR_RAY_BLOCK), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best);
+        else hipLaunchKernelGGL(k_ray_cast<false>, grid, dim3(SWR_RAY_BLOCK), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best);
+        SWR_HIP(c, hipGetLastError());
+    }
+    const dim3 fgrid((unsigned)((n_out + 63) / 64));
+    if (nearest) {
+        if (fused) hipLaunchKernelGGL((k_ray_finish<true, true>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
+        else hipLaunchKernelGGL((k_ray_finish<false, true>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
+    } else {
+        if (fused) hipLaunchKernelGGL((k_ray_finish<true, false>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
+        else hipLaunchKernelGGL((k_ray_finish<false, false>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
+    }
+    SWR_HIP(c, hipGetLastError());
+    void* down = staged ? static_cast<void*>(static_cast<char*>(c->ray_host) + up_bytes) : static_cast<void*>(out);
+    SWR_HIP(c, hipMemcpyAsync(down, d_out, down_bytes, hipMemcpyDeviceToHost, c->ray_stream));
+    SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
+    if (staged) memcpy(out, down, down_bytes);
+    return SWR_OK;
 }
 }  // namespace
 
@@ -195,13 +268,15 @@ void swr_destroy(swr_context* c) {
     for (auto& fs : c->slots) { if (fs.host) (void)hipHostFree(fs.host); if (fs.done) (void)hipEventDestroy(fs.done); }
     if (c->host_poison) (void)hipHostFree(c->host_poison);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
+    if (c->ray_stream) { (void)hipStreamSynchronize(c->ray_stream); (void)hipStreamDestroy(c->ray_stream); }
+    if (c->ray_host) (void)hipHostFree(c->ray_host);
     for (int i = 0; i < 2; ++i) {
         if (c->present_flat[i]) (void)hipEventDestroy(c->present_flat[i]);
         if (c->present_done[i]) (void)hipEventDestroy(c->present_done[i]);
         release(c->present_buf[i]);
     }
     DevBuf* bufs[] = { &c->own_color, &c->own_depth, &c->d_slot_tb, &c->d_want, &c->d_ctrl, &c->d_pair_tile, &c->d_tile_list, &c->d_tile_stats,
-                       &c->d_counters, &c->d_total, &c->d_scratch };
+                       &c->d_counters, &c->d_total, &c->d_scratch, &c->d_ray, &c->d_ray_best };
     for (DevBuf* b : bufs) release(*b);
     for (auto& s : c->sets) {
         DevBuf* sb[] = { &s.d_upload, &s.d_vout, &s.d_vnorm, &s.d_recs, &s.d_masks, &s.d_pcounts, &s.d_pair_refs, &s.d_tile_count, &s.d_tile_start, &s.d_order };
@@ -547,6 +622,13 @@ int swr_mesh_bounds(swr_context* c, const swr_mesh* mesh, float center_radius[4]
     SWR_HIP(c, hipMemcpyAsync(center_radius, mesh->d_bounds, 16, hipMemcpyDeviceToHost, use_front_stream(c)));
     SWR_HIP(c, hipStreamSynchronize(use_front_stream(c)));
     return SWR_OK;
+}
+
+int swr_raycast(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets, int flags, swr_ray_hit* out) {
+    SWR_ENTER(c); return raycast(c, rays, n_rays, targets, n_targets, flags, out, false);
+}
+int swr_raycast_nearest(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets, int flags, swr_ray_hit* out) {
+    SWR_ENTER(c); return raycast(c, rays, n_rays, targets, n_targets, flags, out, true);
 }
 
 int swr_is_sphere_in_frustum(swr_context* c, const float center_radius[4], const float model[16], const float view[16],

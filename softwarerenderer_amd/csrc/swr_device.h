@@ -427,6 +427,19 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
     return (ax * bx + ay * by) + az * bz;
 #endif
 }
+// Vector3.Cross(a, b) (Physics.cs:153,170): FUSED = false, two rounded products per component, (a.y*b.z) - (a.z*b.y); FUSED = true,
+// fma(-a.z, b.y, round(a.y*b.z)) -- one more unpinned System.Numerics switch, chosen per call by
+// SWR_RAY_CROSS_FUSED (include/swr.h).  The fma is spelled out: it is the model, not a contraction.
+template <bool FUSED>
+__device__ __forceinline__ void cross3(const float a[3], const float b[3], float out[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = (k + 1) % 3, j = (k + 2) % 3;           // x: (y, z)   y: (z, x)   z: (x, y)
+        const float p = a[i] * b[j];
+        if (FUSED) out[k] = __builtin_fmaf(-a[j], b[i], p);
+        else { const float q = a[j] * b[i]; out[k] = p - q; }
+    }
+}
 __device__ __forceinline__ float nm_lerp(float a, float b, float t) {   // a*(1-t) + b*t
 #if SWR_NUMERICS_FMA
     return __builtin_fmaf(a, 1.0f - t, b * t);

@@ -11,6 +11,7 @@ void destroy_mesh(swr_mesh* m) {
     if (m->d_verts) (void)hipFree(m->d_verts);
     if (m->d_idx) (void)hipFree(m->d_idx);
     if (m->d_bounds) (void)hipFree(m->d_bounds);
+    if (m->uploaded) (void)hipEventDestroy(m->uploaded);
     delete m;
 }
 // A transient mesh (swr_render_mesh_arrays: the reference's RenderMesh(vertices, indices, ...) makes one per call) whose batch is
@@ -799,6 +800,9 @@ int make_mesh(swr_context* c, const swr_vertex* v, int nv, const uint16_t* idx, 
     // (only front-end kernels read a mesh: the upload goes to their stream, so a pipelined frame does not wait for the raster stream)
     if (e == hipSuccess && nv) e = hipMemcpyAsync(m->d_verts, v, (size_t)nv * sizeof(swr_vertex), hipMemcpyHostToDevice, use_front_stream(c));
     if (e == hipSuccess && ni) e = hipMemcpyAsync(m->d_idx, idx, (size_t)ni * 2, hipMemcpyHostToDevice, use_front_stream(c));
+    // (a retained mesh may be read from the ray stream: an event behind its upload orders that reader without a wait on this stream)
+    if (e == hipSuccess && !transient) e = hipEventCreateWithFlags(&m->uploaded, hipEventDisableTiming);
+    if (e == hipSuccess && !transient) e = hipEventRecord(m->uploaded, use_front_stream(c));
     if (e != hipSuccess) {
         destroy_mesh(m);
         c->err = std::string("mesh upload failed: ") + hipGetErrorString(e);

@@ -12,6 +12,8 @@ struct swr_mesh {
     bool transient = false;
     float box_lo[3] = { 0, 0, 0 }, box_hi[3] = { 0, 0, 0 };   // exact model-space AABB of the vertices (host, at creation)
     bool has_box = false;
+    hipEvent_t uploaded = nullptr;            // retained meshes: recorded behind the upload, for readers on another stream (swr_raycast)
+    bool upload_seen = false;                 // ... the ray stream has been ordered behind it
 };
 struct swr_texture {
     uint8_t* d_rgba = nullptr;
@@ -162,6 +164,11 @@ struct swr_context {
     uint64_t present_ticket[2] = { 0, 0 };    // ticket whose copy the slot carries (0 = none pending)
     uint32_t present_seq[2] = { 0, 0 };       // last batch flushed before that present: retired when the copy is known to be over
     uint64_t next_ticket = 0;
+
+    // swr_raycast / swr_raycast_nearest: a stream of their own (a query does not queue behind a frame in flight), idle between calls
+    hipStream_t ray_stream = nullptr;
+    DevBuf d_ray, d_ray_best;                  // rays | targets | hit records; the pairs' keys, all SWR_RAY_NO_HIT between calls (k_ray_finish)
+    void* ray_host = nullptr; size_t ray_host_cap = 0;     // pinned staging block of small queries
 
     int profiling = 0;                         // 0 off, 1 every stage, 2 only the raster kernel (2 events per flush)
     std::vector<EventSpan> spans;

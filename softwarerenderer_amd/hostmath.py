@@ -70,3 +70,26 @@ def create_look_at(eye, target, up) -> np.ndarray:
 
 def multiply(a, b) -> np.ndarray:
     return (np.asarray(a, dtype=F) @ np.asarray(b, dtype=F)).astype(F)
+
+
+def invert(m):
+    """Matrix4x4.Invert for the normal matrix of Physics.Raycast (Physics.cs:30-38): the inverse, or None where the reference's
+    `if (!Matrix4x4.Invert(...)) return false` applies.  BUILD-DEFINED: the inverse is computed in float64 and rounded to float32,
+    and None is returned when the float64 determinant is 0 or not finite; the numerics of .NET's own Invert are pinned by nothing,
+    which is why swr_ray_target takes the caller's matrix."""
+    a = np.asarray(m, dtype=F).reshape(4, 4).astype(np.float64)
+    with np.errstate(all="ignore"):
+        det = np.linalg.det(a)
+        if det == 0.0 or not np.isfinite(det):
+            return None
+        try:
+            inv = np.linalg.inv(a)
+        except np.linalg.LinAlgError:
+            return None
+    return inv.astype(F)
+
+
+def normal_matrix(model):
+    """Transpose(Invert(model)) as Physics.Raycast forms it (Physics.cs:38), or None where the model does not invert."""
+    inv = invert(model)
+    return None if inv is None else np.ascontiguousarray(inv.T)

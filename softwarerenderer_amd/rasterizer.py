@@ -579,6 +579,95 @@ class FrustumCuller:
         return bool(out.value)
 
 
+class RaycastFaceMask(enum.IntFlag):      # Physics.cs:8-14
+    None_ = 0
+    IgnoreBackfaces = 1
+    IgnoreFrontfaces = 2
+
+
+# numpy views of swr_ray (24 B) and swr_ray_hit (40 B)
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3)])
+RAY_HIT_DTYPE = np.dtype([("found", "<i4"), ("target", "<i4"), ("triangle", "<i4"), ("distance", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3)])
+assert RAY_DTYPE.itemsize == 24 == C.sizeof(N.Ray) and RAY_HIT_DTYPE.itemsize == 40 == C.sizeof(N.RayHit)
+
+
+class Physics:
+    """public static class Physics (Physics.cs:16) over retained meshes: every ray-triangle test runs on the GPU."""
+
+    @staticmethod
+    def _rays(origins, directions) -> np.ndarray:
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions must have the same shape (n, 3)")
+        rays = np.empty(o.shape[0], dtype=RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        return rays
+
+    @staticmethod
+    def _targets(targets):
+        """targets = [(Mesh, model)] or [(Mesh, model, normal_matrix)]; without a normal matrix it is hostmath.normal_matrix(model),
+        and a model that does not invert leaves the target out (Physics.cs:30-36).  Returns (ctypes array, kept indices, device)."""
+        from . import hostmath
+        rows, kept, dev = [], [], None
+        for k, t in enumerate(targets):
+            mesh, model = t[0], _f32(t[1], 16)
+            nm = t[2] if len(t) > 2 and t[2] is not None else hostmath.normal_matrix(model)
+            if nm is None:
+                continue
+            if dev is not None and mesh._dev is not dev:
+                raise ValueError("the meshes of one query must live on one Device")
+            dev = mesh._dev
+            rows.append((mesh, model, _f32(nm, 16))); kept.append(k)
+        arr = (N.RayTarget * max(len(rows), 1))()
+        for a, (mesh, model, nm) in zip(arr, rows):
+            a.mesh = mesh._h.value
+            a.model[:] = model.tolist()
+            a.normal_matrix[:] = nm.tolist()
+        return arr, kept, dev
+
+    @staticmethod
+    def _query(fn_name, rays, targets, faceMask, crossFused, per_pair):
+        arr, kept, dev = Physics._targets(targets)
+        n_out = rays.shape[0] * (len(kept) if per_pair else 1)
+        out = np.zeros(n_out, dtype=RAY_HIT_DTYPE)
+        if per_pair or not kept:
+            out["target"] = np.tile(np.asarray(kept, dtype=np.int32), rays.shape[0]) if per_pair else -1
+            out["triangle"], out["distance"] = -1, np.finfo(np.float32).max
+        if kept and rays.shape[0]:
+            flags = int(faceMask) | (N.SWR_RAY_CROSS_FUSED if crossFused else 0)
+            dev._ck(getattr(dev._lib, fn_name)(dev._ctx, rays.ctypes.data, int(rays.shape[0]), C.addressof(arr), len(kept), flags, out.ctypes.data))
+            tgt = out["target"]
+            out["target"] = np.where(tgt >= 0, np.asarray(kept, dtype=np.int32)[np.maximum(tgt, 0)], tgt)    # index into the CALLER's list
+        return out, kept
+
+    @staticmethod
+    def Raycast(rayOrigin, rayDirection, mesh: "Mesh", model, faceMask=RaycastFaceMask.IgnoreBackfaces, crossFused: bool = False):
+        """Physics.Raycast (Physics.cs:19-52) against a retained mesh: (hit, hitDistance, hitPoint, hitNormal); a model that does not
+        invert gives the reference's (False, float.MaxValue, zero, zero)."""
+        out, _ = Physics._query("swr_raycast", Physics._rays(rayOrigin, rayDirection), [(mesh, model)], faceMask, crossFused, True)
+        if out.shape[0] == 0:
+            return False, float(np.finfo(np.float32).max), np.zeros(3, dtype=np.float32), np.zeros(3, dtype=np.float32)
+        h = out[0]
+        return bool(h["found"]), float(h["distance"]), h["point"].copy(), h["normal"].copy()
+
+    @staticmethod
+    def RaycastBatch(origins, directions, targets, faceMask=RaycastFaceMask.IgnoreBackfaces, crossFused: bool = False) -> np.ndarray:
+        """swr_raycast: Physics.Raycast for every (ray, target) pair; targets = [(Mesh, model[, normal_matrix])].  Returns a
+        (n_rays, n_kept) array of RAY_HIT_DTYPE whose `target` is the index into `targets` (targets whose model does not invert are
+        left out, as the reference returns false for them)."""
+        rays = Physics._rays(origins, directions)
+        out, kept = Physics._query("swr_raycast", rays, targets, faceMask, crossFused, True)
+        return out.reshape(rays.shape[0], len(kept))
+
+    @staticmethod
+    def RaycastNearest(origins, directions, targets, faceMask=RaycastFaceMask.IgnoreBackfaces, crossFused: bool = False) -> np.ndarray:
+        """swr_raycast_nearest: per ray, the nearest hit over the targets in target order under strict `<` (the callers' lock blocks,
+        CharacterController.cs:260-301,308-389); (n_rays,) of RAY_HIT_DTYPE, target = -1 where a ray misses everything."""
+        rays = Physics._rays(origins, directions)
+        return Physics._query("swr_raycast_nearest", rays, targets, faceMask, crossFused, False)[0]
+
+
 def as_vertex_array(vertices) -> np.ndarray:
     v = np.asarray(vertices)
     if v.dtype == VERTEX_DTYPE:
