@@ -113,6 +113,54 @@ namespace SoftwareRenderer
         public Vector3 Normal;
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrCharacterParams       // swr_character_params, 52 bytes: the properties of CharacterController.cs:21-32
+    {
+        public Vector3 Gravity;
+        public float Height;
+        public float Radius;
+        public float StepSize;
+        public float MoveSpeed;
+        public float JumpForce;
+        public float GroundAcceleration;
+        public float AirAcceleration;
+        public float MaxAirSpeed;
+        public float GroundFriction;
+        public float AirControl;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrCharacter             // swr_character, 44 bytes: one controller's state, in and out
+    {
+        public Vector3 Position;
+        public Vector3 Velocity;
+        public float JumpCooldown;
+        public float ActualStepSize;       // the private field of CharacterController.cs:25: 0.03f in a new controller
+        public int Grounded;
+        public int Ceiling;
+        public int NoClip;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrCharacterInput        // swr_character_input, 16 bytes
+    {
+        public Vector3 Move;
+        public int Jump;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrCharacterTrace        // swr_character_trace, 48 bytes
+    {
+        public int GroundFound;
+        public int CeilingFound;
+        public Vector3 GroundPoint;
+        public Vector3 GroundNormal;
+        public int Chain1Attempts;
+        public int Chain2Attempts;
+        public int Chain1Stop;             // 0 not run, 1 no collision, 2 |alignment| > 0.9, 3 zero slide direction, 4 depth limit
+        public int Chain2Stop;
+    }
+
     public enum SwrProgram { FlatColor = 0, Gouraud = 1, Dust2LambertFog = 2, Phong4Point = 3, DebugVaryings = 4 }
 
     // ---------------------------------------------------------------- the 65 entry points ----
@@ -189,6 +237,8 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_program_validate_vf(byte* vertexSource, byte* fragmentSource, byte* log, int logLen);
         [DllImport(Lib)] public static extern int swr_raycast(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
         [DllImport(Lib)] public static extern int swr_raycast_nearest(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
+        [DllImport(Lib)] public static extern int swr_character_ray_counts(SwrCharacterParams* p, out int verticalSteps, out int horizontalRays);
+        [DllImport(Lib)] public static extern int swr_character_update(IntPtr ctx, SwrCharacterParams* p, SwrCharacter* chars, SwrCharacterInput* inputs, int n, float deltaTime, float* ring, int nRing, SwrRayTarget* targets, int nTargets, int flags, SwrCharacterTrace* trace);
     }
 
     // ---------------------------------------------------------------- numerics probe ----
@@ -431,6 +481,7 @@ namespace SoftwareRenderer
                 return crossFlag;
             }
         }
+        internal static int CrossFlagValue => CrossFlag;
 
         /// Physics.Raycast(rayOrigin, rayDirection, mesh.Vertices.ToArray(), mesh.Indices.ToArray(), model, out ..., faceMask) without the copies.
         public static unsafe bool Raycast(Vector3 rayOrigin, Vector3 rayDirection, Mesh mesh, Matrix4x4 model,
@@ -468,6 +519,89 @@ namespace SoftwareRenderer
             if (!Matrix4x4.Invert(model, out var invModel)) return false;
             target = new SwrRayTarget { Mesh = Rasterizer.Retain(mesh), Model = model, NormalMatrix = Matrix4x4.Transpose(invModel) };
             return true;
+        }
+    }
+
+    // ---------------------------------------------------------------- CharacterController ----
+    // CharacterController.Update (CharacterController.cs:50-140) in ONE native call: both CheckPlanes, both MoveWithSlide chains and
+    // the velocity update run on the GPU without a host round trip between them.  What stays on this side: the ring table
+    // (MathF.Cos / MathF.Sin are the C runtime's), Matrix4x4.Invert (a model that does not invert is left out), the flattening of
+    // collisionModels, and CamOffset, which only the camera reads.  Properties and defaults are the reference's.
+    public class CharacterControllerNative
+    {
+        public Vector3 Position { get; set; }
+        public Vector3 Velocity { get; private set; }
+        public bool IsGrounded { get; private set; }
+        public bool IsCeiling { get; private set; }
+        public bool IsNoClipEnabled { get; set; } = false;
+
+        public Vector3 Gravity { get; set; } = new(0, -14.0f, 0);
+        public float Height { get; set; } = 0.5f;
+        public float Radius { get; set; } = 0.15f;
+        public float StepSize { get; set; } = 0.3f;
+        private float ActualStepSize = 0.03f;
+        public float MoveSpeed { get; set; } = 5.0f;
+        public float JumpForce { get; set; } = 4f;
+        public float GroundAcceleration { get; set; } = 3.5f;
+        public float AirAcceleration { get; set; } = 0.35f;
+        public float MaxAirSpeed { get; set; } = 6.0f;
+        public float GroundFriction { get; set; } = 6.0f;
+        public float AirControl { get; set; } = 0.2f;
+        public Vector3 CamOffset { get; set; } = new(0.0f, 0.15f, 0.0f);
+        public SwrCharacterTrace LastTrace;
+
+        private float JumpCooldownTimer = 0f;
+        private readonly SwrRayTarget[] targets;       // collisionModels[i] flattened, model-major, mesh-minor
+        private float[] ring = Array.Empty<float>();
+        private float ringRadius = float.NaN, ringHeight = float.NaN;
+
+        public CharacterControllerNative(Vector3 initialPosition, List<Mesh>[] collisionModels, Matrix4x4[] modelMatrices)
+        {
+            Position = initialPosition;
+            Velocity = Vector3.Zero;
+            var flat = new List<SwrRayTarget>();
+            if (collisionModels != null && modelMatrices != null && collisionModels.Length == modelMatrices.Length)     // :233, :314
+                for (int i = 0; i < collisionModels.Length; i++)
+                    foreach (var mesh in collisionModels[i])
+                        if (PhysicsNative.MakeTarget(mesh, modelMatrices[i], out var t)) flat.Add(t);
+            targets = flat.ToArray();
+        }
+
+        SwrCharacterParams Params() => new SwrCharacterParams {
+            Gravity = Gravity, Height = Height, Radius = Radius, StepSize = StepSize, MoveSpeed = MoveSpeed, JumpForce = JumpForce,
+            GroundAcceleration = GroundAcceleration, AirAcceleration = AirAcceleration, MaxAirSpeed = MaxAirSpeed,
+            GroundFriction = GroundFriction, AirControl = AirControl };
+
+        // (cos, sin) of `2 * MathF.PI * hStep / horizontalRays` (:348) with THIS runtime's MathF, once per change of the radius
+        unsafe void EnsureRing(SwrCharacterParams p)
+        {
+            if (Radius == ringRadius && Height == ringHeight) return;
+            SwrContext.Check(Native.swr_character_ray_counts(&p, out _, out int horizontalRays));
+            ring = new float[2 * horizontalRays];
+            for (int hStep = 0; hStep < horizontalRays; hStep++)
+            {
+                float angle = 2 * MathF.PI * hStep / horizontalRays;
+                ring[2 * hStep] = MathF.Cos(angle);
+                ring[2 * hStep + 1] = MathF.Sin(angle);
+            }
+            ringRadius = Radius; ringHeight = Height;
+        }
+
+        public unsafe void Update(float DeltaTime, Vector3 MoveInput, bool JumpRequested)
+        {
+            var p = Params();
+            EnsureRing(p);
+            var c = new SwrCharacter { Position = Position, Velocity = Velocity, JumpCooldown = JumpCooldownTimer, ActualStepSize = ActualStepSize,
+                                       Grounded = IsGrounded ? 1 : 0, Ceiling = IsCeiling ? 1 : 0, NoClip = IsNoClipEnabled ? 1 : 0 };
+            var input = new SwrCharacterInput { Move = MoveInput, Jump = JumpRequested ? 1 : 0 };
+            SwrCharacterTrace trace;
+            fixed (float* r = ring)
+            fixed (SwrRayTarget* t = targets)
+                SwrContext.Check(Native.swr_character_update(SwrContext.Handle, &p, &c, &input, 1, DeltaTime, r, ring.Length / 2, t, targets.Length,
+                                                             PhysicsNative.CrossFlagValue, &trace));
+            Position = c.Position; Velocity = c.Velocity; JumpCooldownTimer = c.JumpCooldown; ActualStepSize = c.ActualStepSize;
+            IsGrounded = c.Grounded != 0; IsCeiling = c.Ceiling != 0;
+            LastTrace = trace;
         }
     }
 

@@ -288,6 +288,48 @@ int  swr_raycast(swr_context* ctx, const swr_ray* rays, int n_rays, const swr_ra
 int  swr_raycast_nearest(swr_context* ctx, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets,
                          int flags, swr_ray_hit* out /* n_rays */);
 
+/* CharacterController.Update on the GPU (CharacterController.cs:50-140): one call per step for a batch of controllers ------------
+ * The properties of CharacterController.cs:21-32 shared by the call (CamOffset stays with the caller). */
+typedef struct swr_character_params {
+    float gravity[3], height, radius, step_size, move_speed, jump_force, ground_acceleration, air_acceleration, max_air_speed,
+          ground_friction, air_control;
+} swr_character_params;                                                                        /* 52 B */
+/* one controller, in and out.  actual_step_size is the private field of CharacterController.cs:25 and is STATE: 0.03f in a new
+ * controller, then StepSize or 0 as the previous step left it.  jump_cooldown is JumpCooldownTimer (:47). */
+typedef struct swr_character {
+    float position[3], velocity[3], jump_cooldown, actual_step_size;
+    int32_t grounded, ceiling, noclip;
+} swr_character;                                                                               /* 44 B */
+typedef struct swr_character_input { float move[3]; int32_t jump; } swr_character_input;        /* 16 B: MoveInput, JumpRequested */
+/* what a step decided, for tests and debugging: the ground CheckPlane's results (point = Vector3.NegativeInfinity, normal = UnitY
+ * where nothing was found), and for the two MoveWithSlide chains (:96, :118) the number of attempts that cast rays (0..3) and why
+ * the chain ended: 0 not run, 1 no collision, 2 |alignment| > 0.9, 3 zero slide direction, 4 depth limit.  All zero under noclip. */
+typedef struct swr_character_trace {
+    int32_t ground_found, ceiling_found;
+    float ground_point[3], ground_normal[3];
+    int32_t chain_attempts[2], chain_stop[2];
+} swr_character_trace;                                                                         /* 48 B */
+/* verticalSteps = Math.Max(1, (int)(Height / (radius * 2))) and horizontalRays = Math.Max(4, (int)(4 * MathF.PI * radius / 0.1f)) with
+ * radius = Radius + 0.001f (:96,118,327-328), in float arithmetic in the reference's order.  Host code only; a slide attempt casts
+ * (verticalSteps + 1) * horizontalRays rays.  NULL arguments: SWR_ERR_INVALID_ARG. */
+int  swr_character_ray_counts(const swr_character_params* params, int* vertical_steps, int* horizontal_rays);
+/* CharacterController.Update(delta_time, inputs[i].move, inputs[i].jump) for chars[0..n) in ONE call without a host round trip inside
+ * it: both CheckPlanes, both MoveWithSlide chains of up to three attempts and the velocity update, in the reference's serial
+ * schedules (CheckPlane: rays outer in offsets[] order, targets inner; MoveWithSlide: targets outer, then vStep, then hStep; strict
+ * `<` in both), bit for bit under this library's System.Numerics model, the context's Transform flag and the call's Cross model.
+ * ring: n_ring pairs (cos, sin) of the angle 2 * MathF.PI * hStep / horizontalRays AS THE CALLER'S RUNTIME COMPUTES THEM (MathF.Cos is
+ * the C runtime's and cannot be reproduced on the device); the device multiplies by radius.  n_ring must equal horizontal_rays of
+ * swr_character_ray_counts.  targets: collisionModels[i] flattened, model-major, mesh-minor; a model that does not invert is left
+ * out by the caller.  flags: 0 or SWR_RAY_CROSS_FUSED; the face mask is always IgnoreBackfaces (:282,357).  trace: NULL or n records.
+ * n == 0: SWR_OK, nothing written.  n_targets == 0: the step runs with every ray missing.  NULL pointers, negative counts, other
+ * flag bits, a target without a mesh, n_ring != horizontal_rays: SWR_ERR_INVALID_ARG.  LIMITS: n <= 65536 controllers, at most 4096
+ * rays per slide attempt, n * max(18, rays per attempt) <= 2^22 rays (two ray buffers of 24 B each: at most 192 MiB, whatever n_targets
+ * is), n_targets <= 65535, n * max(18, rays per attempt) * n_targets <= 2^24 (ray, target) pairs per call, beyond which SWR_ERR_UNSUPPORTED (split the controllers).  Runs on the ray stream, like swr_raycast: recorded draws are neither flushed
+ * nor waited for. */
+int  swr_character_update(swr_context* ctx, const swr_character_params* params, swr_character* chars, const swr_character_input* inputs,
+                          int n, float delta_time, const float* ring, int n_ring, const swr_ray_target* targets, int n_targets,
+                          int flags, swr_character_trace* trace);
+
 /* User fragment programs --------------------------------------------------------------------------------------------------------
  * Source contract (softwarerenderer_amd/csrc/swr_program.hip.h is the prelude compiled in front of the text; INTEGRATION.md has a
  * porting guide): the text defines

@@ -76,6 +76,26 @@ class RayHit(C.Structure):  # swr_ray_hit (40 bytes)
                 ("point", C.c_float * 3), ("normal", C.c_float * 3)]
 
 
+class CharacterParams(C.Structure):  # swr_character_params (52 bytes): the properties of CharacterController.cs:21-32
+    _fields_ = [("gravity", C.c_float * 3)] + [(n, C.c_float) for n in (
+        "height", "radius", "step_size", "move_speed", "jump_force", "ground_acceleration", "air_acceleration", "max_air_speed",
+        "ground_friction", "air_control")]
+
+
+class Character(C.Structure):  # swr_character (44 bytes): one controller's state, in and out
+    _fields_ = [("position", C.c_float * 3), ("velocity", C.c_float * 3), ("jump_cooldown", C.c_float), ("actual_step_size", C.c_float),
+                ("grounded", C.c_int32), ("ceiling", C.c_int32), ("noclip", C.c_int32)]
+
+
+class CharacterInput(C.Structure):  # swr_character_input (16 bytes)
+    _fields_ = [("move", C.c_float * 3), ("jump", C.c_int32)]
+
+
+class CharacterTrace(C.Structure):  # swr_character_trace (48 bytes)
+    _fields_ = [("ground_found", C.c_int32), ("ceiling_found", C.c_int32), ("ground_point", C.c_float * 3), ("ground_normal", C.c_float * 3),
+                ("chain_attempts", C.c_int32 * 2), ("chain_stop", C.c_int32 * 2)]
+
+
 SWR_RAY_FACES_ALL, SWR_RAY_IGNORE_BACKFACES, SWR_RAY_IGNORE_FRONTFACES, SWR_RAY_CROSS_FUSED = 0, 1, 2, 0x100
 
 # every symbol include/swr.h declares; tests/test_abi.py checks the library exports all of them
@@ -89,7 +109,7 @@ EXPORTS = [
     "swr_profile_enable", "swr_profile_get", "swr_profile_reset", "swr_profile_raster_samples", "swr_device_name", "swr_debug_counters", "swr_selftest_division",
     "swr_program_create", "swr_program_destroy", "swr_program_set_constants", "swr_program_validate",
     "swr_program_create_vf", "swr_program_validate_vf",
-    "swr_raycast", "swr_raycast_nearest",
+    "swr_raycast", "swr_raycast_nearest", "swr_character_ray_counts", "swr_character_update",
 ]
 
 _libs = {}
@@ -177,6 +197,8 @@ def load(name: str = None) -> C.CDLL:
         "swr_program_validate_vf": (I, [C.c_char_p, C.c_char_p, C.c_char_p, I]),
         "swr_raycast": (I, [P, P, I, P, I, I, P]),
         "swr_raycast_nearest": (I, [P, P, I, P, I, I, P]),
+        "swr_character_ray_counts": (I, [P, C.POINTER(I), C.POINTER(I)]),
+        "swr_character_update": (I, [P, P, P, P, I, F, P, I, P, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

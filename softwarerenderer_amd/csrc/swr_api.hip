@@ -41,6 +41,7 @@
 #include "swr_raster_c.hip.h"
 #include "swr_cull.hip.h"
 #include "swr_raycast.hip.h"
+#include "swr_character.hip.h"
 
 using namespace swr;
 
@@ -165,6 +166,123 @@ int raycast(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_targe
     if (staged) memcpy(out, down, down_bytes);
     return SWR_OK;
 }
+
+// Math.Max(1, (int)(Height / (radius * 2))) and Math.Max(4, (int)(4 * MathF.PI * radius / 0.1f)), CharacterController.cs:327-328, radius = Radius + 0.001f
+// (:96,118): float arithmetic in the reference's order.  false: a count that is not a number or does not fit the limits.
+bool character_ray_counts(const swr_character_params* p, int* v_steps, int* h_rays) {
+    const float radius = p->radius + 0.001f;
+    const float two_r = radius * 2.0f;
+    const float v = p->height / two_r;
+    const float four_pi = 4.0f * 3.14159274f;
+    const float h = (four_pi * radius) / 0.1f;
+    const bool ok = v == v && h == h && v < 65536.0f && h < 65536.0f;
+    *v_steps = ok ? std::max(1, (int)v) : 1;
+    *h_rays = ok ? std::max(4, (int)h) : 4;
+    return ok;
+}
+
+// swr_character_update: one upload, k_char_begin, (cast, planes), 6 x (cast, slide), one download, one wait -- nothing between the
+// kernels is read by the host, and no grid depends on a value computed on the device.
+int character_update(swr_context* c, const swr_character_params* params, swr_character* chars, const swr_character_input* inputs, int n, float dt,
+                     const float* ring, int n_ring, const swr_ray_target* targets, int n_targets, int flags, swr_character_trace* trace) {
+    if (n < 0 || n_targets < 0 || n_ring < 0) return fail(c, SWR_ERR_INVALID_ARG, "negative count in character update");
+    if (flags & ~SWR_RAY_CROSS_FUSED) return fail(c, SWR_ERR_INVALID_ARG, "character update accepts SWR_RAY_CROSS_FUSED only");
+    if (n == 0) return SWR_OK;
+    if (!params || !chars || !inputs || !ring || (n_targets > 0 && !targets)) return fail(c, SWR_ERR_INVALID_ARG, "null argument to character update");
+    int v_steps = 0, h_rays = 0;
+    const bool counts_ok = character_ray_counts(params, &v_steps, &h_rays);
+    const uint64_t slide_rays = (uint64_t)(v_steps + 1) * (uint64_t)h_rays;
+    const uint64_t stride = std::max<uint64_t>(slide_rays, SWR_CHAR_PLANE_RAYS);
+    static const char* limits = "character update: at most 65536 controllers, 4096 rays per slide attempt, 2^22 rays (controllers x rays per attempt), 65535 targets and 2^24 (ray, target) pairs per call: split the controllers";
+    if (!counts_ok || slide_rays > SWR_CHAR_MAX_RAYS) return fail(c, SWR_ERR_UNSUPPORTED, limits);
+    if (n_ring != h_rays) return fail(c, SWR_ERR_INVALID_ARG, "n_ring must equal horizontal_rays of swr_character_ray_counts");
+    if (n > 65536 || n_targets > 65535 || (uint64_t)n * stride > (1ull << 22) || (uint64_t)n * stride * (uint64_t)n_targets > (1ull << 24)) return fail(c, SWR_ERR_UNSUPPORTED, limits);
+    for (int t = 0; t < n_targets; ++t) if (!targets[t].mesh) return fail(c, SWR_ERR_INVALID_ARG, "character update target without a mesh");
+    if (!c->ray_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->ray_stream, hipStreamNonBlocking));
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t N = (size_t)n, NT = (size_t)n_targets;
+    const size_t off_chars = 0, off_in = off_chars + al(N * sizeof(swr_character)), off_ring = off_in + al(N * sizeof(swr_character_input));
+    const size_t off_t = off_ring + al((size_t)n_ring * 8), up_bytes = off_t + al(NT * sizeof(RayTarget));
+    const size_t off_work = up_bytes, off_active = off_work + al(N * sizeof(CharWork)), off_rays = off_active + al(N * 4);
+    const size_t rays_bytes = al(N * stride * sizeof(swr_ray));
+    const size_t off_down = off_rays + 2 * rays_bytes, off_trace = al(N * sizeof(swr_character));
+    const size_t down_bytes = off_trace + N * sizeof(swr_character_trace);
+    int rc = ensure(c, c->d_char, off_down + down_bytes); if (rc) return rc;
+    const size_t pairs = N * stride * NT;
+    if (c->d_ray_best.cap < pairs * 8) {
+        if ((rc = ensure(c, c->d_ray_best, pairs * 8))) return rc;
+        SWR_HIP(c, hipMemsetAsync(c->d_ray_best.p, 0xff, c->d_ray_best.cap, c->ray_stream));      // from here on the folds keep it clean
+    }
+    const bool staged = up_bytes + down_bytes <= ((size_t)1 << 20);
+    if (staged && c->ray_host_cap < up_bytes + down_bytes) {
+        if (c->ray_host) (void)hipHostFree(c->ray_host);
+        c->ray_host = nullptr; c->ray_host_cap = 0;
+        const size_t cap = std::max<size_t>(up_bytes + down_bytes, (size_t)1 << 16);
+        SWR_HIP(c, hipHostMalloc(&c->ray_host, cap, hipHostMallocDefault));
+        c->ray_host_cap = cap;
+    }
+    std::vector<char> pageable;
+    if (!staged) pageable.resize(up_bytes + down_bytes);
+    char* up = staged ? static_cast<char*>(c->ray_host) : pageable.data();
+    memcpy(up + off_chars, chars, N * sizeof(swr_character));
+    memcpy(up + off_in, inputs, N * sizeof(swr_character_input));
+    memcpy(up + off_ring, ring, (size_t)n_ring * 8);
+    RayTarget* ht = reinterpret_cast<RayTarget*>(up + off_t);
+    uint32_t max_tris = 0;
+    for (int t = 0; t < n_targets; ++t) {
+        swr_mesh* m = const_cast<swr_mesh*>(targets[t].mesh);
+        if (m->uploaded && !m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
+        ht[t].verts = m->d_verts; ht[t].idx = m->d_idx; ht[t].n_tris = (uint32_t)(m->n_idx / 3); ht[t].pad = 0u;
+        memcpy(ht[t].model, targets[t].model, 64); memcpy(ht[t].normal_matrix, targets[t].normal_matrix, 64);
+        max_tris = std::max(max_tris, ht[t].n_tris);
+    }
+    char* base = static_cast<char*>(c->d_char.p);
+    const swr_character* d_chars = reinterpret_cast<const swr_character*>(base + off_chars);
+    const swr_character_input* d_in = reinterpret_cast<const swr_character_input*>(base + off_in);
+    const float* d_ring = reinterpret_cast<const float*>(base + off_ring);
+    const RayTarget* d_targets = reinterpret_cast<const RayTarget*>(base + off_t);
+    CharWork* d_work = reinterpret_cast<CharWork*>(base + off_work);
+    uint32_t* d_active = reinterpret_cast<uint32_t*>(base + off_active);
+    swr_ray* d_rays[2] = { reinterpret_cast<swr_ray*>(base + off_rays), reinterpret_cast<swr_ray*>(base + off_rays + rays_bytes) };
+    swr_character* d_out = reinterpret_cast<swr_character*>(base + off_down);
+    swr_character_trace* d_trace = trace ? reinterpret_cast<swr_character_trace*>(base + off_down + off_trace) : nullptr;
+    unsigned long long* d_best = c->d_ray_best.as<unsigned long long>();
+    CharCall cc;
+    cc.p = *params; cc.dt = dt; cc.n = (uint32_t)n; cc.n_targets = (uint32_t)n_targets; cc.stride = (uint32_t)stride;
+    cc.v_steps = (uint32_t)v_steps; cc.h_rays = (uint32_t)h_rays; cc.slide_rays = (uint32_t)slide_rays; cc.nm_flags = c->nm_flags;
+    const bool fused = (flags & SWR_RAY_CROSS_FUSED) != 0;
+    const uint32_t tri_blocks = (max_tris + SWR_RAY_BLOCK - 1) / SWR_RAY_BLOCK, nt = cc.n_targets, st = cc.stride;
+    hipStream_t s = c->ray_stream;
+    SWR_HIP(c, hipMemcpyAsync(base, up, up_bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_char_begin, dim3((cc.n + 63u) / 64u), dim3(64), 0, s, cc, d_chars, d_in, d_work, d_active, d_rays[0], d_out, d_trace);
+    if (tri_blocks) {
+        const dim3 grid(cc.n, tri_blocks, nt);
+        if (fused) hipLaunchKernelGGL((k_char_cast<true, true>), grid, dim3(SWR_RAY_BLOCK), 0, s, d_rays[0], st, (uint32_t)SWR_CHAR_PLANE_RAYS, 1u, d_active, d_targets, nt, cc.nm_flags, d_best);
+        else hipLaunchKernelGGL((k_char_cast<false, true>), grid, dim3(SWR_RAY_BLOCK), 0, s, d_rays[0], st, (uint32_t)SWR_CHAR_PLANE_RAYS, 1u, d_active, d_targets, nt, cc.nm_flags, d_best);
+    }
+    if (fused) hipLaunchKernelGGL(k_char_planes<true>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, d_rays[0], d_rays[1], d_targets, d_best);
+    else hipLaunchKernelGGL(k_char_planes<false>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, d_rays[0], d_rays[1], d_targets, d_best);
+    const uint32_t chunks = (cc.slide_rays + SWR_RAY_CHUNK - 1) / SWR_RAY_CHUNK;
+    for (int round = 0; round < SWR_CHAR_SLIDE_ROUNDS; ++round) {
+        swr_ray* in = d_rays[(round + 1) & 1];
+        swr_ray* next = d_rays[round & 1];
+        if (tri_blocks) {
+            const dim3 grid(cc.n * chunks, tri_blocks, nt);
+            if (fused) hipLaunchKernelGGL((k_char_cast<true, false>), grid, dim3(SWR_RAY_BLOCK), 0, s, in, st, cc.slide_rays, chunks, d_active, d_targets, nt, cc.nm_flags, d_best);
+            else hipLaunchKernelGGL((k_char_cast<false, false>), grid, dim3(SWR_RAY_BLOCK), 0, s, in, st, cc.slide_rays, chunks, d_active, d_targets, nt, cc.nm_flags, d_best);
+        }
+        if (fused) hipLaunchKernelGGL(k_char_slide<true>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, in, next, d_targets, d_best, d_out, d_trace);
+        else hipLaunchKernelGGL(k_char_slide<false>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, in, next, d_targets, d_best, d_out, d_trace);
+    }
+    SWR_HIP(c, hipGetLastError());
+    const size_t down_now = trace ? down_bytes : N * sizeof(swr_character);
+    char* down = up + up_bytes;
+    SWR_HIP(c, hipMemcpyAsync(down, d_out, down_now, hipMemcpyDeviceToHost, s));
+    SWR_HIP(c, hipStreamSynchronize(s));
+    memcpy(chars, down, N * sizeof(swr_character));
+    if (trace) memcpy(trace, down + off_trace, N * sizeof(swr_character_trace));
+    return SWR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -276,7 +394,7 @@ void swr_destroy(swr_context* c) {
         release(c->present_buf[i]);
     }
     DevBuf* bufs[] = { &c->own_color, &c->own_depth, &c->d_slot_tb, &c->d_want, &c->d_ctrl, &c->d_pair_tile, &c->d_tile_list, &c->d_tile_stats,
-                       &c->d_counters, &c->d_total, &c->d_scratch, &c->d_ray, &c->d_ray_best };
+                       &c->d_counters, &c->d_total, &c->d_scratch, &c->d_ray, &c->d_ray_best, &c->d_char };
     for (DevBuf* b : bufs) release(*b);
     for (auto& s : c->sets) {
         DevBuf* sb[] = { &s.d_upload, &s.d_vout, &s.d_vnorm, &s.d_recs, &s.d_masks, &s.d_pcounts, &s.d_pair_refs, &s.d_tile_count, &s.d_tile_start, &s.d_order };
@@ -629,6 +747,14 @@ int swr_raycast(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_t
 }
 int swr_raycast_nearest(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets, int flags, swr_ray_hit* out) {
     SWR_ENTER(c); return raycast(c, rays, n_rays, targets, n_targets, flags, out, true);
+}
+int swr_character_ray_counts(const swr_character_params* params, int* vertical_steps, int* horizontal_rays) {
+    if (!params || !vertical_steps || !horizontal_rays) return SWR_ERR_INVALID_ARG;
+    return character_ray_counts(params, vertical_steps, horizontal_rays) ? SWR_OK : SWR_ERR_UNSUPPORTED;
+}
+int swr_character_update(swr_context* c, const swr_character_params* params, swr_character* chars, const swr_character_input* inputs, int n, float delta_time,
+                         const float* ring, int n_ring, const swr_ray_target* targets, int n_targets, int flags, swr_character_trace* trace) {
+    SWR_ENTER(c); return character_update(c, params, chars, inputs, n, delta_time, ring, n_ring, targets, n_targets, flags, trace);
 }
 
 int swr_is_sphere_in_frustum(swr_context* c, const float center_radius[4], const float model[16], const float view[16],

@@ -169,6 +169,7 @@ struct swr_context {
     hipStream_t ray_stream = nullptr;
     DevBuf d_ray, d_ray_best;                  // rays | targets | hit records; the pairs' keys, all SWR_RAY_NO_HIT between calls (k_ray_finish)
     void* ray_host = nullptr; size_t ray_host_cap = 0;     // pinned staging block of small queries
+    DevBuf d_char;                             // swr_character_update: controllers | inputs | ring | targets | work | active | rays x 2 | results
 
     int profiling = 0;                         // 0 off, 1 every stage, 2 only the raster kernel (2 events per flush)
     std::vector<EventSpan> spans;

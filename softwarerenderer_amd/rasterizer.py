@@ -668,6 +668,172 @@ class Physics:
         return Physics._query("swr_raycast_nearest", rays, targets, faceMask, crossFused, False)[0]
 
 
+# numpy views of swr_character_params (52 B), swr_character (44 B), swr_character_input (16 B) and swr_character_trace (48 B)
+CHARACTER_PARAMS_DTYPE = np.dtype([("gravity", "<f4", 3), ("height", "<f4"), ("radius", "<f4"), ("step_size", "<f4"), ("move_speed", "<f4"),
+                                   ("jump_force", "<f4"), ("ground_acceleration", "<f4"), ("air_acceleration", "<f4"), ("max_air_speed", "<f4"),
+                                   ("ground_friction", "<f4"), ("air_control", "<f4")])
+CHARACTER_DTYPE = np.dtype([("position", "<f4", 3), ("velocity", "<f4", 3), ("jump_cooldown", "<f4"), ("actual_step_size", "<f4"),
+                            ("grounded", "<i4"), ("ceiling", "<i4"), ("noclip", "<i4")])
+CHARACTER_INPUT_DTYPE = np.dtype([("move", "<f4", 3), ("jump", "<i4")])
+CHARACTER_TRACE_DTYPE = np.dtype([("ground_found", "<i4"), ("ceiling_found", "<i4"), ("ground_point", "<f4", 3), ("ground_normal", "<f4", 3),
+                                  ("chain_attempts", "<i4", 2), ("chain_stop", "<i4", 2)])
+assert CHARACTER_PARAMS_DTYPE.itemsize == 52 == C.sizeof(N.CharacterParams) and CHARACTER_DTYPE.itemsize == 44 == C.sizeof(N.Character)
+assert CHARACTER_INPUT_DTYPE.itemsize == 16 == C.sizeof(N.CharacterInput) and CHARACTER_TRACE_DTYPE.itemsize == 48 == C.sizeof(N.CharacterTrace)
+
+
+class CharacterController:
+    """public class CharacterController (CharacterController.cs:7-45) over retained meshes: Update runs whole on the GPU, in one
+    call (swr_character_update).  collisionModels = one list of Mesh per model, modelMatrices = one matrix per model, as the
+    reference's constructor takes them; they are flattened model-major, mesh-minor, and a model that does not invert is left out.
+
+    The ring table -- (cos, sin) of the float32 angle 2 * pi * hStep / horizontalRays (:348-353) -- is the CALLER's: .NET's
+    MathF.Cos / MathF.Sin are the C runtime's and the device cannot reproduce them, so this class computes the table with
+    math.cos / math.sin of the float32 angle, rounded to float32, and a C# caller computes it with MathF (csharp/RasterizerNative.cs).
+    CamOffset is kept for the caller's camera and takes no part in Update."""
+
+    JumpCooldownDuration = 0.25
+
+    def __init__(self, initialPosition, collisionModels, modelMatrices, crossFused: bool = False):
+        self.Position = np.asarray(initialPosition, dtype=np.float32).reshape(3).copy()
+        self.Velocity = np.zeros(3, dtype=np.float32)
+        self.IsGrounded = False
+        self.IsCeiling = False
+        self.IsNoClipEnabled = False
+        self.Gravity = np.array([0.0, -14.0, 0.0], dtype=np.float32)
+        self.Height = 0.5
+        self.Radius = 0.15
+        self.StepSize = 0.3
+        self.ActualStepSize = np.float32(0.03)
+        self.MoveSpeed = 5.0
+        self.JumpForce = 4.0
+        self.GroundAcceleration = 3.5
+        self.AirAcceleration = 0.35
+        self.MaxAirSpeed = 6.0
+        self.GroundFriction = 6.0
+        self.AirControl = 0.2
+        self.CamOffset = np.array([0.0, 0.15, 0.0], dtype=np.float32)
+        self.JumpCooldownTimer = np.float32(0.0)
+        self.CrossFused = bool(crossFused)
+        self.CollisionModels = [list(m) for m in collisionModels] if collisionModels is not None else None
+        self.ModelMatrices = [np.asarray(m, dtype=np.float32).reshape(4, 4) for m in modelMatrices] if modelMatrices is not None else None
+        self.LastTrace = None
+        self._flat = None
+        self._ring_key, self._ring = None, None
+
+    # ---- what the caller supplies
+    def Params(self) -> np.ndarray:
+        p = np.zeros((), dtype=CHARACTER_PARAMS_DTYPE)
+        p["gravity"] = self.Gravity
+        for name, v in (("height", self.Height), ("radius", self.Radius), ("step_size", self.StepSize), ("move_speed", self.MoveSpeed),
+                        ("jump_force", self.JumpForce), ("ground_acceleration", self.GroundAcceleration),
+                        ("air_acceleration", self.AirAcceleration), ("max_air_speed", self.MaxAirSpeed),
+                        ("ground_friction", self.GroundFriction), ("air_control", self.AirControl)):
+            p[name] = v
+        return p
+
+    @staticmethod
+    def RayCounts(params) -> tuple:
+        """(verticalSteps, horizontalRays) of MoveWithSlide (:327-328) for a CHARACTER_PARAMS_DTYPE record (swr_character_ray_counts)."""
+        p = np.ascontiguousarray(params, dtype=CHARACTER_PARAMS_DTYPE).reshape(1)
+        v, h = C.c_int(0), C.c_int(0)
+        rc = N.load().swr_character_ray_counts(p.ctypes.data, C.byref(v), C.byref(h))
+        if rc != N.SWR_OK:
+            raise N.SwrError(rc, "ray counts of these parameters are not numbers or beyond the limits")
+        return v.value, h.value
+
+    @staticmethod
+    def Ring(horizontalRays: int) -> np.ndarray:
+        """(horizontalRays, 2) float32: cos and sin of the float32 angle 2 * MathF.PI * hStep / horizontalRays (:348), through the C
+        runtime's double cos / sin rounded to float32 -- this caller's table."""
+        import math
+        two_pi = np.float32(2.0) * np.float32(math.pi)
+        out = np.empty((horizontalRays, 2), dtype=np.float32)
+        for h in range(horizontalRays):
+            angle = np.float32(np.float32(two_pi * np.float32(h)) / np.float32(horizontalRays))
+            out[h] = np.float32(math.cos(float(angle))), np.float32(math.sin(float(angle)))
+        return out
+
+    def _ring_table(self, params) -> np.ndarray:
+        key = float(np.float32(self.Radius)), float(np.float32(self.Height))
+        if self._ring_key != key:
+            self._ring_key, self._ring = key, CharacterController.Ring(CharacterController.RayCounts(params)[1])
+        return self._ring
+
+    def _targets(self):
+        if self.CollisionModels is None or self.ModelMatrices is None or len(self.CollisionModels) != len(self.ModelMatrices):
+            return []                                                          # :233, :314: every query answers "nothing"
+        if self._flat is None:
+            self._flat = [(mesh, m) for meshes, m in zip(self.CollisionModels, self.ModelMatrices) for mesh in meshes]
+        return self._flat
+
+    @staticmethod
+    def _same_targets(a, b) -> bool:
+        """the same Mesh objects under equal matrices, in the same order"""
+        ta, tb = a._targets(), b._targets()
+        return len(ta) == len(tb) and all(x[0] is y[0] and np.array_equal(x[1], y[1]) for x, y in zip(ta, tb))
+
+    def State(self) -> np.ndarray:
+        s = np.zeros((), dtype=CHARACTER_DTYPE)
+        s["position"], s["velocity"] = self.Position, self.Velocity
+        s["jump_cooldown"], s["actual_step_size"] = self.JumpCooldownTimer, self.ActualStepSize
+        s["grounded"], s["ceiling"], s["noclip"] = int(self.IsGrounded), int(self.IsCeiling), int(self.IsNoClipEnabled)
+        return s
+
+    def _take(self, s, trace):
+        self.Position, self.Velocity = s["position"].copy(), s["velocity"].copy()
+        self.JumpCooldownTimer, self.ActualStepSize = np.float32(s["jump_cooldown"]), np.float32(s["actual_step_size"])
+        self.IsGrounded, self.IsCeiling = bool(s["grounded"]), bool(s["ceiling"])
+        self.LastTrace = trace
+
+    def Update(self, DeltaTime: float, MoveInput, JumpRequested: bool) -> None:
+        """CharacterController.Update (:50-140)."""
+        CharacterController.UpdateBatch([self], DeltaTime, [MoveInput], [JumpRequested])
+
+    @staticmethod
+    def UpdateRaw(device, params, states, inputs, DeltaTime, ring, targets, crossFused=False, trace=True):
+        """swr_character_update on arrays: states (CHARACTER_DTYPE) is updated in place; returns the CHARACTER_TRACE_DTYPE array or None.
+        targets = [(Mesh, model[, normal_matrix])] as Physics.RaycastBatch takes them."""
+        p = np.ascontiguousarray(params, dtype=CHARACTER_PARAMS_DTYPE).reshape(1)
+        if states.dtype != CHARACTER_DTYPE or not states.flags.c_contiguous:
+            raise ValueError("states must be a C-contiguous CHARACTER_DTYPE array")
+        inp = np.ascontiguousarray(inputs, dtype=CHARACTER_INPUT_DTYPE).reshape(-1)
+        if inp.shape[0] != states.shape[0]:
+            raise ValueError("one input per controller")
+        r = np.ascontiguousarray(ring, dtype=np.float32).reshape(-1, 2)
+        arr, kept, dev = Physics._targets(targets)
+        dev = dev or device
+        tr = np.zeros(states.shape[0], dtype=CHARACTER_TRACE_DTYPE) if trace else None
+        flags = N.SWR_RAY_CROSS_FUSED if crossFused else 0
+        dev._ck(dev._lib.swr_character_update(dev._ctx, p.ctypes.data, states.ctypes.data, inp.ctypes.data, int(states.shape[0]),
+                                              float(DeltaTime), r.ctypes.data, int(r.shape[0]), C.addressof(arr), len(kept), flags,
+                                              tr.ctypes.data if trace else None))
+        return tr
+
+    @staticmethod
+    def UpdateBatch(controllers, DeltaTime: float, MoveInputs, JumpRequests, device=None) -> None:
+        """Update for many controllers in one call.  They share the first one's properties, collision models and Cross model (the
+        call has one swr_character_params and one target list); position, velocity, timers and flags are each controller's own."""
+        if not controllers:
+            return
+        first = controllers[0]
+        params = first.Params()
+        for c in controllers[1:]:
+            if c.Params().tobytes() != params.tobytes() or c.CrossFused != first.CrossFused or not CharacterController._same_targets(c, first):
+                raise ValueError("the controllers of one batch share their properties, collision models and Cross model")
+        states = np.array([c.State() for c in controllers], dtype=CHARACTER_DTYPE)
+        inputs = np.zeros(len(controllers), dtype=CHARACTER_INPUT_DTYPE)
+        inputs["move"] = np.asarray(MoveInputs, dtype=np.float32).reshape(len(controllers), 3)
+        inputs["jump"] = [1 if j else 0 for j in JumpRequests]
+        targets = first._targets()
+        if device is None:
+            if not targets:
+                raise ValueError("a controller without collision meshes needs the `device` argument")
+            device = targets[0][0]._dev
+        trace = CharacterController.UpdateRaw(device, params, states, inputs, DeltaTime, first._ring_table(params), targets, first.CrossFused)
+        for c, s, t in zip(controllers, states, trace):
+            c._take(s, t)
+
+
 def as_vertex_array(vertices) -> np.ndarray:
     v = np.asarray(vertices)
     if v.dtype == VERTEX_DTYPE:

@@ -1,0 +1,583 @@
+"""Cases and the reference restatement for swr_character_update (test helper; not part of the package).
+
+`update` restates CharacterController.Update, CheckPlane and MoveWithSlide (CharacterController.cs:50-393) in numpy float32, line by
+line, in the reference's SERIAL schedules:
+
+  * CheckPlane (:260-301): rays outer in offsets[] order, targets inner, a hit counts if hitDistance <= maxDistance and wins under
+    strict `<` from float.MaxValue;
+  * MoveWithSlide (:330-373): TARGETS outer, then vStep, then hStep, strict `<` from moveDistance.
+
+It is built on raycast_cases.py: world arrays from the oracle library (so they follow the oracle variant and its Transform flag),
+dot3v / cross3v / normalize3v / fma32 for the Vector3 operations, and `cast_many`, which is raycast_cases.raycast vectorised over
+the rays of one attempt (tests/test_character_host.py holds it to raycast_cases.raycast record by record).  float.Lerp follows the
+variant (fused in the "fma" builds).  ProjectOnPlane is scalar C#: left to right with plain rounded operations in every variant.
+
+`mut` names the mutants of tests/test_character_host.py: "plane_target_major", "slide_ray_major" (the other fold order in each fold),
+"plane_lt" (`<` for `<=` at maxDistance), "chain1_new_step" (chain 1 reading the ActualStepSize of :103), "project_dot3v"
+(ProjectOnPlane through Vector3.Dot)."""
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+
+import raycast_cases as R
+from softwarerenderer_amd import hostmath as hm
+from softwarerenderer_amd.rasterizer import (CHARACTER_DTYPE, CHARACTER_INPUT_DTYPE, CHARACTER_PARAMS_DTYPE, CHARACTER_TRACE_DTYPE,
+                                              CharacterController)
+
+F32 = np.float32
+NEG_INF = F32(-np.inf)
+STATE_FLOATS = ("position", "velocity", "jump_cooldown", "actual_step_size")
+STATE_INTS = ("grounded", "ceiling", "noclip")
+TRACE_FLOATS = ("ground_point", "ground_normal")
+TRACE_INTS = ("ground_found", "ceiling_found", "chain_attempts", "chain_stop")
+
+
+def v3(x, y, z):
+    return np.array([x, y, z], dtype=F32)
+
+
+def params(**kw):
+    """swr_character_params with the defaults of CharacterController.cs:21-32."""
+    p = np.zeros((), dtype=CHARACTER_PARAMS_DTYPE)
+    p["gravity"] = (0, -14.0, 0)
+    p["height"], p["radius"], p["step_size"], p["move_speed"], p["jump_force"] = 0.5, 0.15, 0.3, 5.0, 4.0
+    p["ground_acceleration"], p["air_acceleration"], p["max_air_speed"], p["ground_friction"], p["air_control"] = 3.5, 0.35, 6.0, 6.0, 0.2
+    for k, v in kw.items():
+        p[k] = v
+    return p
+
+
+def state(position, velocity=(0, 0, 0), grounded=0, cooldown=0.0, step=0.03, noclip=0, ceiling=0):
+    s = np.zeros((), dtype=CHARACTER_DTYPE)
+    s["position"], s["velocity"], s["jump_cooldown"], s["actual_step_size"] = position, velocity, cooldown, step
+    s["grounded"], s["ceiling"], s["noclip"] = grounded, ceiling, noclip
+    return s
+
+
+def ray_counts(p):
+    """:327-328 with radius = Radius + 0.001f, float arithmetic in the reference's order."""
+    radius = F32(p["radius"]) + F32(0.001)
+    v = int(F32(p["height"]) / (radius * F32(2)))
+    h = int(((F32(4) * F32(np.pi)) * radius) / F32(0.1))
+    return max(1, v), max(4, h)
+
+
+def same_state(a, b):
+    from cull_edge_cases import same_words
+    return all(same_words(a[f], b[f]) for f in STATE_FLOATS) and all(np.array_equal(a[f], b[f]) for f in STATE_INTS)
+
+
+def same_trace(a, b):
+    from cull_edge_cases import same_words
+    return all(same_words(a[f], b[f]) for f in TRACE_FLOATS) and all(np.array_equal(a[f], b[f]) for f in TRACE_INTS)
+
+
+def show(s, t=None):
+    from cull_edge_cases import words
+    out = (f"pos {words(s['position'])} vel {words(s['velocity'])} cd {words(s['jump_cooldown'])} step {words(s['actual_step_size'])} "
+           f"g/c/n {int(s['grounded'])}{int(s['ceiling'])}{int(s['noclip'])}")
+    if t is not None:
+        out += (f" | ground {int(t['ground_found'])} ceil {int(t['ceiling_found'])} gp {words(t['ground_point'])} gn {words(t['ground_normal'])} "
+                f"attempts {t['chain_attempts'].tolist()} stop {t['chain_stop'].tolist()}")
+    return out
+
+
+# ============================================================================ Physics.Raycast over the rays of one attempt
+def cast_many(origins, directions, P, N, idx, order, fused):
+    """raycast_cases.raycast (mask IgnoreBackfaces) for every ray against one mesh: (found, distance, point, normal) arrays."""
+    O = np.asarray(origins, dtype=F32).reshape(-1, 3)
+    D = np.asarray(directions, dtype=F32).reshape(-1, 3)
+    n = O.shape[0]
+    found, dist_out = np.zeros(n, dtype=bool), np.full(n, R.FLT_MAX, dtype=F32)
+    point, normal = np.zeros((n, 3), dtype=F32), np.zeros((n, 3), dtype=F32)
+    tri = np.asarray(idx, dtype=np.int64).reshape(-1)
+    tri = tri[:(tri.shape[0] // 3) * 3].reshape(-1, 3)
+    if tri.shape[0] == 0 or n == 0:
+        return found, dist_out, point, normal
+    with np.errstate(all="ignore"):
+        d = R.normalize3v(D, order)                                          # Physics.cs:69
+        v0, v1, v2 = P[tri[:, 0]], P[tri[:, 1]], P[tri[:, 2]]
+        e1, e2 = (v1 - v0)[None], (v2 - v0)[None]
+        dd = d[:, None, :]
+        pvec = R.cross3v(dd, e2, fused)
+        det = R.dot3v(e1, pvec, order)
+        alive = ~(det < R.EPS) & ~(np.abs(det) < R.EPS)
+        inv = F32(1.0) / det
+        tvec = O[:, None, :] - v0[None]
+        u = R.dot3v(tvec, pvec, order) * inv
+        alive &= ~((u < 0) | (u > 1))
+        qvec = R.cross3v(tvec, e1, fused)
+        v = R.dot3v(dd, qvec, order) * inv
+        alive &= ~((v < 0) | (u + v > 1))
+        dist = R.dot3v(e2, qvec, order) * inv
+        alive &= ~(dist < 0)
+        cand = alive & (dist < R.FLT_MAX)
+        w = np.argmin(np.where(cand, dist, F32(np.inf)), axis=1)             # the first of the minima: the lowest triangle
+        found = cand.any(axis=1)
+        r = np.arange(n)
+        uw, vw, dw = u[r, w], v[r, w], dist[r, w]
+        b0 = (F32(1.0) - uw) - vw
+        nn = (N[tri[w, 0]] * b0[:, None] + N[tri[w, 1]] * uw[:, None]) + N[tri[w, 2]] * vw[:, None]
+        normal = np.where(found[:, None], R.normalize3v(nn, order), F32(0)).astype(F32)
+        point = np.where(found[:, None], O + d * dw[:, None], F32(0)).astype(F32)
+        dist_out = np.where(found, dw, R.FLT_MAX).astype(F32)
+    return found, dist_out, point, normal
+
+
+# ============================================================================ the world of a case
+class World:
+    """The flattened targets of a case (raycast_cases.Target) under one oracle build, Transform flag and Cross model."""
+
+    def __init__(self, lib, variant, targets, fused=False, flag=None):
+        self.lib, self.variant, self.targets, self.fused, self.flag = lib, variant, list(targets), fused, flag
+        self.order = R.DOT_ORDER[variant]
+        self.lerp_fused = "fma" in variant
+
+    def arrays(self, t):
+        from cull_edge_cases import oracle_flags
+        tg = self.targets[t]
+        key = (self.variant, self.flag)
+        if key not in tg.world:
+            with oracle_flags(self.lib, self.flag):
+                tg.world[key] = R.world_arrays(self.lib, tg.vertices, tg.model, tg.normal_matrix)
+        return tg.world[key]
+
+    def cast(self, origins, directions):
+        """per target: (found, distance, point, normal) over the rays"""
+        out = []
+        for t, tg in enumerate(self.targets):
+            P, N = self.arrays(t)
+            out.append(cast_many(origins, directions, P, N, tg.indices, self.order, self.fused))
+        return out
+
+    def lerp(self, a, b, t):
+        """float.Lerp: a * (1 - t) + b * t, the sum fused in the "fma" builds."""
+        one_minus = F32(1.0) - t
+        return F32(np.asarray(R.fma32(a, one_minus, b * t)).reshape(-1)[0]) if self.lerp_fused else a * one_minus + b * t
+
+
+# ============================================================================ the restatement
+def cs_max(a, b):
+    """MathF.Max"""
+    if a != b:
+        return (a if b < a else b) if not np.isnan(a) else a
+    return a if np.signbit(b) else b
+
+
+def cs_min(a, b):
+    """MathF.Min"""
+    if a != b:
+        return (a if a < b else b) if not np.isnan(a) else a
+    return a if np.signbit(a) else b
+
+
+def length(w, v):
+    return np.sqrt(R.dot3v(v, v, w.order))
+
+
+def project_on_plane(w, vector, normal, mut=()):
+    """:142-155"""
+    n = normal
+    if "project_dot3v" in mut:
+        len_sqr, dot = R.dot3v(n, n, w.order), R.dot3v(vector, n, w.order)
+    else:
+        len_sqr = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]
+    if len_sqr < F32(1e-6):
+        return vector.copy()
+    if "project_dot3v" not in mut:
+        dot = (vector[0] * n[0] + vector[1] * n[1]) + vector[2] * n[2]
+    return (vector - (dot * n) / len_sqr).astype(F32)
+
+
+OFFSETS = [(0, 0, 0), (-1, 0, 0), (1, 0, 0), (0, 0, -1), (0, 0, 1), (-1, 0, -1), (-1, 0, 1), (1, 0, -1), (1, 0, 1)]      # :236-247
+
+
+def check_plane(w, p, pos, direction, velocity, dt, mut=()):
+    """:228-306 -> (anyHit, point, normal)"""
+    height, radius = F32(p["height"]), F32(p["radius"])
+    frame_start = pos
+    frame_end = pos + v3(0, velocity[1], 0) * dt                                               # :257
+    max_distance = np.abs(frame_end[1] - frame_start[1]) + height                              # :258
+    origins, dirs, live = [], [], []
+    for off in OFFSETS:
+        off = v3(*off)
+        safe = v3(0, 0, 0) if (off == 0).all() else R.normalize3v(off, w.order) * (radius - F32(0.01))   # :263
+        height_offset = v3(0, 1, 0) * F32(direction) * ((height / F32(2)) - F32(0.01))         # :264
+        ray_start = frame_start + safe - height_offset                                         # :266
+        ray_end = frame_end + safe + height_offset
+        ray_dir = ray_end - ray_start
+        live.append(not (R.dot3v(ray_dir, ray_dir, w.order) < F32(0.0001)))                    # :270
+        origins.append(ray_start); dirs.append(R.normalize3v(ray_dir, w.order))                # :273
+    hits = w.cast(np.asarray(origins), np.asarray(dirs))
+    best_point, best_normal, best_distance, any_hit = v3(NEG_INF, NEG_INF, NEG_INF), v3(0, 1, 0), R.FLT_MAX, False
+    n_t = len(w.targets)
+    order = [(r, t) for t in range(n_t) for r in range(9)] if "plane_target_major" in mut else [(r, t) for r in range(9) for t in range(n_t)]
+    for r, t in order:
+        found, dist, point, normal = hits[t]
+        if not live[r] or not found[r]:
+            continue
+        inside = dist[r] < max_distance if "plane_lt" in mut else dist[r] <= max_distance      # :285
+        if inside and dist[r] < best_distance:                                                 # :289
+            best_distance, best_point, best_normal, any_hit = dist[r], point[r].copy(), normal[r].copy(), True
+    return any_hit, best_point, best_normal
+
+
+def move_with_slide(w, p, ring, current, desired, step_now, tr, chain, depth=0, mut=()):
+    """:308-393; `step_now` is the ActualStepSize the call reads (:342).  Records attempts and the stop reason in tr."""
+    if depth >= 3:                                                                             # :314
+        tr["chain_stop"][chain] = 4
+        return current
+    tr["chain_attempts"][chain] = depth + 1
+    height, radius = F32(p["height"]), F32(p["radius"]) + F32(0.001)
+    move = desired - current
+    move_distance = length(w, move)
+    direction = R.normalize3v(move, w.order)                                                   # :321
+    half = height * F32(0.5)
+    v_steps, h_rays = ray_counts(p)
+    origins = []
+    for vs in range(v_steps + 1):
+        bottom = -half + step_now                                                              # :342
+        ho = w.lerp(bottom, half, F32(vs) / F32(max(1, v_steps)))
+        for hs in range(h_rays):
+            horizontal = v3(radius * ring[hs][0], 0, radius * ring[hs][1])                     # :349-353
+            origins.append(current + v3(0, ho, 0) + horizontal)                                # :355
+    origins = np.asarray(origins, dtype=F32)
+    hits = w.cast(origins, np.tile(direction, (origins.shape[0], 1)))
+    nearest, hit_normal, collision = move_distance, v3(0, 0, 0), False
+    n_r, n_t = origins.shape[0], len(w.targets)
+    order = [(r, t) for r in range(n_r) for t in range(n_t)] if "slide_ray_major" in mut else [(r, t) for t in range(n_t) for r in range(n_r)]
+    for r, t in order:
+        found, dist, _, normal = hits[t]
+        if found[r] and dist[r] < nearest:                                                     # :362
+            nearest, hit_normal, collision = dist[r], R.normalize3v(normal[r], w.order), True  # :365
+    if not collision:
+        tr["chain_stop"][chain] = 1
+        return desired                                                                         # :376
+    safe = current + direction * (nearest - F32(0.001))                                        # :378
+    remaining = desired - safe
+    alignment = R.dot3v(direction, hit_normal, w.order)
+    if np.abs(alignment) > F32(0.9):
+        tr["chain_stop"][chain] = 2
+        return safe
+    slide = R.cross3v(hit_normal, R.cross3v(remaining, hit_normal, w.fused), w.fused)          # :385
+    if (slide == 0).all():
+        tr["chain_stop"][chain] = 3
+        return safe
+    slide = R.normalize3v(slide, w.order) * length(w, remaining)                               # :389
+    return move_with_slide(w, p, ring, safe, safe + slide, step_now, tr, chain, depth + 1, mut)
+
+
+def update(w, p, s, inp, dt, ring, mut=()):
+    """CharacterController.Update (:50-140) for one controller: (new state, trace)."""
+    with np.errstate(all="ignore"):
+        return _update(w, p, s, inp, F32(dt), np.asarray(ring, dtype=F32).reshape(-1, 2), mut)
+
+
+def _update(w, p, s, inp, dt, ring, mut):
+    s = s.copy()
+    tr = np.zeros((), dtype=CHARACTER_TRACE_DTYPE)
+    pos, vel = s["position"].copy(), s["velocity"].copy()
+    move_speed = F32(p["move_speed"])
+    if s["noclip"]:                                                                            # :52-61
+        d = np.asarray(inp["move"], dtype=F32).copy()
+        mag = length(w, d)
+        if mag > 1:
+            d = d / mag
+        vel = d * move_speed
+        s["velocity"], s["position"] = vel, pos + vel * dt
+        return s, tr
+    move_input = np.asarray(inp["move"], dtype=F32).copy()
+    move_input[1] = 0                                                                          # :63
+    vel = vel + p["gravity"] * dt                                                              # :66
+    cd = F32(s["jump_cooldown"])
+    if cd > 0:
+        cd = cd - dt
+    grounded = bool(s["grounded"])
+    if inp["jump"] and grounded and cd <= 0:                                                   # :75-80
+        vel[1] = F32(p["jump_force"]); grounded = False; cd = F32(0.25)
+    grounded, gp, gn = check_plane(w, p, pos, -1, vel, dt, mut)                                # :83
+    movement = vel * dt
+    move_xz = project_on_plane(w, v3(movement[0], 0, movement[2]), gn, mut)                    # :87
+    ceiling, _, _ = check_plane(w, p, pos, 1, vel, dt, mut)                                    # :90
+    tr["ground_found"], tr["ceiling_found"], tr["ground_point"], tr["ground_normal"] = grounded, ceiling, gp, gn
+    step = F32(s["actual_step_size"])
+    if grounded and not (gp[0] == NEG_INF and gp[1] == NEG_INF and gp[2] == NEG_INF) and cd <= 0:      # :93
+        new_pos = v3(pos[0], gp[1] + F32(p["height"]) * F32(0.5), pos[2])
+        pos = move_with_slide(w, p, ring, pos, new_pos, F32(p["step_size"]) if "chain1_new_step" in mut else step, tr, 0, 0, mut)   # :96
+        if vel[1] < 0:
+            vel[1] = 0
+        step = F32(p["step_size"])                                                             # :103
+    else:
+        step = F32(0)
+    if ceiling and vel[1] > 0:                                                                 # :111-115
+        vel[1] = 0; cd = F32(0)
+    pos = move_with_slide(w, p, ring, pos, pos + move_xz, step, tr, 1, 0, mut)                 # :118
+    pos = pos + v3(0, vel[1], 0) * dt                                                          # :121
+    wish = project_on_plane(w, move_input, gn, mut)                                            # :124
+    wish_speed = length(w, wish)
+    if wish_speed > 1:
+        wish = wish / wish_speed
+    wish_speed = wish_speed * move_speed
+    if grounded:
+        hv = v3(vel[0], 0, vel[2])                                                             # ApplyFriction, :157-171
+        speed = length(w, hv)
+        if speed < F32(0.1):
+            vel = v3(0, vel[1], 0)
+        else:
+            drop = speed * F32(p["ground_friction"]) * dt
+            scale = cs_max(speed - drop, F32(0)) / speed
+            vel = v3(vel[0] * scale, vel[1], vel[2] * scale)
+        current = R.dot3v(v3(vel[0], 0, vel[2]), wish, w.order)                                # GroundAccelerate, :173-182
+        add = wish_speed - current
+        if not add <= 0:
+            accel = cs_min(F32(p["ground_acceleration"]) * wish_speed * dt, add)
+            vel = vel + v3(wish[0] * accel, 0, wish[2] * accel)
+    else:
+        hv = v3(vel[0], 0, vel[2])                                                             # AirAccelerate, :184-203
+        add = wish_speed - R.dot3v(hv, wish, w.order)
+        if not add <= 0:
+            accel = cs_min(F32(p["air_acceleration"]) * wish_speed * dt, add)
+            projected = hv + wish * accel
+            if length(w, projected) > F32(p["max_air_speed"]):
+                projected = R.normalize3v(projected, w.order) * F32(p["max_air_speed"])
+                vel = v3(projected[0], vel[1], projected[2])
+            else:
+                vel = vel + v3(wish[0] * accel, 0, wish[2] * accel)
+        if not R.dot3v(wish, wish, w.order) < F32(0.001):                                      # AirControlFunc, :216-226
+            if not length(w, v3(vel[0], 0, vel[2])) < F32(0.1):
+                k = F32(p["air_control"]) * dt
+                vel = vel + v3(wish[0] * k, 0, wish[2] * k)
+        hv = v3(vel[0], 0, vel[2])                                                             # ClampAirSpeed, :205-214
+        if length(w, hv) > F32(p["max_air_speed"]):
+            hv = R.normalize3v(hv, w.order) * F32(p["max_air_speed"])
+            vel = v3(hv[0], vel[1], hv[2])
+    s["position"], s["velocity"], s["jump_cooldown"], s["actual_step_size"] = pos, vel, cd, step
+    s["grounded"], s["ceiling"] = int(grounded), int(ceiling)
+    return s, tr
+
+
+# ============================================================================ scenes
+def quad(origin, a, b, normal):
+    """Two triangles (0, 1, 2), (0, 2, 3) over origin, +a, +a+b, +b: the front face looks along a x b; every vertex carries `normal`."""
+    o, a, b = (np.asarray(x, dtype=np.float64) for x in (origin, a, b))
+    pos = [o, o + a, o + a + b, o + b]
+    return R.Target(R.make_vertices(pos, [normal] * 4), [0, 1, 2, 0, 2, 3])
+
+
+def floor(y=0.0, x0=-8.0, x1=8.0, z0=-8.0, z1=8.0, normal=(0, 1, 0)):
+    return quad((x0, y, z0), (0, 0, z1 - z0), (x1 - x0, 0, 0), normal)
+
+
+def ceiling_quad(y, x0=-8.0, x1=8.0, z0=-8.0, z1=8.0, normal=(0, -1, 0)):
+    return quad((x0, y, z0), (x1 - x0, 0, 0), (0, 0, z1 - z0), normal)
+
+
+def wall(centre, n, length=8.0, y0=-2.0, y1=4.0, normal=None, along=None):
+    """A vertical wall through `centre` whose front face looks along n = (nx, 0, nz); `along` = (t0, t1) limits it along its tangent
+    (-nz, 0, nx) instead of +-length / 2."""
+    nx, nz = float(n[0]), float(n[2])
+    t = np.array([-nz, 0.0, nx])
+    t0, t1 = along if along is not None else (-length / 2, length / 2)
+    c = np.asarray(centre, dtype=np.float64)
+    o = np.array([c[0], y0, c[2]]) + t * t0
+    return quad(o, (0, y1 - y0, 0), t * (t1 - t0), normal if normal is not None else (nx, 0, nz))
+
+
+def symmetric_ring(n):
+    """n (cos, sin) pairs at the angles (h + 1/2) * 2 pi / n, made EXACTLY symmetric: entry n-1-h is entry h with the sine negated.
+    A caller's table (the call takes any): no ray lies on the axis, and the rays come in pairs of equal cosine."""
+    out = np.zeros((n, 2), dtype=F32)
+    for h in range((n + 1) // 2):
+        a = (h + 0.5) * 2 * np.pi / n
+        out[h] = np.cos(a), np.sin(a)
+        out[n - 1 - h] = out[h][0], -out[h][1]
+    return out
+
+
+@dataclasses.dataclass
+class Case:
+    name: str
+    targets: list
+    start: np.ndarray                    # CHARACTER_DTYPE
+    inputs: list                         # per step: (move, jump)
+    dt: float = 1.0 / 60.0
+    p: np.ndarray = dataclasses.field(default_factory=params)
+    ring: np.ndarray = None
+
+    def __post_init__(self):
+        if self.ring is None:
+            self.ring = CharacterController.Ring(ray_counts(self.p)[1])
+
+    def input(self, k):
+        i = np.zeros((), dtype=CHARACTER_INPUT_DTYPE)
+        i["move"], i["jump"] = self.inputs[k][0], int(self.inputs[k][1])
+        return i
+
+
+STILL = ((0, 0, 0), False)
+X_WALL = lambda: wall((1, 0, 0), (-1, 0, 0))                                # noqa: E731  the plane x = 1, looking at -x
+
+
+def corner_targets():
+    """x = 1 looking at -x; an oblique wall looking along (-0.6, 0, -0.8); z = 1.05 looking at -z: a run into the first slides into
+    the second, then into the third."""
+    return [floor(), X_WALL(), wall((0.85, 0, 0.95), (-0.6, 0, -0.8), length=3.0), wall((0.5, 0, 0.95), (0, 0, -1), length=6.0)]
+
+
+def host_cases():
+    cs = []
+    cs.append(Case("rest_on_floor", [floor()], state((0, 0.26, 0), (0, -1, 0)), [STILL] * 3))
+    cs.append(Case("free_fall", [floor(-100.0)], state((0, 5, 0)), [((1, 0, 0), False)] * 3))
+    cs.append(Case("jump_and_cooldown", [floor()], state((0, 0.25, 0), grounded=1, step=0.3), [(((0, 0, 0)), True)] * 4, dt=0.1))
+    cs.append(Case("ceiling_stops_a_rise", [ceiling_quad(1.0)], state((0, 0.72, 0), (0, 3, 0), cooldown=0.2), [STILL] * 3))
+    cs.append(Case("noclip", [floor()], state((0, 0.1, 0), noclip=1), [((3, 4, 0), False), ((0.3, 0.4, 0), True), ((0, 0, 0), False)]))
+    cs.append(Case("wall_square_on", [floor(), X_WALL()], state((0.83, 0.25, 0), (3, 0, 0), grounded=1, step=0.3), [((1, 0, 0), False)] * 3))
+    cs.append(Case("wall_at_45_degrees", [floor(), X_WALL()], state((0.83, 0.25, 0), (2, 0, 2), grounded=1, step=0.3), [((1, 0, 1), False)] * 4))
+    cs.append(Case("corner", corner_targets(), state((0.80, 0.25, 0.55), (9, 0, 5), grounded=1, step=0.3), [((1, 0, 0.5), False)] * 4, dt=0.05))
+    cs.append(Case("zero_move_in_the_air", [floor(-100.0)], state((0, 5, 0)), [STILL] * 3, p=params(gravity=(0, 0, 0))))
+    cs.append(Case("tilted_ground_normal", [floor(normal=(0.18, 0.9, 0.4))], state((0, 0.25, 0), (1.5, 0, 0.7), grounded=1, step=0.3),
+                   [((0.6, 0, 0.3), False)] * 3))
+    cs.append(Case("friction_below_a_tenth", [floor()], state((0, 0.25, 0), (0.05, 0, 0.02), grounded=1, step=0.3), [STILL] * 3))
+    cs.append(Case("air_speed_clamp", [floor(-100.0)], state((0, 5, 0), (10, 0, 2)), [((1, 0, 0), False)] * 3))
+    big = 16777216.0                                                        # 2^24: one ULP is 2
+    cs.append(Case("slide_swallowed_by_rounding", [wall((big + 2, 0, 0), (-0.6, 0, -0.8), length=10.0)], state((big, 1, 0), (120, 0, 0)),
+                   [STILL] * 3, p=params(gravity=(0, 0, 0))))
+    slope = quad((0.8, 1.02, -1.0), (0, 0, 2.0), (-1.6, -1.2, 0), (0.6, -0.8, 0))          # through (0, 0.42, 0), looking down and along +x
+    cs.append(Case("snap_slides_under_a_slope", [floor(), slope, wall((0.2, 0, 0), (-1, 0, 0))], state((0, 0.1, 0)), [STILL] * 3))
+    cs.append(Case("sunk_below_a_ledge", [floor(), ceiling_quad(0.2, 0.1, 0.3, -0.1, 0.1)], state((0, 0.1, 0)), [STILL] * 3))
+    return cs
+
+
+def slide_tie_case():
+    """The plane x = 1 as two halves that are two targets: z < 0 listed FIRST, with a normal that lets the move slide, z > 0 second,
+    with one that stops it (|alignment| > 0.9).  The ring is exactly symmetric: ray 0 (sine > 0) reaches the z > 0 half and ray
+    n - 1 the z < 0 half at equal distances, the nearest of all.  Targets outer: the first target -- the z < 0 half -- wins and the
+    move slides; rays outer would let ray 0 win, the z > 0 half, and stop (stop 2)."""
+    neg = wall((1, 0, 0), (-1, 0, 0), along=(0.0, 4.0), normal=(-0.6, 0, -0.8))      # tangent (0, 0, -1): along 0..4 is z in [-4, 0]
+    pos = wall((1, 0, 0), (-1, 0, 0), along=(-4.0, 0.0), normal=(-1, 0, 0))          # z in [0, 4]
+    return Case("slide_tie", [neg, pos], state((0.83, 0.25, 0), (3, 0, 0), grounded=0, step=0.0), [STILL] * 3,
+                p=params(gravity=(0, 0, 0)), ring=symmetric_ring(18))
+
+
+def plane_tie_case():
+    """Two floor pieces at y = 0 with different normals, x > 1/16 listed first and x < -1/16 second, nothing under the middle:
+    offset 1 (-x) reaches only the second piece, offset 2 (+x) only the first, at equal distances.  Rays outer: offset 1 comes first,
+    the SECOND target's normal is the ground normal; targets outer would take the first target's."""
+    right = floor(0.0, 0.0625, 8.0, -8.0, 8.0, normal=(0.3, 0.9, 0.1))
+    left = floor(0.0, -8.0, -0.0625, -8.0, 8.0, normal=(-0.2, 0.9, 0.3))
+    return Case("plane_tie", [right, left], state((0, 0.25, 0), (1.5, 0, 0.5), grounded=1, step=0.3), [STILL] * 3)
+
+
+def max_distance_case(w_of):
+    """A floor hit at hitDistance == maxDistance exactly (gravity 0, no vertical velocity: maxDistance = Height): the position is
+    searched ULP by ULP around Height - (Height / 2 - 0.01).  w_of(targets) -> World."""
+    p = params(gravity=(0, 0, 0), height=1.0)
+    targets = [floor()]
+    w = w_of(targets)
+    y = F32(1.0) - (F32(1.0) / F32(2) - F32(0.01))
+    for _ in range(64):
+        s = state((0, y, 0))
+        any_hit, gp, _ = check_plane(w, p, s["position"], -1, s["velocity"], F32(1 / 60))
+        if any_hit and not check_plane(w, p, s["position"], -1, s["velocity"], F32(1 / 60), ("plane_lt",))[0]:
+            return Case("hit_at_max_distance", targets, s, [STILL] * 3, p=p)
+        y = np.nextafter(y, F32(0))                                          # (the start lies at or above it: walk down)
+    raise AssertionError("no position puts the floor at exactly maxDistance")
+
+
+def batch_case(n, n_targets=3):
+    """n controllers in one call: one floor, or floor + x wall + oblique wall + z wall under models of their own (n_targets 1 / 3
+    / 4); near the corner some run into it (chain 2 goes on to later attempts), the far ones end chain 2 at its first attempt,
+    every fourth is in the air, and controller 1 (if any) is noclip."""
+    rng = np.random.default_rng(40 + n)
+    base = corner_targets()[:max(n_targets, 1)]
+    models = [hm.identity(), hm.create_translation(0.0, 0.0, 0.0), hm.multiply(hm.create_rotation_y(0.0), hm.create_translation(0.0, 0.5, 0.0)),
+              hm.create_translation(0.0, -0.25, 0.0)]
+    targets = [R.Target(t.vertices, t.indices, np.asarray(m, dtype=F32)) for t, m in zip(base, models)]
+    states = np.zeros(n, dtype=CHARACTER_DTYPE)
+    inputs = np.zeros(n, dtype=CHARACTER_INPUT_DTYPE)
+    for i in range(n):
+        far = i % 3 == 2
+        pos = (-3.0 + rng.uniform(-1, 1), 0.25 if i % 4 else 0.6, rng.uniform(-2, 0)) if far else \
+            (0.80 - 0.02 * rng.uniform(0, 1), 0.25, 0.55 + 0.05 * rng.uniform(-1, 1))
+        states[i] = state(pos, rng.uniform(-2, 2, 3) if far else (9, 0, 5), grounded=int(i % 2 == 0), step=0.3 if i % 2 == 0 else 0.03,
+                          noclip=int(i == 1))
+        inputs[i]["move"], inputs[i]["jump"] = rng.uniform(-1, 1, 3), int(i % 5 == 0)
+    return targets, states, inputs
+
+
+def chain1_batch():
+    """Five controllers in the scene of snap_slides_under_a_slope, in one call: 0 and 3 sunk under the slope (chain 1 slides along it,
+    then up the wall: three attempts, stop 4), 1 noclip, 2 standing clear of it a little above the floor (chain 1 ends at its first
+    attempt), 4 under the slope further along z and away from the wall (two attempts).  -> (targets, states, inputs)"""
+    case = {c.name: c for c in host_cases()}["snap_slides_under_a_slope"]
+    states = np.zeros(5, dtype=CHARACTER_DTYPE)
+    inputs = np.zeros(5, dtype=CHARACTER_INPUT_DTYPE)
+    states[0] = state((0, 0.1, 0))
+    states[1] = state((0, 0.1, 0), noclip=1)
+    states[2] = state((-3.0, 0.26, 0.5), (1, -1, 0))
+    states[3] = state((0.01, 0.12, 0.3), (0.5, 0, 0.5), grounded=1, step=0.3)
+    states[4] = state((-0.15, 0.1, -0.5), (0, 0, -1))
+    inputs["move"] = [(0, 0, 0), (1, 0, 0), (1, 0, 0), (0, 0, 1), (-1, 0, 0)]
+    return case.targets, states, inputs
+
+
+def run_case(w, case, mut=()):
+    """[(state, trace)] after every step of `case` under World w."""
+    s, out = case.start, []
+    for k in range(len(case.inputs)):
+        s, t = update(w, case.p, s, case.input(k), case.dt, case.ring, mut)
+        out.append((s, t))
+    return out
+
+
+def run_batch(w, p, states, inputs, dt, ring, steps):
+    """[(states, traces)] after every step for a batch sharing p and ring."""
+    out, cur = [], states.copy()
+    for _ in range(steps):
+        nxt, trs = cur.copy(), np.zeros(cur.shape[0], dtype=CHARACTER_TRACE_DTYPE)
+        for i in range(cur.shape[0]):
+            nxt[i], trs[i] = update(w, p, cur[i], inputs[i], dt, ring)
+        out.append((nxt, trs)); cur = nxt
+    return out
+
+
+def dust2_batch():
+    """Two controllers over the 11 meshes of dust2 (identity matrices), started 0.6 above the floor (y = 0) at the two capsule positions
+    of raycast_cases.dust2_case that have a floor under them (its positions 2 and 5, default_rng(5)), each pushed at 8 m/s toward
+    geometry: position 2 toward the wall 1.55 away at 3 pi / 8, position 5 along 0.  dt = 0.05, six steps: both fall for three steps,
+    land, and run on.  -> (targets, states, inputs, dt)"""
+    meshes = R.dust2_meshes()
+    allp = np.concatenate([v["position"] for v, _ in meshes]).astype(np.float64)
+    med, ext = np.median(allp, axis=0), allp.max(axis=0) - allp.min(axis=0)
+    rng = np.random.default_rng(5)
+    spots = []
+    for _ in range(6):
+        spots.append(med + rng.uniform(-0.3, 0.3, 3) * ext)
+        rng.uniform(0, 2 * np.pi); rng.uniform(-0.2, 0.2)
+    I = hm.identity()
+    targets = [R.Target(v, i, I, I.copy()) for v, i in meshes]
+    states = np.zeros(2, dtype=CHARACTER_DTYPE)
+    inputs = np.zeros(2, dtype=CHARACTER_INPUT_DTYPE)
+    for k, (spot, angle) in enumerate(((spots[2], 3 * np.pi / 8), (spots[5], 0.0))):
+        d = (np.cos(angle), 0.0, np.sin(angle))
+        states[k] = state((spot[0], 0.6, spot[2]), tuple(8.0 * c for c in d))
+        inputs[k]["move"] = d
+    return targets, states, inputs, 0.05
+
+
+def numerics_cases():
+    """The 45-degree wall and the corner with what makes every numerics switch matter: a capsule of Height 1.0 (verticalSteps = 3, so
+    float.Lerp runs at 1/3 and 2/3) and the walls under a model that leans them (rotations of 0.05 about Y and 0.03 about X: Transform
+    does work, the normals and edges have three components).  The floor stays flat."""
+    lean = hm.multiply(hm.create_rotation_y(0.05), hm.create_rotation_x(0.03)).astype(F32)
+    out = []
+    for c in host_cases():
+        if c.name not in ("wall_at_45_degrees", "corner"):
+            continue
+        targets = [c.targets[0]] + [R.Target(t.vertices, t.indices, lean) for t in c.targets[1:]]
+        start = c.start.copy()
+        start["position"] = (float(start["position"][0]) - 0.08, 0.5, float(start["position"][2]) - 0.05)
+        out.append(Case(c.name + "_leaning", targets, start, c.inputs, c.dt, params(height=1.0)))
+    return out
