@@ -92,7 +92,9 @@ def test_blend_none_early_out_textured(device):
 
 @pytest.mark.parametrize("layers", [3, 64, 65, 200, 2500])
 def test_stacked_translucent_order(device, layers):
-    """Equal-depth translucent layers: the result depends on submission order (>= ties, alpha blend)."""
+    """Equal-depth translucent layers: the result depends on submission order (>= ties, alpha blend).  Through blending this sees
+    the TAIL of the order only -- a few dozen layers at alpha 0.2-0.9 push the earlier ones below one ULP --; inversions, lost and
+    duplicated pairs anywhere in a list are tests/test_gpu_front_end.py's."""
     run_both(device, scenes.stacked_scene(layers=layers))
 
 
