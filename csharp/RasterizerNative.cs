@@ -194,6 +194,11 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_present_wait(IntPtr ctx, ulong ticket);
         [DllImport(Lib)] public static extern int swr_flatten_rgb_device(IntPtr ctx, IntPtr deviceRgb);
         [DllImport(Lib)] public static extern int swr_flatten_rgb_device_async(IntPtr ctx, IntPtr deviceRgb);
+        [DllImport(Lib)] public static extern int swr_resolved_size(IntPtr ctx, int kx, int ky, out int outWidth, out int outRows);
+        [DllImport(Lib)] public static extern int swr_readback_rgb_resolved(IntPtr ctx, int kx, int ky, Vector3* rgb);
+        [DllImport(Lib)] public static extern int swr_present_rgb_resolved_async(IntPtr ctx, int kx, int ky, Vector3* rgb, out ulong ticket);
+        [DllImport(Lib)] public static extern int swr_resolve_rgb_device(IntPtr ctx, int kx, int ky, IntPtr deviceRgb);
+        [DllImport(Lib)] public static extern int swr_resolve_rgb_device_async(IntPtr ctx, int kx, int ky, IntPtr deviceRgb);
         [DllImport(Lib)] public static extern int swr_replay_count(IntPtr ctx, out ulong replays);
         [DllImport(Lib)] public static extern int swr_sync_count(IntPtr ctx, out ulong syncs);
         [DllImport(Lib)] public static extern int swr_host_register(IntPtr ctx, void* ptr, nuint bytes);
@@ -752,7 +757,17 @@ namespace SoftwareRenderer
     //   OnRender               -> MainWindowNative.Present(flatColorBuffer) instead of the Vector4 -> Vector3 loop (:234-240)
     public static unsafe class MainWindowNative
     {
-        public static void Resize(int renderWidth, int renderHeight) => SwrContext.Check(Native.swr_resize(SwrContext.Handle, renderWidth, renderHeight));
+        /// Supersampling (build-defined; the reference's RenderScale stops at 1, MainWindow.cs:93,313-315): 1, 2, 4 or 8 samples per
+        /// window-scale pixel in each direction.  Resize then allocates window x RenderScale x SuperSample in HBM, the draws render
+        /// into that, and Present / PresentAsync deliver window x RenderScale Vector3s, box-filtered on the GPU (swr_*_resolved):
+        /// the host's arrays, its PCIe traffic and its GL texture keep the size they have today.  Set it before Resize.
+        /// (Like the rest of this file: written by reading, not compiled.)
+        public static int SuperSample { get; set; } = 1;
+        public static void Resize(int renderWidth, int renderHeight)
+        {
+            if (SuperSample != 1 && SuperSample != 2 && SuperSample != 4 && SuperSample != 8) throw new ArgumentException("SuperSample must be 1, 2, 4 or 8");
+            SwrContext.Check(Native.swr_resize(SwrContext.Handle, renderWidth * SuperSample, renderHeight * SuperSample));
+        }
         public static void SetPixel(int x, int y, Vector4 color) => SwrContext.Check(Native.swr_set_pixel(SwrContext.Handle, x, y, &color));
         public static Vector4 GetPixel(int x, int y) { Vector4 c; SwrContext.Check(Native.swr_get_pixel(SwrContext.Handle, x, y, &c)); return c; }
         public static void ClearColorBuffer(Vector4 clearColor) => SwrContext.Check(Native.swr_clear_color(SwrContext.Handle, &clearColor));
@@ -764,11 +779,14 @@ namespace SoftwareRenderer
         /// flattened on the GPU).  Register a long-lived pinned array once with Pin() and the copy runs at PCIe rate.
         public static void Present(Vector3[] flatColorBuffer)
         {
-            fixed (Vector3* p = flatColorBuffer) SwrContext.Check(Native.swr_readback_rgb(SwrContext.Handle, p));
+            fixed (Vector3* p = flatColorBuffer)
+                SwrContext.Check(SuperSample == 1 ? Native.swr_readback_rgb(SwrContext.Handle, p)
+                                                  : Native.swr_readback_rgb_resolved(SwrContext.Handle, SuperSample, SuperSample, p));
         }
         /// Double-buffered present for a host that keeps MainWindow.OnRender (MainWindow.cs:226-263): two PINNED flat buffers
         /// alternate; PresentAsync(i) starts frame i's flatten + copy and returns the buffer of frame i - 1, which has finished
-        /// crossing PCIe while frame i was being rendered (null on the very first call).  Per frame the host then pays
+        /// crossing PCIe while frame i was being rendered (null on the very first call).  width x height is the WINDOW-scale size
+        /// passed to Resize (what the arrays hold under any SuperSample).  Per frame the host then pays
         /// max(render, copy) instead of render + copy: at 4096 x 4096 the copy is 4.6 ms and the render 0.7 ms (DESIGN.md section 5).
         static readonly Vector3[]?[] presentBuffers = new Vector3[]?[2];
         static readonly GCHandle[] presentPins = new GCHandle[2];
@@ -785,7 +803,9 @@ namespace SoftwareRenderer
                 presentBuffers[cur] = new Vector3[n];
                 presentPins[cur] = Pin(presentBuffers[cur]!, (nuint)n * 12);
             }
-            SwrContext.Check(Native.swr_present_rgb_async(SwrContext.Handle, (Vector3*)presentPins[cur].AddrOfPinnedObject(), out presentTickets[cur]));
+            Vector3* dst = (Vector3*)presentPins[cur].AddrOfPinnedObject();
+            SwrContext.Check(SuperSample == 1 ? Native.swr_present_rgb_async(SwrContext.Handle, dst, out presentTickets[cur])
+                                              : Native.swr_present_rgb_resolved_async(SwrContext.Handle, SuperSample, SuperSample, dst, out presentTickets[cur]));
             if (presentTickets[prev] == 0) return null;
             int rc = Native.swr_present_wait(SwrContext.Handle, presentTickets[prev]);
             presentTickets[prev] = 0;

@@ -197,6 +197,25 @@ int  swr_flatten_rgb_device(swr_context* ctx, float* d_rgb);
  * a batch had not fitted its pair buffers, was replayed by that swr_sync, and payloads flattened in between are stale
  * (flatten and send them again).  Steady-state frames never replay. */
 int  swr_flatten_rgb_device_async(swr_context* ctx, float* d_rgb);
+/* SUPERSAMPLED PRESENT (build-defined; the reference's RenderScale stops at 1, MainWindow.cs:93,313-315): render at kx x ky times the
+ * window, average every kx x ky block of the band's colour plane on the GPU and deliver window-sized packed RGB floats -- the bytes
+ * that leave the device fall by kx * ky.  kx, ky in {1, 2, 4, 8}, chosen independently; the render target's width must be a multiple
+ * of kx and its height of ky (then every band's and stripe's rows are a multiple of ky and the concatenated band payloads are the
+ * resolved frame).  Per output pixel and channel, in float32: the kx samples of each row summed as a balanced pairwise tree left to
+ * right, the ky row sums by the same tree top to bottom, times the float 1 / (kx * ky); alpha is dropped; (1, 1) gives the
+ * flatten's values (csrc/swr_resolve.hip.h).  Bad factors, a size that does not divide and NULL pointers:
+ * SWR_ERR_INVALID_ARG, nothing written, no ticket issued.  A zero-size target: SWR_OK, nothing written. */
+/* host only: the payload's size under the size and band in force, out_width = W / kx, out_rows = band rows / ky */
+int  swr_resolved_size(swr_context* ctx, int kx, int ky, int* out_width, int* out_rows);
+/* as swr_readback_rgb: flush, validate, resolve, copy out_rows x out_width x 3 floats into rgb, wait */
+int  swr_readback_rgb_resolved(swr_context* ctx, int kx, int ky, float* rgb);
+/* as swr_present_rgb_async, and sharing its two slots, tickets, staging buffers, staleness rule and back-pressure: never waits for
+ * the stream; swr_present_wait serves both kinds of ticket, and the two kinds may alternate */
+int  swr_present_rgb_resolved_async(swr_context* ctx, int kx, int ky, float* rgb, uint64_t* ticket);
+/* as swr_flatten_rgb_device (validates first) and swr_flatten_rgb_device_async (does not wait), into out_rows x out_width x 3
+ * floats of caller DEVICE memory */
+int  swr_resolve_rgb_device(swr_context* ctx, int kx, int ky, float* d_rgb);
+int  swr_resolve_rgb_device_async(swr_context* ctx, int kx, int ky, float* d_rgb);
 int  swr_replay_count(swr_context* ctx, uint64_t* out);
 /* how many times an entry point has made the calling thread wait for the stream so far (hipStreamSynchronize): lets a frame
  * loop assert that its steady state never blocks (swr_bind_framebuffer, swr_flush, swr_flatten_rgb_device_async, and

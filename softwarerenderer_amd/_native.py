@@ -110,6 +110,7 @@ EXPORTS = [
     "swr_program_create", "swr_program_destroy", "swr_program_set_constants", "swr_program_validate",
     "swr_program_create_vf", "swr_program_validate_vf",
     "swr_raycast", "swr_raycast_nearest", "swr_character_ray_counts", "swr_character_update",
+    "swr_resolved_size", "swr_readback_rgb_resolved", "swr_present_rgb_resolved_async", "swr_resolve_rgb_device", "swr_resolve_rgb_device_async",
 ]
 
 _libs = {}
@@ -199,6 +200,11 @@ def load(name: str = None) -> C.CDLL:
         "swr_raycast_nearest": (I, [P, P, I, P, I, I, P]),
         "swr_character_ray_counts": (I, [P, C.POINTER(I), C.POINTER(I)]),
         "swr_character_update": (I, [P, P, P, P, I, F, P, I, P, I, I, P]),
+        "swr_resolved_size": (I, [P, I, I, C.POINTER(I), C.POINTER(I)]),
+        "swr_readback_rgb_resolved": (I, [P, I, I, P]),
+        "swr_present_rgb_resolved_async": (I, [P, I, I, P, C.POINTER(C.c_uint64)]),
+        "swr_resolve_rgb_device": (I, [P, I, I, P]),
+        "swr_resolve_rgb_device_async": (I, [P, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -42,6 +42,7 @@
 #include "swr_cull.hip.h"
 #include "swr_raycast.hip.h"
 #include "swr_character.hip.h"
+#include "swr_resolve.hip.h"
 
 using namespace swr;
 
@@ -61,16 +62,110 @@ int launch_flatten(swr_context* c, float* d_rgb, size_t n) {
     return SWR_OK;
 }
 
-// swr_flatten_rgb_device [_async].  Stream order puts the flatten after the frame's kernels; a batch that has to be replayed (optimistic
-// flush) is replayed by the caller's swr_sync BEFORE the result is consumed -- and then the flatten must run again, which sync does not
-// know about: so `validate` first (cheap when nothing overflowed: one pinned-flag read after the stream drains)
-int flatten_device(swr_context* c, float* d_rgb, bool validate) {
+// What a present call delivers: the flatten (k_flatten_rgb, one RGB triple per band pixel) or the kx x ky box-filter resolve
+// (k_resolve_rgb, one triple per kx x ky block of band pixels).  Every present shape below is defined once over this.
+struct Payload { bool resolve; int kx, ky; };
+constexpr Payload FLATTEN = {false, 1, 1};
+
+bool resolve_factor_ok(int k) { return k == 1 || k == 2 || k == 4 || k == 8; }
+// a zero-size target resolves to nothing under any factor pair; otherwise the frame must divide (then every band's rows do too:
+// the factors divide the tile, and the last tile row holds H - 16 * (tiles_y - 1) pixel rows)
+int payload_check(swr_context* c, const Payload& p) {
+    if (!p.resolve) return SWR_OK;
+    if (!resolve_factor_ok(p.kx) || !resolve_factor_ok(p.ky)) return fail(c, SWR_ERR_INVALID_ARG, "resolve factors must be 1, 2, 4 or 8");
+    if (c->W <= 0 || c->H <= 0) return SWR_OK;
+    if (c->W % p.kx || c->H % p.ky) return fail(c, SWR_ERR_INVALID_ARG, "the render target's width and height must be multiples of the resolve factors");
+    return SWR_OK;
+}
+int payload_width(const swr_context* c, const Payload& p) { return std::max(0, c->W) / p.kx; }
+int payload_rows(const swr_context* c, const Payload& p) { return band_rows(c) / p.ky; }
+size_t payload_pixels(const swr_context* c, const Payload& p) { return (size_t)payload_width(c, p) * (size_t)payload_rows(c, p); }
+
+using ResolveKernel = void (*)(const float4*, float*, int, int);
+template <int KX> ResolveKernel resolve_kernel_rows(int ky) {
+    return ky == 1 ? k_resolve_rgb<KX, 1> : ky == 2 ? k_resolve_rgb<KX, 2> : ky == 4 ? k_resolve_rgb<KX, 4> : k_resolve_rgb<KX, 8>;
+}
+ResolveKernel resolve_kernel(int kx, int ky) {
+    return kx == 1 ? resolve_kernel_rows<1>(ky) : kx == 2 ? resolve_kernel_rows<2>(ky) : kx == 4 ? resolve_kernel_rows<4>(ky) : resolve_kernel_rows<8>(ky);
+}
+
+// the payload of the band's colour plane in device memory, on the context's stream (checked, and not empty)
+int launch_payload(swr_context* c, const Payload& p, float* d_rgb) {
+    if (!p.resolve) return launch_flatten(c, d_rgb, band_pixels(c));
+    const int ow = payload_width(c, p), orows = payload_rows(c, p);
+    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
+    const int per_block_x = resolve_block_out_x(p.kx);
+    const dim3 grid((ow + per_block_x - 1) / per_block_x, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
+    hipLaunchKernelGGL(resolve_kernel(p.kx, p.ky), grid, block, 0, c->stream, (const float4*)c->color, d_rgb, ow, orows);
+    SWR_HIP(c, hipGetLastError());
+    return SWR_OK;
+}
+
+// swr_flatten_rgb_device / swr_resolve_rgb_device [_async].  Stream order puts the payload kernel after the frame's kernels; a batch that
+// has to be replayed (optimistic flush) is replayed by the caller's swr_sync BEFORE the result is consumed -- and then the kernel must
+// run again, which sync does not know about: so `validate` first (cheap when nothing overflowed: one pinned-flag read after the stream
+// drains)
+int payload_device(swr_context* c, const Payload& p, float* d_rgb, bool validate) {
     if (!d_rgb) return fail(c, SWR_ERR_INVALID_ARG, "d_rgb is null");
-    int rc = flush_locked(c); if (rc) return rc;
-    const size_t n = band_pixels(c);
-    if (!n) return SWR_OK;
+    int rc = payload_check(c, p); if (rc) return rc;
+    if ((rc = flush_locked(c))) return rc;
+    if (!payload_pixels(c, p)) return SWR_OK;
     if (validate && (rc = sync_locked(c))) return rc;
-    return launch_flatten(c, d_rgb, n);
+    return launch_payload(c, p, d_rgb);
+}
+
+// swr_readback_rgb / swr_readback_rgb_resolved: the payload into host memory, between two host syncs
+int payload_readback(swr_context* c, const Payload& p, float* rgb) {
+    if (!rgb) return fail(c, SWR_ERR_INVALID_ARG, "rgb is null");
+    int rc = payload_check(c, p); if (rc) return rc;
+    if ((rc = flush_and_sync_locked(c))) return rc;
+    const size_t n = payload_pixels(c, p);
+    if (!n) return SWR_OK;
+    if ((rc = ensure(c, c->d_scratch, n * 12))) return rc;
+    if ((rc = launch_payload(c, p, c->d_scratch.as<float>()))) return rc;
+    SWR_HIP(c, hipMemcpyAsync(rgb, c->d_scratch.p, n * 12, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+// swr_present_rgb_async / swr_present_rgb_resolved_async: both kinds share the two slots, the tickets and the staging buffers
+int payload_present(swr_context* c, const Payload& p, float* rgb, uint64_t* ticket) {
+    if (!rgb || !ticket) return fail(c, SWR_ERR_INVALID_ARG, "rgb or ticket is null");
+    int rc = payload_check(c, p); if (rc) return rc;
+    if ((rc = flush_locked(c))) return rc;
+    const size_t n = payload_pixels(c, p);
+    const int slot = (int)(c->next_ticket & 1ull);
+    if (!c->copy_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) {
+        if (!c->present_flat[i]) SWR_HIP(c, hipEventCreateWithFlags(&c->present_flat[i], hipEventDisableTiming));
+        if (!c->present_done[i]) SWR_HIP(c, hipEventCreateWithFlags(&c->present_done[i], hipEventDisableTiming));
+    }
+    // the slot's previous copy (two presents ago) must be over before its staging buffer is overwritten: back-pressure, not
+    // steady-state waiting -- a caller that waits for ticket i before it presents frame i + 2 never blocks here
+    if (c->present_ticket[slot]) {
+        SWR_HIP(c, hipEventSynchronize(c->present_done[slot]));
+        // the ticket is dropped unwaited: if a batch at or before that present poisoned itself, its pixels were stale -- remember it
+        // for the swr_present_wait that may still come (ADVICE r3)
+        bool stale = false;
+        if ((rc = present_is_stale(c, slot, stale))) return rc;
+        if (stale) c->stale_dropped[slot] = c->present_ticket[slot];
+        c->present_ticket[slot] = 0;
+    }
+    if (n) {
+        if (c->present_buf[slot].cap < n * 12) {
+            // growing frees the old block: make sure neither stream still uses it (first frame / after a resize only)
+            SWR_HIP(c, hipStreamSynchronize(c->copy_stream));
+            if ((rc = ensure(c, c->present_buf[slot], n * 12))) return rc;
+        }
+        if ((rc = launch_payload(c, p, c->present_buf[slot].as<float>()))) return rc;
+    }
+    SWR_HIP(c, hipEventRecord(c->present_flat[slot], c->stream));
+    SWR_HIP(c, hipStreamWaitEvent(c->copy_stream, c->present_flat[slot], 0));
+    if (n) SWR_HIP(c, hipMemcpyAsync(rgb, c->present_buf[slot].p, n * 12, hipMemcpyDeviceToHost, c->copy_stream));
+    SWR_HIP(c, hipEventRecord(c->present_done[slot], c->copy_stream));
+    c->present_ticket[slot] = ++c->next_ticket;
+    c->present_seq[slot] = c->next_seq - 1u;
+    *ticket = c->present_ticket[slot];
+    return SWR_OK;
 }
 
 // swr_readback / swr_upload: the band's planes (either may be null) to or from the host, between two host syncs: optimistic batches are
@@ -503,56 +598,22 @@ int swr_sync(swr_context* c) {
 
 int swr_readback(swr_context* c, float* color, float* depth) { SWR_ENTER(c); return planes_transfer(c, color, depth, true); }
 
-int swr_readback_rgb(swr_context* c, float* rgb) {
+int swr_readback_rgb(swr_context* c, float* rgb) { SWR_ENTER(c); return payload_readback(c, FLATTEN, rgb); }
+int swr_readback_rgb_resolved(swr_context* c, int kx, int ky, float* rgb) { SWR_ENTER(c); return payload_readback(c, Payload{true, kx, ky}, rgb); }
+
+int swr_resolved_size(swr_context* c, int kx, int ky, int* out_width, int* out_rows) {
     SWR_ENTER(c);
-    if (!rgb) return fail(c, SWR_ERR_INVALID_ARG, "rgb is null");
-    int rc = flush_and_sync_locked(c); if (rc) return rc;
-    size_t n = band_pixels(c);
-    if (!n) return SWR_OK;
-    if ((rc = ensure(c, c->d_scratch, n * 12))) return rc;
-    if ((rc = launch_flatten(c, c->d_scratch.as<float>(), n))) return rc;
-    SWR_HIP(c, hipMemcpyAsync(rgb, c->d_scratch.p, n * 12, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
+    if (!out_width || !out_rows) return fail(c, SWR_ERR_INVALID_ARG, "out_width or out_rows is null");
+    const Payload p = {true, kx, ky};
+    int rc = payload_check(c, p); if (rc) return rc;
+    *out_width = payload_width(c, p); *out_rows = payload_rows(c, p);
+    return SWR_OK;
 }
 
-int swr_present_rgb_async(swr_context* c, float* rgb, uint64_t* ticket) {
+int swr_present_rgb_async(swr_context* c, float* rgb, uint64_t* ticket) { SWR_ENTER(c); return payload_present(c, FLATTEN, rgb, ticket); }
+int swr_present_rgb_resolved_async(swr_context* c, int kx, int ky, float* rgb, uint64_t* ticket) {
     SWR_ENTER(c);
-    if (!rgb || !ticket) return fail(c, SWR_ERR_INVALID_ARG, "rgb or ticket is null");
-    int rc = flush_locked(c); if (rc) return rc;
-    const size_t n = band_pixels(c);
-    const int slot = (int)(c->next_ticket & 1ull);
-    if (!c->copy_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-        if (!c->present_flat[i]) SWR_HIP(c, hipEventCreateWithFlags(&c->present_flat[i], hipEventDisableTiming));
-        if (!c->present_done[i]) SWR_HIP(c, hipEventCreateWithFlags(&c->present_done[i], hipEventDisableTiming));
-    }
-    // the slot's previous copy (two presents ago) must be over before its staging buffer is overwritten: back-pressure, not
-    // steady-state waiting -- a caller that waits for ticket i before it presents frame i + 2 never blocks here
-    if (c->present_ticket[slot]) {
-        SWR_HIP(c, hipEventSynchronize(c->present_done[slot]));
-        // the ticket is dropped unwaited: if a batch at or before that present poisoned itself, its pixels were stale -- remember it
-        // for the swr_present_wait that may still come (ADVICE r3)
-        bool stale = false;
-        if ((rc = present_is_stale(c, slot, stale))) return rc;
-        if (stale) c->stale_dropped[slot] = c->present_ticket[slot];
-        c->present_ticket[slot] = 0;
-    }
-    if (n) {
-        if (c->present_buf[slot].cap < n * 12) {
-            // growing frees the old block: make sure neither stream still uses it (first frame / after a resize only)
-            SWR_HIP(c, hipStreamSynchronize(c->copy_stream));
-            if ((rc = ensure(c, c->present_buf[slot], n * 12))) return rc;
-        }
-        if ((rc = launch_flatten(c, c->present_buf[slot].as<float>(), n))) return rc;
-    }
-    SWR_HIP(c, hipEventRecord(c->present_flat[slot], c->stream));
-    SWR_HIP(c, hipStreamWaitEvent(c->copy_stream, c->present_flat[slot], 0));
-    if (n) SWR_HIP(c, hipMemcpyAsync(rgb, c->present_buf[slot].p, n * 12, hipMemcpyDeviceToHost, c->copy_stream));
-    SWR_HIP(c, hipEventRecord(c->present_done[slot], c->copy_stream));
-    c->present_ticket[slot] = ++c->next_ticket;
-    c->present_seq[slot] = c->next_seq - 1u;
-    *ticket = c->present_ticket[slot];
-    return SWR_OK;
+    return payload_present(c, Payload{true, kx, ky}, rgb, ticket);
 }
 
 int swr_present_wait(swr_context* c, uint64_t ticket) {
@@ -600,8 +661,10 @@ int swr_host_unregister(swr_context* c, void* ptr) {
     return SWR_OK;
 }
 
-int swr_flatten_rgb_device(swr_context* c, float* d_rgb) { SWR_ENTER(c); return flatten_device(c, d_rgb, true); }
-int swr_flatten_rgb_device_async(swr_context* c, float* d_rgb) { SWR_ENTER(c); return flatten_device(c, d_rgb, false); }
+int swr_flatten_rgb_device(swr_context* c, float* d_rgb) { SWR_ENTER(c); return payload_device(c, FLATTEN, d_rgb, true); }
+int swr_flatten_rgb_device_async(swr_context* c, float* d_rgb) { SWR_ENTER(c); return payload_device(c, FLATTEN, d_rgb, false); }
+int swr_resolve_rgb_device(swr_context* c, int kx, int ky, float* d_rgb) { SWR_ENTER(c); return payload_device(c, Payload{true, kx, ky}, d_rgb, true); }
+int swr_resolve_rgb_device_async(swr_context* c, int kx, int ky, float* d_rgb) { SWR_ENTER(c); return payload_device(c, Payload{true, kx, ky}, d_rgb, false); }
 
 int swr_replay_count(swr_context* c, uint64_t* out) { SWR_ENTER(c); if (!out) return SWR_ERR_INVALID_ARG; *out = c->replays; return SWR_OK; }
 int swr_sync_count(swr_context* c, uint64_t* out) { SWR_ENTER(c); if (!out) return SWR_ERR_INVALID_ARG; *out = c->host_syncs; return SWR_OK; }

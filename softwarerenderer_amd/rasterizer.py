@@ -510,6 +510,54 @@ class MainWindow:
         self._activate()
         self._dev._ck(self._dev._lib.swr_flatten_rgb_device_async(self._dev._ctx, C.c_void_p(device_ptr)))
 
+    def ResolvedSize(self, kx: int, ky: int) -> tuple:
+        """(rows, width) of the supersampled present's payload: band rows / ky and W / kx, the arithmetic of swr_resolved_size
+        restated on the host (as FlatColorBuffer's shape is).  kx, ky in {1, 2, 4, 8}; the window's width must be a multiple of kx
+        and its height of ky -- then every band's and stripe's rows are a multiple of ky."""
+        if kx not in (1, 2, 4, 8) or ky not in (1, 2, 4, 8):
+            raise ValueError("resolve factors must be 1, 2, 4 or 8")
+        w, h = self.RenderWidth, self.RenderHeight
+        if w <= 0 or h <= 0:
+            return 0, 0
+        if w % kx or h % ky:
+            raise ValueError(f"a {w} x {h} window does not divide by the resolve factors ({kx}, {ky})")
+        return self.band_pixel_rows()[1] // ky, w // kx
+
+    def _resolved_out(self, kx, ky, out):
+        shape = self.ResolvedSize(kx, ky) + (3,)
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+        self._activate()
+        return out
+
+    def ResolvedColorBuffer(self, kx: int, ky: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """FlatColorBuffer of a window rendered at kx x ky times its size: every kx x ky block of the band box-filtered on the GPU
+        (swr_readback_rgb_resolved; the arithmetic is in include/swr.h), (rows / ky, W / kx, 3) floats."""
+        out = self._resolved_out(kx, ky, out)
+        if out.size:
+            self._dev._ck(self._dev._lib.swr_readback_rgb_resolved(self._dev._ctx, int(kx), int(ky), out.ctypes.data))
+        return out
+
+    def PresentResolvedAsync(self, out: np.ndarray, kx: int, ky: int) -> int:
+        """PresentAsync with the resolved payload (swr_present_rgb_resolved_async): 1 / (kx * ky) of the bytes cross PCIe.  Shares
+        PresentAsync's two slots; PresentWait serves the ticket."""
+        out = self._resolved_out(kx, ky, out)
+        t = C.c_uint64(0)
+        self._dev._ck(self._dev._lib.swr_present_rgb_resolved_async(self._dev._ctx, int(kx), int(ky), C.c_void_p(out.ctypes.data), C.byref(t)))
+        return int(t.value)
+
+    def ResolveTo(self, device_ptr: int, kx: int, ky: int):
+        """ResolvedColorBuffer into caller-owned DEVICE memory (ResolvedSize x 3 floats); completes with Device.sync()."""
+        self._activate()
+        self._dev._ck(self._dev._lib.swr_resolve_rgb_device(self._dev._ctx, int(kx), int(ky), C.c_void_p(device_ptr)))
+
+    def ResolveToAsync(self, device_ptr: int, kx: int, ky: int):
+        """ResolveTo without the validation sync (swr_resolve_rgb_device_async), as FlattenToAsync."""
+        self._activate()
+        self._dev._ck(self._dev._lib.swr_resolve_rgb_device_async(self._dev._ctx, int(kx), int(ky), C.c_void_p(device_ptr)))
+
     def Upload(self, color=None, depth=None):
         self._activate()
         c = np.ascontiguousarray(color, dtype=np.float32) if color is not None else None
