@@ -199,6 +199,11 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_present_rgb_resolved_async(IntPtr ctx, int kx, int ky, Vector3* rgb, out ulong ticket);
         [DllImport(Lib)] public static extern int swr_resolve_rgb_device(IntPtr ctx, int kx, int ky, IntPtr deviceRgb);
         [DllImport(Lib)] public static extern int swr_resolve_rgb_device_async(IntPtr ctx, int kx, int ky, IntPtr deviceRgb);
+        [DllImport(Lib)] public static extern int swr_present8_size(IntPtr ctx, int kx, int ky, int bpp, out int outWidth, out int outRows, out nuint outBytes);
+        [DllImport(Lib)] public static extern int swr_readback_rgb8(IntPtr ctx, int kx, int ky, int bpp, byte* bytes);
+        [DllImport(Lib)] public static extern int swr_present_rgb8_async(IntPtr ctx, int kx, int ky, int bpp, byte* bytes, out ulong ticket);
+        [DllImport(Lib)] public static extern int swr_resolve_rgb8_device(IntPtr ctx, int kx, int ky, int bpp, IntPtr deviceBytes);
+        [DllImport(Lib)] public static extern int swr_resolve_rgb8_device_async(IntPtr ctx, int kx, int ky, int bpp, IntPtr deviceBytes);
         [DllImport(Lib)] public static extern int swr_replay_count(IntPtr ctx, out ulong replays);
         [DllImport(Lib)] public static extern int swr_sync_count(IntPtr ctx, out ulong syncs);
         [DllImport(Lib)] public static extern int swr_host_register(IntPtr ctx, void* ptr, nuint bytes);
@@ -816,6 +821,45 @@ namespace SoftwareRenderer
             }
             SwrContext.Check(rc);
             return presentBuffers[prev];
+        }
+        /// 8-bit present (build-defined; DESIGN.md section 18): 0 keeps today's Vector3 payload (Present / PresentAsync); 3 or 4 makes
+        /// PresentAsync8 deliver the bytes the window's 8-bit framebuffer would hold anyway -- R, G, B or R, G, B, 255 per
+        /// window-scale pixel, clamped to [0, 1], times 255, rounded to nearest even on the GPU --, a quarter or a third of the bytes.
+        /// Upload them with PixelType.UnsignedByte and PixelFormat.Rgb (after Gl.PixelStore(UnpackAlignment, 1): rows are tightly
+        /// packed) or PixelFormat.Rgba; the texture's internal format can stay Rgba32f (INTEGRATION.md).  Composes with SuperSample.
+        public static int PresentBytes { get; set; } = 0;
+        static readonly byte[]?[] present8Buffers = new byte[]?[2];
+        static readonly GCHandle[] present8Pins = new GCHandle[2];
+        static readonly ulong[] present8Tickets = new ulong[2];
+        static int present8Next;
+        /// PresentAsync with byte payloads: starts frame i's quantise + copy and returns the bytes of frame i - 1 (null on the very
+        /// first call); width x height is the WINDOW-scale size passed to Resize.  Shares the library's two present slots with
+        /// PresentAsync, so a host uses one of the two in its loop.
+        public static byte[]? PresentAsync8(int width, int height)
+        {
+            if (PresentBytes != 3 && PresentBytes != 4) throw new InvalidOperationException("set PresentBytes to 3 or 4 first");
+            int cur = present8Next, prev = present8Next ^ 1;
+            present8Next = prev;
+            int n = Math.Max(width, 0) * Math.Max(height, 0) * PresentBytes;
+            if (present8Buffers[cur] == null || present8Buffers[cur]!.Length != n)
+            {
+                if (present8Buffers[cur] != null) { SwrContext.Check(Native.swr_host_unregister(SwrContext.Handle, (void*)present8Pins[cur].AddrOfPinnedObject())); present8Pins[cur].Free(); }
+                present8Buffers[cur] = new byte[n];
+                present8Pins[cur] = Pin(present8Buffers[cur]!, (nuint)n);
+            }
+            byte* dst = (byte*)present8Pins[cur].AddrOfPinnedObject();
+            SwrContext.Check(Native.swr_present_rgb8_async(SwrContext.Handle, SuperSample, SuperSample, PresentBytes, dst, out present8Tickets[cur]));
+            if (present8Tickets[prev] == 0) return null;
+            int rc = Native.swr_present_wait(SwrContext.Handle, present8Tickets[prev]);
+            present8Tickets[prev] = 0;
+            if (rc == 1)        // SWR_STALE, as in PresentAsync: take that frame synchronously
+            {
+                fixed (byte* p = present8Buffers[prev]!)
+                    SwrContext.Check(Native.swr_readback_rgb8(SwrContext.Handle, SuperSample, SuperSample, PresentBytes, p));
+                return present8Buffers[prev];
+            }
+            SwrContext.Check(rc);
+            return present8Buffers[prev];
         }
         /// Full-precision read-back into the reference's own arrays (tools, screenshots).
         public static void Readback(Vector4[] colorBuffer, float[] depthBuffer)

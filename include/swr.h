@@ -216,6 +216,25 @@ int  swr_present_rgb_resolved_async(swr_context* ctx, int kx, int ky, float* rgb
  * floats of caller DEVICE memory */
 int  swr_resolve_rgb_device(swr_context* ctx, int kx, int ky, float* d_rgb);
 int  swr_resolve_rgb_device_async(swr_context* ctx, int kx, int ky, float* d_rgb);
+/* 8-BIT PRESENT (build-defined): the payload above -- the flatten's R, G, B under kx = ky = 1, otherwise the resolve's -- quantised
+ * on the GPU, so that 3 or 4 bytes per window pixel leave the device instead of 12.  Per channel c, after the resolve's arithmetic
+ * has been rounded to float32: NaN -> 0; c <= 0 -> 0; c >= 1 -> 255; otherwise (uint8) rintf(c * 255.0f), the product rounded to
+ * float32 and ties to even.  No gamma, no dither (the reference has neither: it hands the floats to GL, which clamps and rounds
+ * them to its 8-bit framebuffer; GL prefers round-to-nearest and leaves ties open).  bpp = 3 delivers R, G, B; bpp = 4 delivers
+ * R, G, B, 255.  Rows are tightly packed: out_rows x out_width x bpp contiguous bytes, and the concatenated band payloads are the
+ * frame (csrc/swr_present8.hip.h).  A bpp other than 3 or 4, bad factors, a size that does not divide and NULL
+ * pointers: SWR_ERR_INVALID_ARG, nothing written, no ticket issued.  A zero-size target: SWR_OK, nothing written. */
+/* host only: swr_resolved_size plus out_bytes = out_rows * out_width * bpp */
+int  swr_present8_size(swr_context* ctx, int kx, int ky, int bpp, int* out_width, int* out_rows, size_t* out_bytes);
+/* as swr_readback_rgb_resolved; `out` may have any alignment */
+int  swr_readback_rgb8(swr_context* ctx, int kx, int ky, int bpp, uint8_t* out);
+/* as swr_present_rgb_resolved_async, on the same two slots, tickets and staging buffers: the three kinds of present may alternate
+ * and swr_present_wait serves every ticket; `out` may have any alignment */
+int  swr_present_rgb8_async(swr_context* ctx, int kx, int ky, int bpp, uint8_t* out, uint64_t* ticket);
+/* as swr_resolve_rgb_device (validates first) and its async form (does not wait), into out_bytes of caller DEVICE memory, which
+ * must be 4-byte aligned (the kernel stores whole dwords): SWR_ERR_INVALID_ARG otherwise */
+int  swr_resolve_rgb8_device(swr_context* ctx, int kx, int ky, int bpp, uint8_t* d_out);
+int  swr_resolve_rgb8_device_async(swr_context* ctx, int kx, int ky, int bpp, uint8_t* d_out);
 int  swr_replay_count(swr_context* ctx, uint64_t* out);
 /* how many times an entry point has made the calling thread wait for the stream so far (hipStreamSynchronize): lets a frame
  * loop assert that its steady state never blocks (swr_bind_framebuffer, swr_flush, swr_flatten_rgb_device_async, and

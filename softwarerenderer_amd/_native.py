@@ -111,6 +111,7 @@ EXPORTS = [
     "swr_program_create_vf", "swr_program_validate_vf",
     "swr_raycast", "swr_raycast_nearest", "swr_character_ray_counts", "swr_character_update",
     "swr_resolved_size", "swr_readback_rgb_resolved", "swr_present_rgb_resolved_async", "swr_resolve_rgb_device", "swr_resolve_rgb_device_async",
+    "swr_present8_size", "swr_readback_rgb8", "swr_present_rgb8_async", "swr_resolve_rgb8_device", "swr_resolve_rgb8_device_async",
 ]
 
 _libs = {}
@@ -205,6 +206,11 @@ def load(name: str = None) -> C.CDLL:
         "swr_present_rgb_resolved_async": (I, [P, I, I, P, C.POINTER(C.c_uint64)]),
         "swr_resolve_rgb_device": (I, [P, I, I, P]),
         "swr_resolve_rgb_device_async": (I, [P, I, I, P]),
+        "swr_present8_size": (I, [P, I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_size_t)]),
+        "swr_readback_rgb8": (I, [P, I, I, I, P]),
+        "swr_present_rgb8_async": (I, [P, I, I, I, P, C.POINTER(C.c_uint64)]),
+        "swr_resolve_rgb8_device": (I, [P, I, I, I, P]),
+        "swr_resolve_rgb8_device_async": (I, [P, I, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -43,6 +43,7 @@
 #include "swr_raycast.hip.h"
 #include "swr_character.hip.h"
 #include "swr_resolve.hip.h"
+#include "swr_present8.hip.h"
 
 using namespace swr;
 
@@ -62,16 +63,22 @@ int launch_flatten(swr_context* c, float* d_rgb, size_t n) {
     return SWR_OK;
 }
 
-// What a present call delivers: the flatten (k_flatten_rgb, one RGB triple per band pixel) or the kx x ky box-filter resolve
-// (k_resolve_rgb, one triple per kx x ky block of band pixels).  Every present shape below is defined once over this.
-struct Payload { bool resolve; int kx, ky; };
-constexpr Payload FLATTEN = {false, 1, 1};
+// What a present call delivers: the flatten (k_flatten_rgb, one RGB triple per band pixel), the kx x ky box-filter resolve
+// (k_resolve_rgb, one triple per kx x ky block of band pixels), or the resolve quantised to bytes (k_present8: RGB8 or RGBX8, factors
+// (1, 1) being the plain frame).  Every present shape below is defined once over this, in bytes of the payload's format.
+enum PayloadFormat { PAYLOAD_RGB32F, PAYLOAD_RGB8, PAYLOAD_RGBX8, PAYLOAD_NO_FORMAT };
+struct Payload { bool resolve; int kx, ky; PayloadFormat format; };
+constexpr Payload FLATTEN = {false, 1, 1, PAYLOAD_RGB32F};
+constexpr Payload resolved(int kx, int ky) { return Payload{true, kx, ky, PAYLOAD_RGB32F}; }
+constexpr Payload quantised(int kx, int ky, int bpp) { return Payload{true, kx, ky, bpp == 3 ? PAYLOAD_RGB8 : bpp == 4 ? PAYLOAD_RGBX8 : PAYLOAD_NO_FORMAT}; }
+size_t payload_bpp(const Payload& p) { return p.format == PAYLOAD_RGB32F ? 12 : p.format == PAYLOAD_RGB8 ? 3 : 4; }
 
 bool resolve_factor_ok(int k) { return k == 1 || k == 2 || k == 4 || k == 8; }
 // a zero-size target resolves to nothing under any factor pair; otherwise the frame must divide (then every band's rows do too:
 // the factors divide the tile, and the last tile row holds H - 16 * (tiles_y - 1) pixel rows)
 int payload_check(swr_context* c, const Payload& p) {
     if (!p.resolve) return SWR_OK;
+    if (p.format == PAYLOAD_NO_FORMAT) return fail(c, SWR_ERR_INVALID_ARG, "bpp must be 3 (RGB8) or 4 (RGBX8)");
     if (!resolve_factor_ok(p.kx) || !resolve_factor_ok(p.ky)) return fail(c, SWR_ERR_INVALID_ARG, "resolve factors must be 1, 2, 4 or 8");
     if (c->W <= 0 || c->H <= 0) return SWR_OK;
     if (c->W % p.kx || c->H % p.ky) return fail(c, SWR_ERR_INVALID_ARG, "the render target's width and height must be multiples of the resolve factors");
@@ -80,6 +87,7 @@ int payload_check(swr_context* c, const Payload& p) {
 int payload_width(const swr_context* c, const Payload& p) { return std::max(0, c->W) / p.kx; }
 int payload_rows(const swr_context* c, const Payload& p) { return band_rows(c) / p.ky; }
 size_t payload_pixels(const swr_context* c, const Payload& p) { return (size_t)payload_width(c, p) * (size_t)payload_rows(c, p); }
+size_t payload_bytes(const swr_context* c, const Payload& p) { return payload_pixels(c, p) * payload_bpp(p); }
 
 using ResolveKernel = void (*)(const float4*, float*, int, int);
 template <int KX> ResolveKernel resolve_kernel_rows(int ky) {
@@ -89,8 +97,33 @@ ResolveKernel resolve_kernel(int kx, int ky) {
     return kx == 1 ? resolve_kernel_rows<1>(ky) : kx == 2 ? resolve_kernel_rows<2>(ky) : kx == 4 ? resolve_kernel_rows<4>(ky) : resolve_kernel_rows<8>(ky);
 }
 
-// the payload of the band's colour plane in device memory, on the context's stream (checked, and not empty)
-int launch_payload(swr_context* c, const Payload& p, float* d_rgb) {
+using Present8Kernel = void (*)(const float4*, uint8_t*, uint32_t, uint32_t);
+template <int KX, int BPP> Present8Kernel present8_kernel_rows(int ky) {
+    return ky == 1 ? k_present8<KX, 1, BPP> : ky == 2 ? k_present8<KX, 2, BPP> : ky == 4 ? k_present8<KX, 4, BPP> : k_present8<KX, 8, BPP>;
+}
+template <int BPP> Present8Kernel present8_kernel(int kx, int ky) {
+    return kx == 1 ? present8_kernel_rows<1, BPP>(ky) : kx == 2 ? present8_kernel_rows<2, BPP>(ky)
+         : kx == 4 ? present8_kernel_rows<4, BPP>(ky) : present8_kernel_rows<8, BPP>(ky);
+}
+
+int launch_present8(swr_context* c, const Payload& p, uint8_t* d_out) {
+    const uint32_t ow = (uint32_t)payload_width(c, p), orows = (uint32_t)payload_rows(c, p);    // a frame is at most 65535 x 65535
+#if defined(SWR_PRESENT8_FOUR_PER_THREAD)
+    const dim3 block(SWR_PRESENT8_BLOCK), grid((present8_threads(ow * orows) + SWR_PRESENT8_BLOCK - 1) / SWR_PRESENT8_BLOCK);
+#else
+    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
+    const dim3 grid((ow + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
+#endif
+    const Present8Kernel k = p.format == PAYLOAD_RGB8 ? present8_kernel<3>(p.kx, p.ky) : present8_kernel<4>(p.kx, p.ky);
+    hipLaunchKernelGGL(k, grid, block, 0, c->stream, (const float4*)c->color, d_out, ow, orows);
+    SWR_HIP(c, hipGetLastError());
+    return SWR_OK;
+}
+
+// the payload of the band's colour plane in device memory (4-byte aligned), on the context's stream (checked, and not empty)
+int launch_payload(swr_context* c, const Payload& p, void* d_out) {
+    if (p.format != PAYLOAD_RGB32F) return launch_present8(c, p, (uint8_t*)d_out);
+    float* d_rgb = (float*)d_out;
     if (!p.resolve) return launch_flatten(c, d_rgb, band_pixels(c));
     const int ow = payload_width(c, p), orows = payload_rows(c, p);
     const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
@@ -101,38 +134,42 @@ int launch_payload(swr_context* c, const Payload& p, float* d_rgb) {
     return SWR_OK;
 }
 
-// swr_flatten_rgb_device / swr_resolve_rgb_device [_async].  Stream order puts the payload kernel after the frame's kernels; a batch that
+// swr_flatten_rgb_device / swr_resolve_rgb_device / swr_resolve_rgb8_device [_async].  Stream order puts the payload kernel after the frame's kernels; a batch that
 // has to be replayed (optimistic flush) is replayed by the caller's swr_sync BEFORE the result is consumed -- and then the kernel must
 // run again, which sync does not know about: so `validate` first (cheap when nothing overflowed: one pinned-flag read after the stream
 // drains)
-int payload_device(swr_context* c, const Payload& p, float* d_rgb, bool validate) {
-    if (!d_rgb) return fail(c, SWR_ERR_INVALID_ARG, "d_rgb is null");
+int payload_device(swr_context* c, const Payload& p, void* d_out, bool validate) {
+    if (!d_out) return fail(c, SWR_ERR_INVALID_ARG, "the device destination is null");
+    // k_present8 stores whole dwords (the float kernels' float stores have always needed this much)
+    if (p.format != PAYLOAD_RGB32F && ((uintptr_t)d_out & 3u)) return fail(c, SWR_ERR_INVALID_ARG, "the device destination must be 4-byte aligned");
     int rc = payload_check(c, p); if (rc) return rc;
     if ((rc = flush_locked(c))) return rc;
     if (!payload_pixels(c, p)) return SWR_OK;
     if (validate && (rc = sync_locked(c))) return rc;
-    return launch_payload(c, p, d_rgb);
+    return launch_payload(c, p, d_out);
 }
 
-// swr_readback_rgb / swr_readback_rgb_resolved: the payload into host memory, between two host syncs
-int payload_readback(swr_context* c, const Payload& p, float* rgb) {
-    if (!rgb) return fail(c, SWR_ERR_INVALID_ARG, "rgb is null");
+// swr_readback_rgb / swr_readback_rgb_resolved / swr_readback_rgb8: the payload into host memory (of any alignment: the copy comes
+// from the scratch block), between two host syncs
+int payload_readback(swr_context* c, const Payload& p, void* out) {
+    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "the destination is null");
     int rc = payload_check(c, p); if (rc) return rc;
     if ((rc = flush_and_sync_locked(c))) return rc;
-    const size_t n = payload_pixels(c, p);
-    if (!n) return SWR_OK;
-    if ((rc = ensure(c, c->d_scratch, n * 12))) return rc;
-    if ((rc = launch_payload(c, p, c->d_scratch.as<float>()))) return rc;
-    SWR_HIP(c, hipMemcpyAsync(rgb, c->d_scratch.p, n * 12, hipMemcpyDeviceToHost, c->stream));
+    const size_t bytes = payload_bytes(c, p);
+    if (!bytes) return SWR_OK;
+    if ((rc = ensure(c, c->d_scratch, bytes))) return rc;
+    if ((rc = launch_payload(c, p, c->d_scratch.p))) return rc;
+    SWR_HIP(c, hipMemcpyAsync(out, c->d_scratch.p, bytes, hipMemcpyDeviceToHost, c->stream));
     return sync_locked(c);
 }
 
-// swr_present_rgb_async / swr_present_rgb_resolved_async: both kinds share the two slots, the tickets and the staging buffers
-int payload_present(swr_context* c, const Payload& p, float* rgb, uint64_t* ticket) {
-    if (!rgb || !ticket) return fail(c, SWR_ERR_INVALID_ARG, "rgb or ticket is null");
+// swr_present_rgb_async / swr_present_rgb_resolved_async / swr_present_rgb8_async: every kind shares the two slots, the tickets and
+// the staging buffers (sized in bytes); a ticket does not say which kind it was
+int payload_present(swr_context* c, const Payload& p, void* out, uint64_t* ticket) {
+    if (!out || !ticket) return fail(c, SWR_ERR_INVALID_ARG, "the destination or ticket is null");
     int rc = payload_check(c, p); if (rc) return rc;
     if ((rc = flush_locked(c))) return rc;
-    const size_t n = payload_pixels(c, p);
+    const size_t bytes = payload_bytes(c, p);
     const int slot = (int)(c->next_ticket & 1ull);
     if (!c->copy_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
@@ -150,17 +187,17 @@ int payload_present(swr_context* c, const Payload& p, float* rgb, uint64_t* tick
         if (stale) c->stale_dropped[slot] = c->present_ticket[slot];
         c->present_ticket[slot] = 0;
     }
-    if (n) {
-        if (c->present_buf[slot].cap < n * 12) {
+    if (bytes) {
+        if (c->present_buf[slot].cap < bytes) {
             // growing frees the old block: make sure neither stream still uses it (first frame / after a resize only)
             SWR_HIP(c, hipStreamSynchronize(c->copy_stream));
-            if ((rc = ensure(c, c->present_buf[slot], n * 12))) return rc;
+            if ((rc = ensure(c, c->present_buf[slot], bytes))) return rc;
         }
-        if ((rc = launch_payload(c, p, c->present_buf[slot].as<float>()))) return rc;
+        if ((rc = launch_payload(c, p, c->present_buf[slot].p))) return rc;
     }
     SWR_HIP(c, hipEventRecord(c->present_flat[slot], c->stream));
     SWR_HIP(c, hipStreamWaitEvent(c->copy_stream, c->present_flat[slot], 0));
-    if (n) SWR_HIP(c, hipMemcpyAsync(rgb, c->present_buf[slot].p, n * 12, hipMemcpyDeviceToHost, c->copy_stream));
+    if (bytes) SWR_HIP(c, hipMemcpyAsync(out, c->present_buf[slot].p, bytes, hipMemcpyDeviceToHost, c->copy_stream));
     SWR_HIP(c, hipEventRecord(c->present_done[slot], c->copy_stream));
     c->present_ticket[slot] = ++c->next_ticket;
     c->present_seq[slot] = c->next_seq - 1u;
@@ -599,21 +636,35 @@ int swr_sync(swr_context* c) {
 int swr_readback(swr_context* c, float* color, float* depth) { SWR_ENTER(c); return planes_transfer(c, color, depth, true); }
 
 int swr_readback_rgb(swr_context* c, float* rgb) { SWR_ENTER(c); return payload_readback(c, FLATTEN, rgb); }
-int swr_readback_rgb_resolved(swr_context* c, int kx, int ky, float* rgb) { SWR_ENTER(c); return payload_readback(c, Payload{true, kx, ky}, rgb); }
+int swr_readback_rgb_resolved(swr_context* c, int kx, int ky, float* rgb) { SWR_ENTER(c); return payload_readback(c, resolved(kx, ky), rgb); }
+int swr_readback_rgb8(swr_context* c, int kx, int ky, int bpp, uint8_t* out) { SWR_ENTER(c); return payload_readback(c, quantised(kx, ky, bpp), out); }
 
 int swr_resolved_size(swr_context* c, int kx, int ky, int* out_width, int* out_rows) {
     SWR_ENTER(c);
     if (!out_width || !out_rows) return fail(c, SWR_ERR_INVALID_ARG, "out_width or out_rows is null");
-    const Payload p = {true, kx, ky};
+    const Payload p = resolved(kx, ky);
     int rc = payload_check(c, p); if (rc) return rc;
     *out_width = payload_width(c, p); *out_rows = payload_rows(c, p);
+    return SWR_OK;
+}
+
+int swr_present8_size(swr_context* c, int kx, int ky, int bpp, int* out_width, int* out_rows, size_t* out_bytes) {
+    SWR_ENTER(c);
+    if (!out_width || !out_rows || !out_bytes) return fail(c, SWR_ERR_INVALID_ARG, "out_width, out_rows or out_bytes is null");
+    const Payload p = quantised(kx, ky, bpp);
+    int rc = payload_check(c, p); if (rc) return rc;
+    *out_width = payload_width(c, p); *out_rows = payload_rows(c, p); *out_bytes = payload_bytes(c, p);
     return SWR_OK;
 }
 
 int swr_present_rgb_async(swr_context* c, float* rgb, uint64_t* ticket) { SWR_ENTER(c); return payload_present(c, FLATTEN, rgb, ticket); }
 int swr_present_rgb_resolved_async(swr_context* c, int kx, int ky, float* rgb, uint64_t* ticket) {
     SWR_ENTER(c);
-    return payload_present(c, Payload{true, kx, ky}, rgb, ticket);
+    return payload_present(c, resolved(kx, ky), rgb, ticket);
+}
+int swr_present_rgb8_async(swr_context* c, int kx, int ky, int bpp, uint8_t* out, uint64_t* ticket) {
+    SWR_ENTER(c);
+    return payload_present(c, quantised(kx, ky, bpp), out, ticket);
 }
 
 int swr_present_wait(swr_context* c, uint64_t ticket) {
@@ -663,8 +714,13 @@ int swr_host_unregister(swr_context* c, void* ptr) {
 
 int swr_flatten_rgb_device(swr_context* c, float* d_rgb) { SWR_ENTER(c); return payload_device(c, FLATTEN, d_rgb, true); }
 int swr_flatten_rgb_device_async(swr_context* c, float* d_rgb) { SWR_ENTER(c); return payload_device(c, FLATTEN, d_rgb, false); }
-int swr_resolve_rgb_device(swr_context* c, int kx, int ky, float* d_rgb) { SWR_ENTER(c); return payload_device(c, Payload{true, kx, ky}, d_rgb, true); }
-int swr_resolve_rgb_device_async(swr_context* c, int kx, int ky, float* d_rgb) { SWR_ENTER(c); return payload_device(c, Payload{true, kx, ky}, d_rgb, false); }
+int swr_resolve_rgb_device(swr_context* c, int kx, int ky, float* d_rgb) { SWR_ENTER(c); return payload_device(c, resolved(kx, ky), d_rgb, true); }
+int swr_resolve_rgb_device_async(swr_context* c, int kx, int ky, float* d_rgb) { SWR_ENTER(c); return payload_device(c, resolved(kx, ky), d_rgb, false); }
+int swr_resolve_rgb8_device(swr_context* c, int kx, int ky, int bpp, uint8_t* d_out) { SWR_ENTER(c); return payload_device(c, quantised(kx, ky, bpp), d_out, true); }
+int swr_resolve_rgb8_device_async(swr_context* c, int kx, int ky, int bpp, uint8_t* d_out) {
+    SWR_ENTER(c);
+    return payload_device(c, quantised(kx, ky, bpp), d_out, false);
+}
 
 int swr_replay_count(swr_context* c, uint64_t* out) { SWR_ENTER(c); if (!out) return SWR_ERR_INVALID_ARG; *out = c->replays; return SWR_OK; }
 int swr_sync_count(swr_context* c, uint64_t* out) { SWR_ENTER(c); if (!out) return SWR_ERR_INVALID_ARG; *out = c->host_syncs; return SWR_OK; }

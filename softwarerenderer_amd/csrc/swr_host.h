@@ -156,8 +156,9 @@ struct swr_context {
     unsigned long long host_tile_pairs = 0;   // rounds sized on the host (MODE_SYNC)
     unsigned long long replays = 0;           // times an optimistic batch did not fit and was replayed
     unsigned long long host_syncs = 0;        // times an entry point made the host wait for the stream (swr_sync_count)
-    // asynchronous present (swr_present_rgb_async): two device staging buffers alternate; the flatten runs on `stream`, the copy to
-    // the host on `copy_stream`, so the next frame renders while this one crosses PCIe
+    // asynchronous present (swr_present_rgb_async and its resolved and 8-bit forms): two device staging buffers alternate, sized in
+    // bytes for whichever payload format used them last; the payload kernel runs on `stream`, the copy to the host on `copy_stream`,
+    // so the next frame renders while this one crosses PCIe
     hipStream_t copy_stream = nullptr;
     DevBuf present_buf[2];
     hipEvent_t present_flat[2] = { nullptr, nullptr }, present_done[2] = { nullptr, nullptr };

@@ -558,6 +558,52 @@ class MainWindow:
         self._activate()
         self._dev._ck(self._dev._lib.swr_resolve_rgb_device_async(self._dev._ctx, int(kx), int(ky), C.c_void_p(device_ptr)))
 
+    def Present8Size(self, kx: int = 1, ky: int = 1, channels: int = 3) -> tuple:
+        """(rows, width, channels) of the 8-bit present's payload (swr_present8_size restated on the host): ResolvedSize, and 3
+        (R, G, B) or 4 (R, G, B, 255) bytes per pixel, rows tightly packed."""
+        if channels not in (3, 4):
+            raise ValueError("channels must be 3 (RGB8) or 4 (RGBX8)")
+        return self.ResolvedSize(kx, ky) + (channels,)
+
+    def _present8_out(self, kx, ky, channels, out):
+        shape = self.Present8Size(kx, ky, channels)
+        if out is None:
+            out = np.empty(shape, dtype=np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
+        self._activate()
+        return out
+
+    def ColorBuffer8(self, kx: int = 1, ky: int = 1, channels: int = 3, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The frame as the window's 8-bit framebuffer will hold it, quantised on the GPU (swr_readback_rgb8; the rule is in
+        include/swr.h): FlatColorBuffer under (1, 1), ResolvedColorBuffer otherwise, clamped to [0, 1], times 255, rounded to nearest
+        even; (rows / ky, W / kx, channels) uint8.  A quarter (channels = 3) or a third (channels = 4) of the float payload's bytes."""
+        out = self._present8_out(kx, ky, channels, out)
+        if out.size:
+            self._dev._ck(self._dev._lib.swr_readback_rgb8(self._dev._ctx, int(kx), int(ky), int(channels), out.ctypes.data))
+        return out
+
+    def Present8Async(self, out: np.ndarray, kx: int = 1, ky: int = 1) -> int:
+        """PresentAsync with the 8-bit payload (swr_present_rgb8_async); out.shape[-1] (3 or 4) selects the format.  Shares
+        PresentAsync's two slots; PresentWait serves the ticket."""
+        if getattr(out, "ndim", 0) != 3:
+            raise ValueError("out must be a uint8 array of shape (rows, width, 3 or 4)")
+        channels = int(out.shape[-1])
+        out = self._present8_out(kx, ky, channels, out)
+        t = C.c_uint64(0)
+        self._dev._ck(self._dev._lib.swr_present_rgb8_async(self._dev._ctx, int(kx), int(ky), channels, C.c_void_p(out.ctypes.data), C.byref(t)))
+        return int(t.value)
+
+    def Quantise8To(self, device_ptr: int, kx: int = 1, ky: int = 1, channels: int = 3):
+        """ColorBuffer8 into caller-owned DEVICE memory (Present8Size bytes, 4-byte aligned); completes with Device.sync()."""
+        self._activate()
+        self._dev._ck(self._dev._lib.swr_resolve_rgb8_device(self._dev._ctx, int(kx), int(ky), int(channels), C.c_void_p(device_ptr)))
+
+    def Quantise8ToAsync(self, device_ptr: int, kx: int = 1, ky: int = 1, channels: int = 3):
+        """Quantise8To without the validation sync (swr_resolve_rgb8_device_async), as FlattenToAsync."""
+        self._activate()
+        self._dev._ck(self._dev._lib.swr_resolve_rgb8_device_async(self._dev._ctx, int(kx), int(ky), int(channels), C.c_void_p(device_ptr)))
+
     def Upload(self, color=None, depth=None):
         self._activate()
         c = np.ascontiguousarray(color, dtype=np.float32) if color is not None else None
