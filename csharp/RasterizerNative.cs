@@ -215,6 +215,9 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_texture_destroy(IntPtr ctx, IntPtr texture);
         [DllImport(Lib)] public static extern int swr_texture_set_filter(IntPtr ctx, IntPtr texture, int bilinear);
         [DllImport(Lib)] public static extern int swr_texture_sample(IntPtr ctx, IntPtr texture, Vector2* uv, int n, Vector4* outRgba);
+        [DllImport(Lib)] public static extern int swr_texture_create_target(IntPtr ctx, int width, int height, out IntPtr texture);
+        [DllImport(Lib)] public static extern int swr_texture_update_from_frame(IntPtr ctx, IntPtr texture, IntPtr sourceCtx, int kx, int ky, int alphaMode);
+        [DllImport(Lib)] public static extern int swr_texture_readback(IntPtr ctx, IntPtr texture, byte* rgba8);
         [DllImport(Lib)] public static extern int swr_mesh_create(IntPtr ctx, Shaders.VertexInput* vertices, int nVertices, ushort* indices, int nIndices, out IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_mesh_destroy(IntPtr ctx, IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_set_state(IntPtr ctx, float nearClip, float farClip, int debugMode);
@@ -895,6 +898,34 @@ namespace SoftwareRenderer
                 SwrContext.Check(Native.swr_texture_create(SwrContext.Handle, p, Width, Height, out IntPtr h));
                 Handle = h;
             }
+        }
+
+        private TextureNative(int width, int height, IntPtr handle) { Width = width; Height = height; Handle = handle; }
+
+        /// Render to texture (build-defined: the reference links Texture and the window's buffers nowhere).  A texture of zeros
+        /// without host data, to be filled by UpdateFrom.
+        public static TextureNative CreateTarget(int width, int height)
+        {
+            SwrContext.Check(Native.swr_texture_create_target(SwrContext.Handle, width, height, out IntPtr h));
+            return new TextureNative(width, height, h);
+        }
+
+        /// The texels become the frame of Width * kx by Height * ky pixels, box-filtered and quantised as the 8-bit present; alpha
+        /// 255, or the frame's with keepAlpha.  The frame is this context's (MainWindowNative's) unless sourceContext names another
+        /// swr_context on the same GPU.  Immediate-mode semantics -- draws recorded earlier sample the old texels, later ones the
+        /// new -- and no wait for the GPU: one kernel on the context's stream (swr_texture_update_from_frame).
+        public void UpdateFrom(int kx = 1, int ky = 1, bool keepAlpha = false, IntPtr sourceContext = default)
+        {
+            SwrContext.Check(Native.swr_texture_update_from_frame(SwrContext.Handle, Handle, sourceContext, kx, ky, keepAlpha ? 1 : 0));
+        }
+
+        /// The RGBA8 texels, row-major, Width * Height * 4 bytes; waits for the GPU (screenshots, tests).
+        public byte[] Read()
+        {
+            var pixels = new byte[Width * Height * 4];
+            fixed (byte* p = pixels)
+                SwrContext.Check(Native.swr_texture_readback(SwrContext.Handle, Handle, p));
+            return pixels;
         }
 
         public Vector4 Sample(Vector2 uv)                                       // Texture.cs:43-63: nearest, wrap, byte * (1f / 255f)

@@ -259,6 +259,30 @@ int  swr_texture_destroy(swr_context* ctx, swr_texture* tex);
 int  swr_texture_set_filter(swr_context* ctx, swr_texture* tex, int bilinear);
 /* Texture.Sample, Texture.cs:43-63, batched: n uv pairs -> n RGBA float4 (runs on the GPU) */
 int  swr_texture_sample(swr_context* ctx, const swr_texture* tex, const float* uv, int n, float* out_rgba);
+/* RENDER TO TEXTURE (build-defined: the reference has Texture over Image<Rgba32> and MainWindow's float buffers and no link between
+ * them; csrc/swr_rtt.hip.h): a frame becomes a draw's texture without leaving the device -- a scope, a mirror,
+ * a camera screen, a minimap, last frame's image. */
+enum { SWR_TEXTURE_ALPHA_OPAQUE = 0, SWR_TEXTURE_ALPHA_KEEP = 1 };
+/* a texture of zeros without host data, to be filled by swr_texture_update_from_frame; the limits of swr_texture_create */
+int  swr_texture_create_target(swr_context* ctx, int width, int height, swr_texture** out);
+/* Texel (x, y) of the w x h texture from src's frame of w * kx by h * ky pixels, kx, ky in {1, 2, 4, 8}: R, G, B are the bytes
+ * swr_readback_rgb8(src, kx, ky, 4) delivers for output pixel (x, y); A is 255 under SWR_TEXTURE_ALPHA_OPAQUE and, under
+ * SWR_TEXTURE_ALPHA_KEEP, the frame's alpha through the same pairwise tree, scale and quantiser.  src == NULL: ctx's own frame.
+ * IMMEDIATE-MODE SEMANTICS, as `tex[x, y] = quantise(window.GetPixel(...))` executed at this point of the program: draws recorded
+ * earlier -- flushed or not -- sample the old texels, draws recorded later the new ones; src's frame is what its draws recorded so far
+ * leave.  ASYNCHRONOUS: both contexts' recorded draws are flushed, ONE kernel is enqueued on ctx's stream, and nothing waits for the GPU
+ * (swr_sync_count of both contexts stays); between two contexts one event orders the kernel behind src's frame and one orders src's
+ * later work behind the kernel.  The block-linear copy of a bilinear texture (swr_texture_set_filter) is written by the same kernel.
+ * Reads whatever colour buffer src has bound (swr_bind_framebuffer) and honours swr_set_stream.  A texture is used with the context
+ * that created it.  Like the *_device_async calls the update does not validate optimistic flushes: if swr_replay_count of src or ctx
+ * grows at the next validating call, a batch in front of the update had not fitted its pair buffers and the texels were made from
+ * an incomplete frame -- update (and redraw what sampled it) again; steady-state frames never replay.
+ * SWR_ERR_INVALID_ARG: tex NULL, factors outside {1, 2, 4, 8}, an unknown alpha_mode, a frame that is not w * kx by h * ky.
+ * SWR_ERR_UNSUPPORTED: src holds only a band of its frame (swr_set_band*), or lives on another device.  Nothing is written then and
+ * the context stays usable. */
+int  swr_texture_update_from_frame(swr_context* ctx, swr_texture* tex, swr_context* src, int kx, int ky, int alpha_mode);
+/* the row-major texels, w * h * 4 bytes, as the kernels enqueued so far leave them; waits for the stream (screenshots, tests) */
+int  swr_texture_readback(swr_context* ctx, const swr_texture* tex, uint8_t* rgba8);
 /* mesh.Vertices / mesh.Indices (ModelLoader.cs:45-47): u16 indices, 3 per triangle; an index >= n_vertices
  * is SWR_ERR_INVALID_ARG (C#: IndexOutOfRangeException at Rasterizer.cs:187) */
 int  swr_mesh_create(swr_context* ctx, const swr_vertex* vertices, int n_vertices,

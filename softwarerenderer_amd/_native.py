@@ -23,6 +23,7 @@ SWR_ERR_HIP = -2
 SWR_ERR_OOM = -3
 SWR_ERR_NO_DEVICE = -4
 SWR_ERR_UNSUPPORTED = -5
+SWR_TEXTURE_ALPHA_OPAQUE, SWR_TEXTURE_ALPHA_KEEP = 0, 1     # swr_texture_update_from_frame
 SWR_STALE = 1          # swr_present_wait: not an error -- the copied frame predates a replayed batch, present again
 
 
@@ -112,6 +113,7 @@ EXPORTS = [
     "swr_raycast", "swr_raycast_nearest", "swr_character_ray_counts", "swr_character_update",
     "swr_resolved_size", "swr_readback_rgb_resolved", "swr_present_rgb_resolved_async", "swr_resolve_rgb_device", "swr_resolve_rgb_device_async",
     "swr_present8_size", "swr_readback_rgb8", "swr_present_rgb8_async", "swr_resolve_rgb8_device", "swr_resolve_rgb8_device_async",
+    "swr_texture_create_target", "swr_texture_update_from_frame", "swr_texture_readback",
 ]
 
 _libs = {}
@@ -211,6 +213,9 @@ def load(name: str = None) -> C.CDLL:
         "swr_present_rgb8_async": (I, [P, I, I, I, P, C.POINTER(C.c_uint64)]),
         "swr_resolve_rgb8_device": (I, [P, I, I, I, P]),
         "swr_resolve_rgb8_device_async": (I, [P, I, I, I, P]),
+        "swr_texture_create_target": (I, [P, I, I, C.POINTER(P)]),
+        "swr_texture_update_from_frame": (I, [P, P, P, I, I, I]),
+        "swr_texture_readback": (I, [P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

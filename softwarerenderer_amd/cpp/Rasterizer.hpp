@@ -78,12 +78,23 @@ struct Shaders {
 };
 static_assert(sizeof(Shaders::VertexInput) == 48, "VertexInput must match Shaders.cs:10-24");
 
+class MainWindow;
 class Texture {                               // Texture.cs:31-68
 public:
     Texture(const Device& dev, const uint8_t* rgba8, int width, int height) : dev_(dev), Width(width), Height(height) {
         dev_.check(swr_texture_create(dev_.ctx(), rgba8, width, height, &h_));
     }
     ~Texture() { Dispose(); }
+    // render to texture (build-defined, swr.h): a texture of zeros without host data, to be filled by UpdateFrom
+    static Texture Target(const Device& dev, int width, int height) { return Texture(dev, width, height); }
+    // the texels become the window's frame of Width * kx by Height * ky pixels, box-filtered and quantised as the 8-bit present; the
+    // window may belong to another Device on the same GPU.  Immediate-mode semantics, no wait for the GPU
+    inline void UpdateFrom(const MainWindow& window, int kx = 1, int ky = 1, bool keepAlpha = false);
+    std::vector<uint8_t> Read() const {       // RGBA8 row-major; waits for the GPU
+        std::vector<uint8_t> out((size_t)Width * (size_t)Height * 4);
+        dev_.check(swr_texture_readback(dev_.ctx(), h_, out.data()));
+        return out;
+    }
     Vector4 Sample(float u, float v) const {  // Texture.cs:43-63 (runs on the GPU)
         float uv[2] = { u, v }; Vector4 out{};
         dev_.check(swr_texture_sample(dev_.ctx(), h_, uv, 1, out.data()));
@@ -93,6 +104,9 @@ public:
     swr_texture* handle() const { return h_; }
     const int Width, Height;
 private:
+    Texture(const Device& dev, int width, int height) : dev_(dev), Width(width), Height(height) {
+        dev_.check(swr_texture_create_target(dev_.ctx(), width, height, &h_));
+    }
     const Device& dev_;
     swr_texture* h_ = nullptr;
 };
@@ -151,6 +165,11 @@ public:
 private:
     const Device& dev_;
 };
+
+inline void Texture::UpdateFrom(const MainWindow& window, int kx, int ky, bool keepAlpha) {
+    swr_context* src = window.device().ctx() == dev_.ctx() ? nullptr : window.device().ctx();
+    dev_.check(swr_texture_update_from_frame(dev_.ctx(), h_, src, kx, ky, keepAlpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
+}
 
 class Rasterizer {                            // public static class Rasterizer, Rasterizer.cs:12
 public:

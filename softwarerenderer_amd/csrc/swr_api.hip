@@ -44,6 +44,7 @@
 #include "swr_character.hip.h"
 #include "swr_resolve.hip.h"
 #include "swr_present8.hip.h"
+#include "swr_rtt.hip.h"
 
 using namespace swr;
 
@@ -415,6 +416,57 @@ int character_update(swr_context* c, const swr_character_params* params, swr_cha
     if (trace) memcpy(trace, down + off_trace, N * sizeof(swr_character_trace));
     return SWR_OK;
 }
+
+// swr_texture_update_from_frame: k_frame_to_texture by factors, alpha mode and whether the block-linear copy exists
+using RttKernel = void (*)(const float4*, uint32_t*, uint32_t*, uint32_t, uint32_t);
+template <int KX, bool ALPHA, bool BLOCKED> RttKernel rtt_kernel_rows(int ky) {
+    return ky == 1 ? k_frame_to_texture<KX, 1, ALPHA, BLOCKED> : ky == 2 ? k_frame_to_texture<KX, 2, ALPHA, BLOCKED>
+         : ky == 4 ? k_frame_to_texture<KX, 4, ALPHA, BLOCKED> : k_frame_to_texture<KX, 8, ALPHA, BLOCKED>;
+}
+template <bool ALPHA, bool BLOCKED> RttKernel rtt_kernel_factors(int kx, int ky) {
+    return kx == 1 ? rtt_kernel_rows<1, ALPHA, BLOCKED>(ky) : kx == 2 ? rtt_kernel_rows<2, ALPHA, BLOCKED>(ky)
+         : kx == 4 ? rtt_kernel_rows<4, ALPHA, BLOCKED>(ky) : rtt_kernel_rows<8, ALPHA, BLOCKED>(ky);
+}
+RttKernel rtt_kernel(int kx, int ky, bool alpha, bool blocked) {
+    return alpha ? (blocked ? rtt_kernel_factors<true, true>(kx, ky) : rtt_kernel_factors<true, false>(kx, ky))
+                 : (blocked ? rtt_kernel_factors<false, true>(kx, ky) : rtt_kernel_factors<false, false>(kx, ky));
+}
+
+// Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream.
+int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
+    if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
+    if (alpha_mode != SWR_TEXTURE_ALPHA_OPAQUE && alpha_mode != SWR_TEXTURE_ALPHA_KEEP)
+        return fail(c, SWR_ERR_INVALID_ARG, "alpha_mode must be SWR_TEXTURE_ALPHA_OPAQUE (0) or SWR_TEXTURE_ALPHA_KEEP (1)");
+    if (!resolve_factor_ok(kx) || !resolve_factor_ok(ky)) return fail(c, SWR_ERR_INVALID_ARG, "resolve factors must be 1, 2, 4 or 8");
+    if (src->device != c->device) return fail(c, SWR_ERR_UNSUPPORTED, "the source frame lives on another device");
+    if (src->W > 0 && src->H > 0 && (src->band_ty0 != 0 || band_rows(src) != src->H))
+        return fail(c, SWR_ERR_UNSUPPORTED, "the source context holds only a band of its frame (swr_set_band*)");
+    if ((long long)t->w * kx != (long long)src->W || (long long)t->h * ky != (long long)src->H)
+        return fail(c, SWR_ERR_INVALID_ARG, "the source frame must measure texture width * kx by texture height * ky");
+    int rc;
+    // the frame is complete behind this point of src's stream, and c's recorded draws are in front of the kernel on c's stream: they
+    // sample the old texels (raster kernels and k_texture_sample, the only readers of a texture, run on `stream`, never on the front stream)
+    if ((rc = flush_locked(src))) { if (src != c) c->err = src->err; return rc; }
+    if (src != c && (rc = flush_locked(c))) return rc;
+    if (src != c && src->stream != c->stream) {
+        if (!src->rtt_frame_ev) SWR_HIP(c, hipEventCreateWithFlags(&src->rtt_frame_ev, hipEventDisableTiming));
+        SWR_HIP(c, hipEventRecord(src->rtt_frame_ev, src->stream));
+        SWR_HIP(c, hipStreamWaitEvent(c->stream, src->rtt_frame_ev, 0));
+    }
+    const bool blocked = t->d_blocked != nullptr;         // (made by swr_texture_set_filter: both sides are multiples of 4)
+    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
+    const dim3 grid(((uint32_t)t->w + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, ((uint32_t)t->h + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
+    hipLaunchKernelGGL(rtt_kernel(kx, ky, alpha_mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
+                       (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
+    SWR_HIP(c, hipGetLastError());
+    if (src != c && src->stream != c->stream) {
+        // src's next raster, clear or upload may not overwrite the frame under the kernel
+        if (!c->rtt_done_ev) SWR_HIP(c, hipEventCreateWithFlags(&c->rtt_done_ev, hipEventDisableTiming));
+        SWR_HIP(c, hipEventRecord(c->rtt_done_ev, c->stream));
+        SWR_HIP(c, hipStreamWaitEvent(src->stream, c->rtt_done_ev, 0));
+    }
+    return SWR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -520,6 +572,8 @@ void swr_destroy(swr_context* c) {
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->ray_stream) { (void)hipStreamSynchronize(c->ray_stream); (void)hipStreamDestroy(c->ray_stream); }
     if (c->ray_host) (void)hipHostFree(c->ray_host);
+    if (c->rtt_frame_ev) (void)hipEventDestroy(c->rtt_frame_ev);
+    if (c->rtt_done_ev) (void)hipEventDestroy(c->rtt_done_ev);
     for (int i = 0; i < 2; ++i) {
         if (c->present_flat[i]) (void)hipEventDestroy(c->present_flat[i]);
         if (c->present_done[i]) (void)hipEventDestroy(c->present_done[i]);
@@ -771,6 +825,44 @@ int swr_texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_t
     }
     *out = t;
     return SWR_OK;
+}
+
+int swr_texture_create_target(swr_context* c, int w, int h, swr_texture** out) {
+    SWR_ENTER(c);
+    if (w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
+    if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
+    swr_texture* t = new swr_texture();
+    t->w = w; t->h = h;
+    hipError_t e = hipMalloc((void**)&t->d_rgba, (size_t)w * h * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_rgba, 0, (size_t)w * h * 4, c->stream);
+    if (e != hipSuccess) {
+        if (t->d_rgba) (void)hipFree(t->d_rgba);
+        delete t;
+        c->err = std::string("texture allocation failed: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+    }
+    *out = t;
+    return SWR_OK;
+}
+
+int swr_texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
+    if (!c) return SWR_ERR_INVALID_ARG;
+    if (!src || src == c) {
+        std::lock_guard<std::mutex> lock_(c->mu);
+        (void)hipSetDevice(c->device);
+        return texture_update_from_frame(c, t, c, kx, ky, alpha_mode);
+    }
+    std::lock(c->mu, src->mu);                            // (both, in an order that cannot deadlock against the opposite call)
+    std::lock_guard<std::mutex> lock_c(c->mu, std::adopt_lock), lock_s(src->mu, std::adopt_lock);
+    (void)hipSetDevice(c->device);
+    return texture_update_from_frame(c, t, src, kx, ky, alpha_mode);
+}
+
+int swr_texture_readback(swr_context* c, const swr_texture* t, uint8_t* rgba8) {
+    SWR_ENTER(c);
+    if (!t || !rgba8) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback arguments");
+    SWR_HIP(c, hipMemcpyAsync(rgba8, t->d_rgba, (size_t)t->w * t->h * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
 }
 
 int swr_texture_set_filter(swr_context* c, swr_texture* t, int bilinear) {

@@ -18,6 +18,7 @@ struct swr_mesh {
 struct swr_texture {
     uint8_t* d_rgba = nullptr;
     uint8_t* d_blocked = nullptr;             // block-linear copy (4 x 4-texel blocks of 64 B) for the bilinear filter, made when it is first switched on
+                                              // and written beside d_rgba by swr_texture_update_from_frame from then on
     int w = 0, h = 0;
     bool bilinear = false;                    // build-defined extension; the reference's Texture.Sample is nearest
 };
@@ -167,6 +168,10 @@ struct swr_context {
     uint64_t next_ticket = 0;
 
     // swr_raycast / swr_raycast_nearest: a stream of their own (a query does not queue behind a frame in flight), idle between calls
+    // swr_texture_update_from_frame between two contexts: recorded on this context's stream behind its frame (the updating context's
+    // stream waits for it) and, in the updating context, behind the kernel (this context's stream waits before it touches the frame again)
+    hipEvent_t rtt_frame_ev = nullptr, rtt_done_ev = nullptr;
+
     hipStream_t ray_stream = nullptr;
     DevBuf d_ray, d_ray_best;                  // rays | targets | hit records; the pairs' keys, all SWR_RAY_NO_HIT between calls (k_ray_finish)
     void* ray_host = nullptr; size_t ray_host_cap = 0;     // pinned staging block of small queries

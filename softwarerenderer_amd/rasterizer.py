@@ -252,6 +252,32 @@ class Texture:
         self._h = C.c_void_p()
         device._ck(device._lib.swr_texture_create(device._ctx, px.ctypes.data, self.Width, self.Height, C.byref(self._h)))
 
+    @classmethod
+    def Target(cls, device: Device, width: int, height: int) -> "Texture":
+        """A texture of zeros without host data (swr_texture_create_target), to be filled by UpdateFrom."""
+        t = cls.__new__(cls)
+        t._dev = device
+        t.Height, t.Width = int(height), int(width)
+        t._h = C.c_void_p()
+        device._ck(device._lib.swr_texture_create_target(device._ctx, t.Width, t.Height, C.byref(t._h)))
+        return t
+
+    def UpdateFrom(self, window: "MainWindow", kx: int = 1, ky: int = 1, keep_alpha: bool = False):
+        """Render to texture (swr_texture_update_from_frame; build-defined, the reference has no such link): the texels become the
+        window's frame, box-filtered by kx x ky and quantised as the 8-bit present; alpha 255, or the frame's with keep_alpha.  The
+        window measures Width * kx by Height * ky and may belong to this texture's Device or to another Device on the same GPU.
+        Immediate-mode semantics and no wait for the GPU: draws recorded earlier sample the old texels, later ones the new."""
+        window._activate()
+        src = window._dev._ctx if window._dev is not self._dev else None
+        self._dev._ck(self._dev._lib.swr_texture_update_from_frame(
+            self._dev._ctx, self._h, src, int(kx), int(ky), N.SWR_TEXTURE_ALPHA_KEEP if keep_alpha else N.SWR_TEXTURE_ALPHA_OPAQUE))
+
+    def Read(self) -> np.ndarray:
+        """The texels as (Height, Width, 4) uint8 (swr_texture_readback); waits for the GPU."""
+        out = np.empty((self.Height, self.Width, 4), dtype=np.uint8)
+        self._dev._ck(self._dev._lib.swr_texture_readback(self._dev._ctx, self._h, out.ctypes.data))
+        return out
+
     def Sample(self, uv) -> np.ndarray:
         """Texture.Sample, Texture.cs:43-63 (batched: uv of shape (..., 2) -> (..., 4)); runs on the GPU."""
         a = np.ascontiguousarray(np.asarray(uv, dtype=np.float32))
