@@ -54,6 +54,7 @@ using namespace swr;
 #include "swr_host.h"
 #include "swr_rtc.h"
 #include "swr_flush.h"
+#include "swr_query.h"
 
 namespace {      // shapes several entry points share
 // the band's colour plane as packed RGB floats in device memory, on the context's stream
@@ -91,20 +92,12 @@ size_t payload_pixels(const swr_context* c, const Payload& p) { return (size_t)p
 size_t payload_bytes(const swr_context* c, const Payload& p) { return payload_pixels(c, p) * payload_bpp(p); }
 
 using ResolveKernel = void (*)(const float4*, float*, int, int);
-template <int KX> ResolveKernel resolve_kernel_rows(int ky) {
-    return ky == 1 ? k_resolve_rgb<KX, 1> : ky == 2 ? k_resolve_rgb<KX, 2> : ky == 4 ? k_resolve_rgb<KX, 4> : k_resolve_rgb<KX, 8>;
-}
 ResolveKernel resolve_kernel(int kx, int ky) {
-    return kx == 1 ? resolve_kernel_rows<1>(ky) : kx == 2 ? resolve_kernel_rows<2>(ky) : kx == 4 ? resolve_kernel_rows<4>(ky) : resolve_kernel_rows<8>(ky);
+    return with_factor<ResolveKernel>(kx, [&](auto x) -> ResolveKernel { return with_factor<ResolveKernel>(ky, [](auto y) -> ResolveKernel { return k_resolve_rgb<decltype(x)::value, decltype(y)::value>; }); });
 }
-
 using Present8Kernel = void (*)(const float4*, uint8_t*, uint32_t, uint32_t);
-template <int KX, int BPP> Present8Kernel present8_kernel_rows(int ky) {
-    return ky == 1 ? k_present8<KX, 1, BPP> : ky == 2 ? k_present8<KX, 2, BPP> : ky == 4 ? k_present8<KX, 4, BPP> : k_present8<KX, 8, BPP>;
-}
 template <int BPP> Present8Kernel present8_kernel(int kx, int ky) {
-    return kx == 1 ? present8_kernel_rows<1, BPP>(ky) : kx == 2 ? present8_kernel_rows<2, BPP>(ky)
-         : kx == 4 ? present8_kernel_rows<4, BPP>(ky) : present8_kernel_rows<8, BPP>(ky);
+    return with_factor<Present8Kernel>(kx, [&](auto x) -> Present8Kernel { return with_factor<Present8Kernel>(ky, [](auto y) -> Present8Kernel { return k_present8<decltype(x)::value, decltype(y)::value, BPP>; }); });
 }
 
 int launch_present8(swr_context* c, const Payload& p, uint8_t* d_out) {
@@ -228,208 +221,31 @@ int pixel_transfer(swr_context* c, int x, int y, void* plane, size_t bytes, void
     return sync_locked(c);
 }
 
-// swr_raycast / swr_raycast_nearest.  Everything runs on the context's ray stream, which is idle between calls (the call waits for
-// its own result under the context mutex): rays and targets go up in one copy, k_ray_cast and k_ray_finish run, the records come
-// back in one copy.  No allocation in the steady state (hipMalloc / hipFree would wait for the frame in flight).
-int raycast(swr_context* c, const swr_ray* rays, int n_rays, const swr_ray_target* targets, int n_targets, int flags, swr_ray_hit* out, bool nearest) {
-    if (n_rays < 0 || n_targets < 0) return fail(c, SWR_ERR_INVALID_ARG, "negative ray or target count");
-    if (flags & ~(SWR_RAY_IGNORE_BACKFACES | SWR_RAY_IGNORE_FRONTFACES | SWR_RAY_CROSS_FUSED)) return fail(c, SWR_ERR_INVALID_ARG, "unknown raycast flag bits");
-    if (n_rays == 0 || n_targets == 0) return SWR_OK;
-    if (!rays || !targets || !out) return fail(c, SWR_ERR_INVALID_ARG, "null argument to raycast");
-    if (n_rays > (1 << 20) || n_targets > 65535 || (uint64_t)n_rays * (uint64_t)n_targets > (1ull << 24))
-        return fail(c, SWR_ERR_UNSUPPORTED, "raycast: at most 2^20 rays, 65535 targets and 2^24 (ray, target) pairs per call: split the rays");
-    for (int t = 0; t < n_targets; ++t) if (!targets[t].mesh) return fail(c, SWR_ERR_INVALID_ARG, "raycast target without a mesh");
-    if (!c->ray_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->ray_stream, hipStreamNonBlocking));
-    const size_t pairs = (size_t)n_rays * (size_t)n_targets, n_out = nearest ? (size_t)n_rays : pairs;
-    const size_t off_t = ((size_t)n_rays * sizeof(swr_ray) + 15) & ~(size_t)15;
-    const size_t up_bytes = off_t + (((size_t)n_targets * sizeof(RayTarget) + 15) & ~(size_t)15), down_bytes = n_out * sizeof(swr_ray_hit);
-    int rc = ensure(c, c->d_ray, up_bytes + down_bytes); if (rc) return rc;
-    if (c->d_ray_best.cap < pairs * 8) {
-        if ((rc = ensure(c, c->d_ray_best, pairs * 8))) return rc;
-        SWR_HIP(c, hipMemsetAsync(c->d_ray_best.p, 0xff, c->d_ray_best.cap, c->ray_stream));      // from here on k_ray_finish keeps it clean
-    }
-    // small queries (a slide attempt: 111 rays x 11 meshes, 4.4 KB each way) go through one pinned block; large ones use the caller's memory
-    const bool staged = up_bytes + down_bytes <= ((size_t)1 << 20);
-    if (staged && c->ray_host_cap < up_bytes + down_bytes) {
-        if (c->ray_host) (void)hipHostFree(c->ray_host);
-        c->ray_host = nullptr; c->ray_host_cap = 0;
-        const size_t cap = std::max<size_t>(up_bytes + down_bytes, (size_t)1 << 16);
-        SWR_HIP(c, hipHostMalloc(&c->ray_host, cap, hipHostMallocDefault));
-        c->ray_host_cap = cap;
-    }
-    std::vector<char> pageable;
-    if (!staged) pageable.resize(up_bytes);
-    char* up = staged ? static_cast<char*>(c->ray_host) : pageable.data();
-    memcpy(up, rays, (size_t)n_rays * sizeof(swr_ray));
-    RayTarget* ht = reinterpret_cast<RayTarget*>(up + off_t);
-    uint32_t max_tris = 0;
-    for (int t = 0; t < n_targets; ++t) {
-        swr_mesh* m = const_cast<swr_mesh*>(targets[t].mesh);
-        if (m->uploaded && !m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
-        ht[t].verts = m->d_verts; ht[t].idx = m->d_idx; ht[t].n_tris = (uint32_t)(m->n_idx / 3); ht[t].pad = 0u;
-        memcpy(ht[t].model, targets[t].model, 64); memcpy(ht[t].normal_matrix, targets[t].normal_matrix, 64);
-        max_tris = std::max(max_tris, ht[t].n_tris);
-    }
-    char* base = static_cast<char*>(c->d_ray.p);
-    const swr_ray* d_rays = reinterpret_cast<const swr_ray*>(base);
-    const RayTarget* d_targets = reinterpret_cast<const RayTarget*>(base + off_t);
-    swr_ray_hit* d_out = reinterpret_cast<swr_ray_hit*>(base + up_bytes);
-    unsigned long long* d_best = c->d_ray_best.as<unsigned long long>();
-    const uint32_t mask = (uint32_t)flags & 3u, nr = (uint32_t)n_rays, nt = (uint32_t)n_targets;
-    const bool fused = (flags & SWR_RAY_CROSS_FUSED) != 0;
-    SWR_HIP(c, hipMemcpyAsync(base, up, up_bytes, hipMemcpyHostToDevice, c->ray_stream));
-    if (max_tris) {
-        const dim3 grid((max_tris + SWR_RAY_BLOCK - 1) / SWR_RAY_BLOCK, (nr + SWR_RAY_CHUNK - 1) / SWR_RAY_CHUNK, nt);
-        if (fused) hipLaunchKernelGGL(k_ray_cast<true>, grid, dim3(SWR_RAY_BLOCK), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best);
-        else hipLaunchKernelGGL(k_ray_cast<false>, grid, dim3(SWR_RAY_BLOCK), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best);
-        SWR_HIP(c, hipGetLastError());
-    }
-    const dim3 fgrid((unsigned)((n_out + 63) / 64));
-    if (nearest) {
-        if (fused) hipLaunchKernelGGL((k_ray_finish<true, true>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
-        else hipLaunchKernelGGL((k_ray_finish<false, true>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
-    } else {
-        if (fused) hipLaunchKernelGGL((k_ray_finish<true, false>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
-        else hipLaunchKernelGGL((k_ray_finish<false, false>), fgrid, dim3(64), 0, c->ray_stream, d_rays, nr, d_targets, nt, mask, c->nm_flags, d_best, d_out);
-    }
-    SWR_HIP(c, hipGetLastError());
-    void* down = staged ? static_cast<void*>(static_cast<char*>(c->ray_host) + up_bytes) : static_cast<void*>(out);
-    SWR_HIP(c, hipMemcpyAsync(down, d_out, down_bytes, hipMemcpyDeviceToHost, c->ray_stream));
-    SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
-    if (staged) memcpy(out, down, down_bytes);
-    return SWR_OK;
-}
-
-// Math.Max(1, (int)(Height / (radius * 2))) and Math.Max(4, (int)(4 * MathF.PI * radius / 0.1f)), CharacterController.cs:327-328, radius = Radius + 0.001f
-// (:96,118): float arithmetic in the reference's order.  false: a count that is not a number or does not fit the limits.
-bool character_ray_counts(const swr_character_params* p, int* v_steps, int* h_rays) {
-    const float radius = p->radius + 0.001f;
-    const float two_r = radius * 2.0f;
-    const float v = p->height / two_r;
-    const float four_pi = 4.0f * 3.14159274f;
-    const float h = (four_pi * radius) / 0.1f;
-    const bool ok = v == v && h == h && v < 65536.0f && h < 65536.0f;
-    *v_steps = ok ? std::max(1, (int)v) : 1;
-    *h_rays = ok ? std::max(4, (int)h) : 4;
-    return ok;
-}
-
-// swr_character_update: one upload, k_char_begin, (cast, planes), 6 x (cast, slide), one download, one wait -- nothing between the
-// kernels is read by the host, and no grid depends on a value computed on the device.
-int character_update(swr_context* c, const swr_character_params* params, swr_character* chars, const swr_character_input* inputs, int n, float dt,
-                     const float* ring, int n_ring, const swr_ray_target* targets, int n_targets, int flags, swr_character_trace* trace) {
-    if (n < 0 || n_targets < 0 || n_ring < 0) return fail(c, SWR_ERR_INVALID_ARG, "negative count in character update");
-    if (flags & ~SWR_RAY_CROSS_FUSED) return fail(c, SWR_ERR_INVALID_ARG, "character update accepts SWR_RAY_CROSS_FUSED only");
-    if (n == 0) return SWR_OK;
-    if (!params || !chars || !inputs || !ring || (n_targets > 0 && !targets)) return fail(c, SWR_ERR_INVALID_ARG, "null argument to character update");
-    int v_steps = 0, h_rays = 0;
-    const bool counts_ok = character_ray_counts(params, &v_steps, &h_rays);
-    const uint64_t slide_rays = (uint64_t)(v_steps + 1) * (uint64_t)h_rays;
-    const uint64_t stride = std::max<uint64_t>(slide_rays, SWR_CHAR_PLANE_RAYS);
-    static const char* limits = "character update: at most 65536 controllers, 4096 rays per slide attempt, 2^22 rays (controllers x rays per attempt), 65535 targets and 2^24 (ray, target) pairs per call: split the controllers";
-    if (!counts_ok || slide_rays > SWR_CHAR_MAX_RAYS) return fail(c, SWR_ERR_UNSUPPORTED, limits);
-    if (n_ring != h_rays) return fail(c, SWR_ERR_INVALID_ARG, "n_ring must equal horizontal_rays of swr_character_ray_counts");
-    if (n > 65536 || n_targets > 65535 || (uint64_t)n * stride > (1ull << 22) || (uint64_t)n * stride * (uint64_t)n_targets > (1ull << 24)) return fail(c, SWR_ERR_UNSUPPORTED, limits);
-    for (int t = 0; t < n_targets; ++t) if (!targets[t].mesh) return fail(c, SWR_ERR_INVALID_ARG, "character update target without a mesh");
-    if (!c->ray_stream) SWR_HIP(c, hipStreamCreateWithFlags(&c->ray_stream, hipStreamNonBlocking));
-    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t N = (size_t)n, NT = (size_t)n_targets;
-    const size_t off_chars = 0, off_in = off_chars + al(N * sizeof(swr_character)), off_ring = off_in + al(N * sizeof(swr_character_input));
-    const size_t off_t = off_ring + al((size_t)n_ring * 8), up_bytes = off_t + al(NT * sizeof(RayTarget));
-    const size_t off_work = up_bytes, off_active = off_work + al(N * sizeof(CharWork)), off_rays = off_active + al(N * 4);
-    const size_t rays_bytes = al(N * stride * sizeof(swr_ray));
-    const size_t off_down = off_rays + 2 * rays_bytes, off_trace = al(N * sizeof(swr_character));
-    const size_t down_bytes = off_trace + N * sizeof(swr_character_trace);
-    int rc = ensure(c, c->d_char, off_down + down_bytes); if (rc) return rc;
-    const size_t pairs = N * stride * NT;
-    if (c->d_ray_best.cap < pairs * 8) {
-        if ((rc = ensure(c, c->d_ray_best, pairs * 8))) return rc;
-        SWR_HIP(c, hipMemsetAsync(c->d_ray_best.p, 0xff, c->d_ray_best.cap, c->ray_stream));      // from here on the folds keep it clean
-    }
-    const bool staged = up_bytes + down_bytes <= ((size_t)1 << 20);
-    if (staged && c->ray_host_cap < up_bytes + down_bytes) {
-        if (c->ray_host) (void)hipHostFree(c->ray_host);
-        c->ray_host = nullptr; c->ray_host_cap = 0;
-        const size_t cap = std::max<size_t>(up_bytes + down_bytes, (size_t)1 << 16);
-        SWR_HIP(c, hipHostMalloc(&c->ray_host, cap, hipHostMallocDefault));
-        c->ray_host_cap = cap;
-    }
-    std::vector<char> pageable;
-    if (!staged) pageable.resize(up_bytes + down_bytes);
-    char* up = staged ? static_cast<char*>(c->ray_host) : pageable.data();
-    memcpy(up + off_chars, chars, N * sizeof(swr_character));
-    memcpy(up + off_in, inputs, N * sizeof(swr_character_input));
-    memcpy(up + off_ring, ring, (size_t)n_ring * 8);
-    RayTarget* ht = reinterpret_cast<RayTarget*>(up + off_t);
-    uint32_t max_tris = 0;
-    for (int t = 0; t < n_targets; ++t) {
-        swr_mesh* m = const_cast<swr_mesh*>(targets[t].mesh);
-        if (m->uploaded && !m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
-        ht[t].verts = m->d_verts; ht[t].idx = m->d_idx; ht[t].n_tris = (uint32_t)(m->n_idx / 3); ht[t].pad = 0u;
-        memcpy(ht[t].model, targets[t].model, 64); memcpy(ht[t].normal_matrix, targets[t].normal_matrix, 64);
-        max_tris = std::max(max_tris, ht[t].n_tris);
-    }
-    char* base = static_cast<char*>(c->d_char.p);
-    const swr_character* d_chars = reinterpret_cast<const swr_character*>(base + off_chars);
-    const swr_character_input* d_in = reinterpret_cast<const swr_character_input*>(base + off_in);
-    const float* d_ring = reinterpret_cast<const float*>(base + off_ring);
-    const RayTarget* d_targets = reinterpret_cast<const RayTarget*>(base + off_t);
-    CharWork* d_work = reinterpret_cast<CharWork*>(base + off_work);
-    uint32_t* d_active = reinterpret_cast<uint32_t*>(base + off_active);
-    swr_ray* d_rays[2] = { reinterpret_cast<swr_ray*>(base + off_rays), reinterpret_cast<swr_ray*>(base + off_rays + rays_bytes) };
-    swr_character* d_out = reinterpret_cast<swr_character*>(base + off_down);
-    swr_character_trace* d_trace = trace ? reinterpret_cast<swr_character_trace*>(base + off_down + off_trace) : nullptr;
-    unsigned long long* d_best = c->d_ray_best.as<unsigned long long>();
-    CharCall cc;
-    cc.p = *params; cc.dt = dt; cc.n = (uint32_t)n; cc.n_targets = (uint32_t)n_targets; cc.stride = (uint32_t)stride;
-    cc.v_steps = (uint32_t)v_steps; cc.h_rays = (uint32_t)h_rays; cc.slide_rays = (uint32_t)slide_rays; cc.nm_flags = c->nm_flags;
-    const bool fused = (flags & SWR_RAY_CROSS_FUSED) != 0;
-    const uint32_t tri_blocks = (max_tris + SWR_RAY_BLOCK - 1) / SWR_RAY_BLOCK, nt = cc.n_targets, st = cc.stride;
-    hipStream_t s = c->ray_stream;
-    SWR_HIP(c, hipMemcpyAsync(base, up, up_bytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_char_begin, dim3((cc.n + 63u) / 64u), dim3(64), 0, s, cc, d_chars, d_in, d_work, d_active, d_rays[0], d_out, d_trace);
-    if (tri_blocks) {
-        const dim3 grid(cc.n, tri_blocks, nt);
-        if (fused) hipLaunchKernelGGL((k_char_cast<true, true>), grid, dim3(SWR_RAY_BLOCK), 0, s, d_rays[0], st, (uint32_t)SWR_CHAR_PLANE_RAYS, 1u, d_active, d_targets, nt, cc.nm_flags, d_best);
-        else hipLaunchKernelGGL((k_char_cast<false, true>), grid, dim3(SWR_RAY_BLOCK), 0, s, d_rays[0], st, (uint32_t)SWR_CHAR_PLANE_RAYS, 1u, d_active, d_targets, nt, cc.nm_flags, d_best);
-    }
-    if (fused) hipLaunchKernelGGL(k_char_planes<true>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, d_rays[0], d_rays[1], d_targets, d_best);
-    else hipLaunchKernelGGL(k_char_planes<false>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, d_rays[0], d_rays[1], d_targets, d_best);
-    const uint32_t chunks = (cc.slide_rays + SWR_RAY_CHUNK - 1) / SWR_RAY_CHUNK;
-    for (int round = 0; round < SWR_CHAR_SLIDE_ROUNDS; ++round) {
-        swr_ray* in = d_rays[(round + 1) & 1];
-        swr_ray* next = d_rays[round & 1];
-        if (tri_blocks) {
-            const dim3 grid(cc.n * chunks, tri_blocks, nt);
-            if (fused) hipLaunchKernelGGL((k_char_cast<true, false>), grid, dim3(SWR_RAY_BLOCK), 0, s, in, st, cc.slide_rays, chunks, d_active, d_targets, nt, cc.nm_flags, d_best);
-            else hipLaunchKernelGGL((k_char_cast<false, false>), grid, dim3(SWR_RAY_BLOCK), 0, s, in, st, cc.slide_rays, chunks, d_active, d_targets, nt, cc.nm_flags, d_best);
-        }
-        if (fused) hipLaunchKernelGGL(k_char_slide<true>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, in, next, d_targets, d_best, d_out, d_trace);
-        else hipLaunchKernelGGL(k_char_slide<false>, dim3(cc.n), dim3(64), 0, s, cc, d_ring, d_work, d_active, in, next, d_targets, d_best, d_out, d_trace);
-    }
-    SWR_HIP(c, hipGetLastError());
-    const size_t down_now = trace ? down_bytes : N * sizeof(swr_character);
-    char* down = up + up_bytes;
-    SWR_HIP(c, hipMemcpyAsync(down, d_out, down_now, hipMemcpyDeviceToHost, s));
-    SWR_HIP(c, hipStreamSynchronize(s));
-    memcpy(chars, down, N * sizeof(swr_character));
-    if (trace) memcpy(trace, down + off_trace, N * sizeof(swr_character_trace));
-    return SWR_OK;
-}
-
 // swr_texture_update_from_frame: k_frame_to_texture by factors, alpha mode and whether the block-linear copy exists
 using RttKernel = void (*)(const float4*, uint32_t*, uint32_t*, uint32_t, uint32_t);
-template <int KX, bool ALPHA, bool BLOCKED> RttKernel rtt_kernel_rows(int ky) {
-    return ky == 1 ? k_frame_to_texture<KX, 1, ALPHA, BLOCKED> : ky == 2 ? k_frame_to_texture<KX, 2, ALPHA, BLOCKED>
-         : ky == 4 ? k_frame_to_texture<KX, 4, ALPHA, BLOCKED> : k_frame_to_texture<KX, 8, ALPHA, BLOCKED>;
-}
-template <bool ALPHA, bool BLOCKED> RttKernel rtt_kernel_factors(int kx, int ky) {
-    return kx == 1 ? rtt_kernel_rows<1, ALPHA, BLOCKED>(ky) : kx == 2 ? rtt_kernel_rows<2, ALPHA, BLOCKED>(ky)
-         : kx == 4 ? rtt_kernel_rows<4, ALPHA, BLOCKED>(ky) : rtt_kernel_rows<8, ALPHA, BLOCKED>(ky);
-}
 RttKernel rtt_kernel(int kx, int ky, bool alpha, bool blocked) {
-    return alpha ? (blocked ? rtt_kernel_factors<true, true>(kx, ky) : rtt_kernel_factors<true, false>(kx, ky))
-                 : (blocked ? rtt_kernel_factors<false, true>(kx, ky) : rtt_kernel_factors<false, false>(kx, ky));
+    using K = RttKernel;
+    return with_flag<K>(alpha, [&](auto a) -> K { return with_flag<K>(blocked, [&](auto b) -> K { return with_factor<K>(kx, [&](auto x) -> K { return with_factor<K>(ky, [](auto y) -> K {
+        return k_frame_to_texture<decltype(x)::value, decltype(y)::value, decltype(a)::value, decltype(b)::value>; }); }); }); });
+}
+
+// swr_texture_create / swr_texture_create_target: w x h texels on the context's stream, the caller's or (rgba8 null) zeros
+int texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_texture** out, const char* what_failed) {
+    if (w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
+    if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
+    swr_texture* t = new swr_texture();
+    t->w = w; t->h = h;
+    const size_t bytes = (size_t)w * h * 4;
+    hipError_t e = hipMalloc((void**)&t->d_rgba, bytes);
+    if (e == hipSuccess) e = rgba8 ? hipMemcpyAsync(t->d_rgba, rgba8, bytes, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(t->d_rgba, 0, bytes, c->stream);
+    if (e != hipSuccess) {
+        if (t->d_rgba) (void)hipFree(t->d_rgba);
+        delete t;
+        c->err = std::string(what_failed) + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+    }
+    *out = t;
+    return SWR_OK;
 }
 
 // Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream.
@@ -567,11 +383,11 @@ void swr_destroy(swr_context* c) {
     for (swr_mesh* m : c->mesh_pool) destroy_mesh(m);
     c->mesh_pool.clear();
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto& fs : c->slots) { if (fs.host) (void)hipHostFree(fs.host); if (fs.done) (void)hipEventDestroy(fs.done); }
+    for (auto& fs : c->slots) { release(fs.host); if (fs.done) (void)hipEventDestroy(fs.done); }
     if (c->host_poison) (void)hipHostFree(c->host_poison);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->ray_stream) { (void)hipStreamSynchronize(c->ray_stream); (void)hipStreamDestroy(c->ray_stream); }
-    if (c->ray_host) (void)hipHostFree(c->ray_host);
+    release(c->ray_host);
     if (c->rtt_frame_ev) (void)hipEventDestroy(c->rtt_frame_ev);
     if (c->rtt_done_ev) (void)hipEventDestroy(c->rtt_done_ev);
     for (int i = 0; i < 2; ++i) {
@@ -811,39 +627,9 @@ int swr_set_depth(swr_context* c, int x, int y, float d) {
 
 int swr_texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_texture** out) {
     SWR_ENTER(c);
-    if (!rgba8 || w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
-    if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
-    swr_texture* t = new swr_texture();
-    t->w = w; t->h = h;
-    hipError_t e = hipMalloc((void**)&t->d_rgba, (size_t)w * h * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(t->d_rgba, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-        if (t->d_rgba) (void)hipFree(t->d_rgba);
-        delete t;
-        c->err = std::string("texture upload failed: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
-    }
-    *out = t;
-    return SWR_OK;
+    return rgba8 ? texture_create(c, rgba8, w, h, out, "texture upload failed: ") : fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
 }
-
-int swr_texture_create_target(swr_context* c, int w, int h, swr_texture** out) {
-    SWR_ENTER(c);
-    if (w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
-    if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
-    swr_texture* t = new swr_texture();
-    t->w = w; t->h = h;
-    hipError_t e = hipMalloc((void**)&t->d_rgba, (size_t)w * h * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_rgba, 0, (size_t)w * h * 4, c->stream);
-    if (e != hipSuccess) {
-        if (t->d_rgba) (void)hipFree(t->d_rgba);
-        delete t;
-        c->err = std::string("texture allocation failed: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
-    }
-    *out = t;
-    return SWR_OK;
-}
+int swr_texture_create_target(swr_context* c, int w, int h, swr_texture** out) { SWR_ENTER(c); return texture_create(c, nullptr, w, h, out, "texture allocation failed: "); }
 
 int swr_texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
     if (!c) return SWR_ERR_INVALID_ARG;

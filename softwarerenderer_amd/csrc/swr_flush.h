@@ -259,8 +259,7 @@ int bin_and_raster(swr_context* c, Pass& P, uint32_t lo, uint32_t hi, bool count
         ca.dbg = d_total + 8;
         // (a multiple of 8 blocks: the kernel hands XCD x the x-th contiguous eighth of the blocks that hold pairs)
         const dim3 cg((unsigned)((((cover_items + (uint32_t)SWR_COVER_BLOCK - 1u) / (uint32_t)SWR_COVER_BLOCK) + 7u) & ~7u)), cb(SWR_COVER_BLOCK);
-        if (b.wireframe) hipLaunchKernelGGL(k_cover<true>, cg, cb, 0, F, ca);
-        else hipLaunchKernelGGL(k_cover<false>, cg, cb, 0, F, ca);
+        with_flag(b.wireframe, [&](auto wire) { hipLaunchKernelGGL(k_cover<decltype(wire)::value>, cg, cb, 0, F, ca); });
         SWR_HIP(c, hipGetLastError());
     }
     if (F != c->stream) {

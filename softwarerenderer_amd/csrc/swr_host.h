@@ -1,6 +1,7 @@
 // swr_host.h -- host side of libswr_hip.so: the context and batch types, device buffers, the frame-slot ring, band geometry,
-// timing spans and the front stream.  Included by swr_api.hip only (the library's one translation unit).
+// timing spans, the front stream, run-time values as kernel template arguments.  Included by swr_api.hip only (the library's one translation unit).
 #pragma once
+#include <type_traits>
 
 struct swr_mesh {
     float4* d_bounds = nullptr;               // Mesh.SphereBounds (ModelLoader.cs:291), computed on first use
@@ -44,7 +45,8 @@ struct EventSpan { int stage; hipEvent_t a, b; };
 #define SWR_HANDOVER_EVENT_FLAGS hipEventDisableTiming
 #endif
 #define SWR_SLOTS 3
-struct FrameSlot { void* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
+struct PinnedBuf { void* p = nullptr; size_t cap = 0; };      // a pinned host block (ensure_pinned)
+struct FrameSlot { PinnedBuf host; hipEvent_t done = nullptr; bool busy = false; };
 
 // Everything of a batch that its raster kernel reads (or that a front-end kernel and the raster kernel share).  With frames
 // pipelined two sets alternate per flush, so the front end of flush N+1 never writes what the raster kernel of flush N reads;
@@ -174,7 +176,7 @@ struct swr_context {
 
     hipStream_t ray_stream = nullptr;
     DevBuf d_ray, d_ray_best;                  // rays | targets | hit records; the pairs' keys, all SWR_RAY_NO_HIT between calls (k_ray_finish)
-    void* ray_host = nullptr; size_t ray_host_cap = 0;     // pinned staging block of small queries
+    PinnedBuf ray_host;                        // staging block of small queries
     DevBuf d_char;                             // swr_character_update: controllers | inputs | ring | targets | work | active | rays x 2 | results
 
     int profiling = 0;                         // 0 off, 1 every stage, 2 only the raster kernel (2 events per flush)
@@ -210,6 +212,23 @@ int ensure(swr_context* c, DevBuf& b, size_t bytes, bool zero_new = false) {
 }
 
 void release(DevBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+void release(PinnedBuf& b) { if (b.p) (void)hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
+
+// A pinned block of at least want_cap bytes (the old contents are not kept).  Sizing want_cap and what a failure means are the caller's.
+hipError_t ensure_pinned(PinnedBuf& b, size_t want_cap) {
+    if (b.cap >= want_cap) return hipSuccess;
+    release(b);
+    const hipError_t e = hipHostMalloc(&b.p, want_cap, hipHostMallocDefault);
+    if (e == hipSuccess) b.cap = want_cap; else b.p = nullptr;
+    return e;
+}
+// A run-time value that is a kernel's template argument: f gets it as a std::integral_constant (`decltype(x)::value` in a generic lambda).
+// The result type is stated, not deduced: deduction would instantiate f's kernels where the call stands, ahead of the frame's kernels.
+template <class R = void, class F> R with_flag(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class R = void, class F> R with_factor(int k, F&& f) {            // a resolve factor: 1, 2, 4 or 8 (resolve_factor_ok)
+    return k == 1 ? f(std::integral_constant<int, 1>{}) : k == 2 ? f(std::integral_constant<int, 2>{})
+         : k == 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 8>{});
+}
 
 // Frame-slot ring: a batch takes the next slot = {pinned staging block for its upload, completion event}.
 // Taking a slot first waits for the batch that used it SWR_SLOTS flushes ago, which (a) makes the pinned block
@@ -218,14 +237,8 @@ void release(DevBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0;
 void* slot_acquire(swr_context* c, size_t bytes) {
     FrameSlot& fs = c->slots[c->slot_next % SWR_SLOTS];
     if (fs.busy) { (void)hipEventSynchronize(fs.done); fs.busy = false; }
-    if (fs.cap < bytes) {
-        if (fs.host) (void)hipHostFree(fs.host);
-        fs.host = nullptr; fs.cap = 0;
-        size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-        if (hipHostMalloc(&fs.host, cap, hipHostMallocDefault) != hipSuccess) { fs.host = nullptr; return nullptr; }
-        fs.cap = cap;
-    }
-    return fs.host;
+    if (fs.host.cap < bytes && ensure_pinned(fs.host, std::max<size_t>(bytes + bytes / 2, 1 << 16)) != hipSuccess) return nullptr;
+    return fs.host.p;
 }
 void slot_submit(swr_context* c) {            // call after the batch's last launch
     FrameSlot& fs = c->slots[c->slot_next % SWR_SLOTS];

@@ -488,17 +488,20 @@ class MainWindow:
     def DepthBuffer(self) -> np.ndarray:
         return self._read(False, True)[1]
 
+    def _payload_out(self, shape, dtype, out, allow_none=True):
+        """The array a present or read-back fills: `out` held to the payload's shape and dtype, or a new one; makes the window current."""
+        if out is None and allow_none:
+            out = np.empty(shape, dtype=dtype)
+        elif out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        self._activate()
+        return out
+
     def FlatColorBuffer(self, out: Optional[np.ndarray] = None) -> np.ndarray:
         """The Vector3[] `flatColorBuffer` of MainWindow.OnRender (MainWindow.cs:234-240), flattened on the GPU.
         `out`: a caller-owned (rows, W, 3) float32 array to fill -- page-lock it once with Device.pin() and the copy runs
         at PCIe rate."""
-        _, rows = self.band_pixel_rows()
-        shape = (rows, max(self.RenderWidth, 0), 3)
-        if out is None:
-            out = np.empty(shape, dtype=np.float32)
-        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
-        self._activate()
+        out = self._payload_out((self.band_pixel_rows()[1], max(self.RenderWidth, 0), 3), np.float32, out)
         if out.size:
             self._dev._ck(self._dev._lib.swr_readback_rgb(self._dev._ctx, out.ctypes.data))
         return out
@@ -507,11 +510,7 @@ class MainWindow:
         """Asynchronous FlatColorBuffer (swr_present_rgb_async): flatten on the GPU behind the recorded draws, copy into `out`
         (page-lock it with Device.pin()) on the context's copy stream, return a ticket at once.  The next frame renders while this
         one crosses PCIe; `out` must stay untouched until PresentWait(ticket)."""
-        _, rows = self.band_pixel_rows()
-        shape = (rows, max(self.RenderWidth, 0), 3)
-        if out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
-        self._activate()
+        out = self._payload_out((self.band_pixel_rows()[1], max(self.RenderWidth, 0), 3), np.float32, out, allow_none=False)
         t = C.c_uint64(0)
         self._dev._ck(self._dev._lib.swr_present_rgb_async(self._dev._ctx, C.c_void_p(out.ctypes.data), C.byref(t)))
         return int(t.value)
@@ -550,13 +549,7 @@ class MainWindow:
         return self.band_pixel_rows()[1] // ky, w // kx
 
     def _resolved_out(self, kx, ky, out):
-        shape = self.ResolvedSize(kx, ky) + (3,)
-        if out is None:
-            out = np.empty(shape, dtype=np.float32)
-        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
-        self._activate()
-        return out
+        return self._payload_out(self.ResolvedSize(kx, ky) + (3,), np.float32, out)
 
     def ResolvedColorBuffer(self, kx: int, ky: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         """FlatColorBuffer of a window rendered at kx x ky times its size: every kx x ky block of the band box-filtered on the GPU
@@ -592,13 +585,7 @@ class MainWindow:
         return self.ResolvedSize(kx, ky) + (channels,)
 
     def _present8_out(self, kx, ky, channels, out):
-        shape = self.Present8Size(kx, ky, channels)
-        if out is None:
-            out = np.empty(shape, dtype=np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
-        self._activate()
-        return out
+        return self._payload_out(self.Present8Size(kx, ky, channels), np.uint8, out)
 
     def ColorBuffer8(self, kx: int = 1, ky: int = 1, channels: int = 3, out: Optional[np.ndarray] = None) -> np.ndarray:
         """The frame as the window's 8-bit framebuffer will hold it, quantised on the GPU (swr_readback_rgb8; the rule is in

@@ -14,6 +14,8 @@ after EVERY step every field of the state and of the trace is compared -- intege
   - beside the renderer: an update between two recorded draws leaves them one batch; an update beside a frame in flight makes no
     host wait on the frame's stream; both frames are the oracle's;
   - swr_raycast_nearest right after an update returns what it returned before (the key buffer is left clean);
+  - the staging threshold: 7000 controllers in one call (pageable host block) against the same in two calls of 3500 (pinned block),
+    byte for byte, with and without the trace, on a context of its own whose key buffer grows under the call;
   - arguments: the INVALID_ARG / UNSUPPORTED cases and the empty calls; the Python class against the restatement.
 
 Device mutants (one change in a scratch copy of csrc/, the product library rebuilt, this file run once on it) have NOT been run for
@@ -289,6 +291,59 @@ def test_the_key_buffer_is_left_clean(device, oracle_lib):
         after = Physics.RaycastNearest(case.origins, case.directions, ray_targets, case.mask)
         assert R.same_records(after, before) and int(before["found"].sum()) > 0
         assert R.same_records(Physics.RaycastBatch(case.origins, case.directions, ray_targets, case.mask), pairs)
+
+
+# ------------------------------------------------------------------------------------------------ the staging threshold
+RAY_TARGET_BYTES = 152                  # sizeof(RayTarget), csrc/swr_raycast.hip.h
+STAGED_BYTES = 1 << 20                  # a call of up to this many bytes, up and down together, goes through the pinned block
+
+
+def update_bytes(n, n_ring, n_targets):
+    """what swr_character_update moves with the trace on: controllers | inputs | ring | targets up, states | traces down"""
+    al = lambda b: (b + 15) & ~15
+    up = al(n * CHARACTER_DTYPE.itemsize) + al(n * CHARACTER_INPUT_DTYPE.itemsize) + al(n_ring * 8) + al(n_targets * RAY_TARGET_BYTES)
+    return up + al(n * CHARACTER_DTYPE.itemsize) + n * CHARACTER_TRACE_DTYPE.itemsize
+
+
+def test_across_the_staging_threshold():
+    """7000 controllers in one call are staged in pageable memory, the same controllers in two calls of 3500 in the pinned block: three
+    steps from the same states, byte for byte the same states and traces after each; once more without the trace (the shorter
+    download).  On a context of its own, so that the key buffer grows under this call: the 65-ray queries of
+    test_the_key_buffer_is_left_clean return afterwards what they returned before.
+
+    Two targets, the floor and the x wall: over the floor alone no slide ray can decide anything at any start height (chain 1 moves
+    straight down onto it and its lowest ray starts ActualStepSize above the capsule's foot, chain 2 runs parallel to it), and every
+    chain of the restatement stops with 1; with the wall the controllers near the corner stop with 2 from the second step on."""
+    assert update_bytes(7000, 18, 1) == 1064304 and update_bytes(3500, 18, 1) == 532304       # (one target: 144 bytes fewer)
+    assert update_bytes(7000, 18, 2) == 1064448 > STAGED_BYTES >= 532448 == update_bytes(3500, 18, 2)
+    targets, states, inputs = K.batch_case(7000, 2)
+    p, ring, half = K.params(), CharacterController.Ring(18), 3500
+    case = R.shape_case(65, 3)
+    dev = Device(0)
+    try:
+        with Uploaded(dev, case.targets) as ray_targets, Uploaded(dev, targets[:2]) as up:
+            before = Physics.RaycastNearest(case.origins, case.directions, ray_targets, case.mask)
+            pairs = Physics.RaycastBatch(case.origins, case.directions, ray_targets, case.mask)
+            assert int(before["found"].sum()) > 0
+            one, two, first = states.copy(), states.copy(), None
+            grounded = stopped = 0
+            for k in range(3):
+                tr = CharacterController.UpdateRaw(dev, p, one, inputs, 0.05, ring, up)
+                halves = [CharacterController.UpdateRaw(dev, p, two[a:a + half], inputs[a:a + half], 0.05, ring, up) for a in (0, half)]
+                assert one.tobytes() == two.tobytes(), f"states differ after step {k}"
+                assert tr.tobytes() == np.concatenate(halves).tobytes(), f"traces differ after step {k}"
+                grounded += int(tr["ground_found"].sum())
+                stopped += int((tr["chain_stop"] >= 2).any(axis=1).sum())
+                if first is None:
+                    first = one.copy()
+            assert grounded > 0 and stopped > 0, (grounded, stopped)         # rays were cast, and some of them decided something
+            bare = states.copy()
+            assert CharacterController.UpdateRaw(dev, p, bare, inputs, 0.05, ring, up, trace=False) is None
+            assert bare.tobytes() == first.tobytes()
+            assert R.same_records(Physics.RaycastNearest(case.origins, case.directions, ray_targets, case.mask), before)
+            assert R.same_records(Physics.RaycastBatch(case.origins, case.directions, ray_targets, case.mask), pairs)
+    finally:
+        dev.close()
 
 
 # ------------------------------------------------------------------------------------------------ arguments

@@ -15,6 +15,9 @@ anywhere: every record of every (ray, target) pair is compared -- found, target,
   - the renderer is not disturbed: a query between two recorded draws leaves them one batch; a query beside a frame in flight
     (pipelining 1, flushed, not synchronised) returns the same hits, makes no host wait on the frame's stream, and the frame is
     still the oracle's;
+  - the staging threshold: 7278 rays x 3 targets (1 048 496 bytes up and down: the largest such query staged in the pinned block) and
+    7280 (1 048 784: pageable) against the reference, swr_raycast_nearest on the 7280, and a 65-ray query repeated after the key buffer
+    has grown under it, on a context of its own;
   - arguments: the INVALID_ARG / UNSUPPORTED cases and the empty calls.
 
 Device mutants (one change in a scratch copy of csrc/, the product library rebuilt, this file run once on it) have NOT been run for
@@ -147,6 +150,63 @@ def test_nearest_over_targets(device, oracle_lib):
 def test_dust2(device, oracle_lib):
     got, _ = check(device, oracle_lib, "", R.dust2_case())
     assert got.shape == (42, 11) and int(got["found"].sum()) == 55 and bool(got["found"].any(axis=1).all())
+
+
+# ------------------------------------------------------------------------------------------------ the staging threshold
+RAY_TARGET_BYTES = 152                  # sizeof(RayTarget), csrc/swr_raycast.hip.h
+STAGED_BYTES = 1 << 20                  # a query of up to this many bytes, up and down together, goes through the pinned block
+
+
+def query_bytes(n_rays, n_targets, n_out):
+    """what swr_raycast / swr_raycast_nearest move: align16(rays) + align16(targets) up, the records down"""
+    al = lambda b: (b + 15) & ~15
+    return al(n_rays * RAY_DTYPE.itemsize) + al(n_targets * RAY_TARGET_BYTES) + n_out * RAY_HIT_DTYPE.itemsize
+
+
+@pytest.fixture(scope="module")
+def own_device():
+    """A context whose key buffer and staging blocks no earlier test has grown."""
+    dev = Device(0)
+    yield dev
+    dev.close()
+
+
+@pytest.fixture(scope="module")
+def small_query(own_device, oracle_lib):
+    """The 65-ray query of test_gpu_character.py::test_the_key_buffer_is_left_clean on the fresh context, taken BEFORE anything large."""
+    case = R.shape_case(65, 3)
+    with Uploaded(own_device, case) as targets:
+        near = Physics.RaycastNearest(case.origins, case.directions, targets, case.mask)
+        pairs = Physics.RaycastBatch(case.origins, case.directions, targets, case.mask)
+    assert R.same_records(pairs, R.reference(oracle_lib, "", case)) and int(near["found"].sum()) > 0
+    return case, near, pairs
+
+
+@pytest.mark.parametrize("n_rays,pinned", [(7278, True), (7280, False)], ids=["largest_pinned", "pageable"])
+def test_across_the_staging_threshold(own_device, oracle_lib, small_query, n_rays, pinned):
+    """7278 rays x 3 targets per pair is the largest query of that shape that is staged in the pinned block; 7280 goes through the
+    caller's memory.  Both against the reference, pair by pair; the small query taken before still returns the same records after the
+    key buffer has grown under it."""
+    assert RAY_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 40
+    total = query_bytes(n_rays, 3, 3 * n_rays)
+    assert total == (1048496 if pinned else 1048784) and (total <= STAGED_BYTES) == pinned
+    case = R.shape_case(n_rays, 3)
+    want = R.reference(oracle_lib, "", case)
+    assert int(want["found"].sum()) > 1000
+    with Uploaded(own_device, case) as targets:
+        got = Physics.RaycastBatch(case.origins, case.directions, targets, case.mask)
+        near = Physics.RaycastNearest(case.origins, case.directions, targets, case.mask) if not pinned else None
+    assert got.shape == want.shape
+    bad = [(r, t) for r in range(want.shape[0]) for t in range(3) if not R.same_records(got[r, t], want[r, t])]
+    assert not bad, f"{case.name}: {len(bad)} of {want.size} pairs differ, first {bad[:8]}"
+    if near is not None:
+        assert query_bytes(n_rays, 3, n_rays) <= STAGED_BYTES                    # (the same rays, 40 n bytes down: pinned)
+        badn = [r for r in range(n_rays) if not R.same_records(near[r], R.fold_nearest(got[r]))]
+        assert not badn, f"{case.name}: nearest is not the nearest of the pairs for {len(badn)} rays, first {badn[:8]}"
+    small, near65, pairs65 = small_query
+    with Uploaded(own_device, small) as targets:
+        assert R.same_records(Physics.RaycastNearest(small.origins, small.directions, targets, small.mask), near65)
+        assert R.same_records(Physics.RaycastBatch(small.origins, small.directions, targets, small.mask), pairs65)
 
 
 # ------------------------------------------------------------------------------------------------ numerics
