@@ -248,6 +248,16 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_program_validate(byte* fragmentSource, byte* log, int logLen);
         [DllImport(Lib)] public static extern int swr_program_create_vf(IntPtr ctx, byte* vertexSource, byte* fragmentSource, out int programId);
         [DllImport(Lib)] public static extern int swr_program_validate_vf(byte* vertexSource, byte* fragmentSource, byte* log, int logLen);
+        // post-process programs (swr.h: POST-PROCESS programs); format: 0 = three floats, 3 = RGB8, 4 = RGBX8
+        [DllImport(Lib)] public static extern int swr_post_create(IntPtr ctx, byte* source, out int postId);
+        [DllImport(Lib)] public static extern int swr_post_destroy(IntPtr ctx, int postId);
+        [DllImport(Lib)] public static extern int swr_post_set_constants(IntPtr ctx, int postId, float* values, int n);
+        [DllImport(Lib)] public static extern int swr_post_validate(byte* source, byte* log, int logLen);
+        [DllImport(Lib)] public static extern int swr_post_size(IntPtr ctx, int kx, int ky, int format, out int outWidth, out int outRows, out nuint outBytes);
+        [DllImport(Lib)] public static extern int swr_readback_post(IntPtr ctx, int postId, int kx, int ky, int format, void* bytes);
+        [DllImport(Lib)] public static extern int swr_present_post_async(IntPtr ctx, int postId, int kx, int ky, int format, void* bytes, out ulong ticket);
+        [DllImport(Lib)] public static extern int swr_post_device(IntPtr ctx, int postId, int kx, int ky, int format, IntPtr deviceBytes);
+        [DllImport(Lib)] public static extern int swr_post_device_async(IntPtr ctx, int postId, int kx, int ky, int format, IntPtr deviceBytes);
         [DllImport(Lib)] public static extern int swr_raycast(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
         [DllImport(Lib)] public static extern int swr_raycast_nearest(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
         [DllImport(Lib)] public static extern int swr_character_ray_counts(SwrCharacterParams* p, out int verticalSteps, out int horizontalRays);
@@ -864,6 +874,35 @@ namespace SoftwareRenderer
             SwrContext.Check(rc);
             return present8Buffers[prev];
         }
+        /// PresentAsync8 with a post-process program in front of the quantiser (build-defined; DESIGN.md section 20): starts frame i's
+        /// resolve + program + copy and returns the bytes of frame i - 1 (null on the very first call).  The program's constants are
+        /// captured by this call.  Shares PresentAsync8's buffers and the library's two present slots: a host uses one present in its loop.
+        public static byte[]? PresentPost(PostProgramNative post, int width, int height)
+        {
+            if (PresentBytes != 3 && PresentBytes != 4) throw new InvalidOperationException("set PresentBytes to 3 or 4 first");
+            int cur = present8Next, prev = present8Next ^ 1;
+            present8Next = prev;
+            int n = Math.Max(width, 0) * Math.Max(height, 0) * PresentBytes;
+            if (present8Buffers[cur] == null || present8Buffers[cur]!.Length != n)
+            {
+                if (present8Buffers[cur] != null) { SwrContext.Check(Native.swr_host_unregister(SwrContext.Handle, (void*)present8Pins[cur].AddrOfPinnedObject())); present8Pins[cur].Free(); }
+                present8Buffers[cur] = new byte[n];
+                present8Pins[cur] = Pin(present8Buffers[cur]!, (nuint)n);
+            }
+            byte* dst = (byte*)present8Pins[cur].AddrOfPinnedObject();
+            SwrContext.Check(Native.swr_present_post_async(SwrContext.Handle, post.Id, SuperSample, SuperSample, PresentBytes, dst, out present8Tickets[cur]));
+            if (present8Tickets[prev] == 0) return null;
+            int rc = Native.swr_present_wait(SwrContext.Handle, present8Tickets[prev]);
+            present8Tickets[prev] = 0;
+            if (rc == 1)        // SWR_STALE, as in PresentAsync8: take that frame synchronously (with the constants as they are now)
+            {
+                fixed (byte* p = present8Buffers[prev]!)
+                    SwrContext.Check(Native.swr_readback_post(SwrContext.Handle, post.Id, SuperSample, SuperSample, PresentBytes, p));
+                return present8Buffers[prev];
+            }
+            SwrContext.Check(rc);
+            return present8Buffers[prev];
+        }
         /// Full-precision read-back into the reference's own arrays (tools, screenshots).
         public static void Readback(Vector4[] colorBuffer, float[] depthBuffer)
         {
@@ -876,6 +915,36 @@ namespace SoftwareRenderer
             return h;
         }
         public static SwrStats Stats() { SwrContext.Check(Native.swr_get_stats(SwrContext.Handle, out SwrStats s)); return s; }
+    }
+
+    // ---------------------------------------------------------------- Post-process programs ----
+    // A per-pixel pass between the frame and its delivery, written against the contract of swr.h (swr_post) and compiled at run time;
+    // MainWindowNative.PresentPost runs it in front of the 8-bit quantiser.  INTEGRATION.md, "Porting a post-process pass".
+    public sealed unsafe class PostProgramNative : IDisposable
+    {
+        public int Id { get; private set; }
+        public PostProgramNative(string source)
+        {
+            byte[] src = System.Text.Encoding.UTF8.GetBytes(source + "\0");
+            byte[] log = new byte[1 << 16];
+            int rc;
+            fixed (byte* s = src) fixed (byte* l = log) rc = Native.swr_post_validate(s, l, log.Length);
+            if (rc == -1) throw new ArgumentException("post program does not compile:\n" + System.Text.Encoding.UTF8.GetString(log).TrimEnd('\0'));
+            if (rc != 0) throw new NotSupportedException($"swr_post_validate: {rc}");
+            int id;
+            fixed (byte* s = src) SwrContext.Check(Native.swr_post_create(SwrContext.Handle, s, out id));
+            Id = id;
+        }
+        /// Up to 64 floats the program reads as env.constants[i]; each present captures them when it is called.
+        public void SetConstants(ReadOnlySpan<float> values)
+        {
+            fixed (float* v = values) SwrContext.Check(Native.swr_post_set_constants(SwrContext.Handle, Id, v, values.Length));
+        }
+        public void Dispose()
+        {
+            if (Id != 0) Native.swr_post_destroy(SwrContext.Handle, Id);       // a present in flight with the program still completes
+            Id = 0;
+        }
     }
 
     // ---------------------------------------------------------------- Texture ----

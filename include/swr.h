@@ -438,6 +438,49 @@ int  swr_program_validate(const char* fragment_source, char* log, int log_len);
 int  swr_program_create_vf(swr_context* ctx, const char* vertex_source, const char* fragment_source, int* program_id);
 int  swr_program_validate_vf(const char* vertex_source, const char* fragment_source, char* log, int log_len);
 
+/* POST-PROCESS programs (build-defined: the reference presents the frame as rendered) ---------------------------------------------
+ * A user's per-pixel pass between the frame and its delivery -- a damage flash, a tone curve in front of the 8-bit quantiser, a
+ * vignette, a depth fog or outline, a small blur -- without the frame leaving the device (csrc/swr_post.hip.h is the prelude compiled
+ * in front of the text; INTEGRATION.md has a porting guide).  The text defines
+ *     __device__ float4 swr_post(const swr_post_in& in, const swr_post_env& env);
+ * and runs once per OUTPUT pixel of the present.  `in` = x, y (the output pixel, window coordinates after the resolve) and color (the
+ * resolved pixel: R, G, B exactly the floats swr_readback_rgb_resolved(kx, ky) delivers, the flatten's under (1, 1); A the frame's
+ * alpha through the same pairwise tree and scale).  `env` = width, height (the resolved size), kx, ky, constants[64].  Helpers:
+ * swr_post_fetch(env, x, y), the resolved RGBA of output pixel (x, y), and swr_post_depth(env, x, y), the depth word swr_get_depth
+ * returns for sample (x * kx, y * ky) -- the top-left sample of the pixel's block, not an average; float.MinValue where the depth
+ * plane was cleared -- both with x clamped to [0, width - 1] and y to [0, height - 1]; swr_lerp, swr_max, swr_clamp as in fragment
+ * programs.  There are no textures in a post program.  Compiled with this library's switches and its numerics model.
+ * What the result's x, y, z become (w is ignored): */
+enum { SWR_POST_RGB32F = 0,     /* three floats as they are, no clamp: the payload of swr_readback_rgb_resolved */
+       SWR_POST_RGB8 = 3,       /* the 8-bit present's quantiser (above), three bytes: the payload of swr_readback_rgb8(.., 3) */
+       SWR_POST_RGBX8 = 4 };    /* the same and a fourth byte of 255: the payload of swr_readback_rgb8(.., 4) */
+/* compile for this context's device.  Compile error -> SWR_ERR_INVALID_ARG with the compiler's log in swr_last_error(ctx), naming the
+ * caller's line as `post.hip:LINE:`; a text that does not define swr_post -> SWR_ERR_INVALID_ARG; libhiprtc not loadable ->
+ * SWR_ERR_UNSUPPORTED.  Post ids are not program ids of swr_render_mesh, and one context's id is unknown to every other context */
+int  swr_post_create(swr_context* ctx, const char* source, int* post_id);
+/* the id stops being valid; a present already enqueued with the program still completes (safe with a kernel in flight) */
+int  swr_post_destroy(swr_context* ctx, int post_id);
+/* up to 64 floats the program reads as env.constants[i] (the rest read 0).  A present takes a copy when it is CALLED: two
+ * presents in flight each keep their own */
+int  swr_post_set_constants(swr_context* ctx, int post_id, const float* values, int n);
+/* compile only, without a context or a device, as swr_program_validate */
+int  swr_post_validate(const char* source, char* log, int log_len);
+/* host only: swr_resolved_size plus out_bytes = out_rows * out_width * (12, 3 or 4 by format) */
+int  swr_post_size(swr_context* ctx, int kx, int ky, int format, int* out_width, int* out_rows, size_t* out_bytes);
+/* The four deliveries, each exactly as its 8-bit counterpart -- swr_readback_rgb8, swr_present_rgb8_async (the same two slots,
+ * tickets, staging buffers, swr_present_wait, staleness rule and back-pressure: all four kinds of present may alternate),
+ * swr_resolve_rgb8_device and its _async form (device destinations 4-byte aligned) -- with the program's result in the payload's
+ * place: recorded draws are flushed first, the _async forms never wait for the GPU, swr_set_stream and a bound framebuffer are
+ * honoured, a zero-size target is SWR_OK and writes nothing.
+ * SWR_ERR_INVALID_ARG: an unknown or destroyed id (or another context's), a format other than the three above, bad factors, a size
+ * the factors do not divide, NULL pointers.  SWR_ERR_UNSUPPORTED: the context holds only a band of its frame (swr_set_band*): a
+ * neighbour across the band's edge is not there.  Nothing is written then, no ticket is issued and the context stays usable.
+ * A program must terminate and read through the helpers only. */
+int  swr_readback_post(swr_context* ctx, int post_id, int kx, int ky, int format, void* out);
+int  swr_present_post_async(swr_context* ctx, int post_id, int kx, int ky, int format, void* out, uint64_t* ticket);
+int  swr_post_device(swr_context* ctx, int post_id, int kx, int ky, int format, void* d_out);
+int  swr_post_device_async(swr_context* ctx, int post_id, int kx, int ky, int format, void* d_out);
+
 int  swr_flush(swr_context* ctx);    /* execute recorded draws (asynchronous on the stream) */
 int  swr_sync(swr_context* ctx);     /* flush + wait for the stream */
 /* Frames in flight.  The reference's loop renders frames back to back (Renderer.cs:404-419: RenderScene per frame; Rasterizer.cs:

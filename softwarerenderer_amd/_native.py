@@ -24,6 +24,7 @@ SWR_ERR_OOM = -3
 SWR_ERR_NO_DEVICE = -4
 SWR_ERR_UNSUPPORTED = -5
 SWR_TEXTURE_ALPHA_OPAQUE, SWR_TEXTURE_ALPHA_KEEP = 0, 1     # swr_texture_update_from_frame
+SWR_POST_RGB32F, SWR_POST_RGB8, SWR_POST_RGBX8 = 0, 3, 4     # swr_readback_post & co: what a post program's result becomes
 SWR_STALE = 1          # swr_present_wait: not an error -- the copied frame predates a replayed batch, present again
 
 
@@ -114,6 +115,8 @@ EXPORTS = [
     "swr_resolved_size", "swr_readback_rgb_resolved", "swr_present_rgb_resolved_async", "swr_resolve_rgb_device", "swr_resolve_rgb_device_async",
     "swr_present8_size", "swr_readback_rgb8", "swr_present_rgb8_async", "swr_resolve_rgb8_device", "swr_resolve_rgb8_device_async",
     "swr_texture_create_target", "swr_texture_update_from_frame", "swr_texture_readback",
+    "swr_post_create", "swr_post_destroy", "swr_post_set_constants", "swr_post_validate", "swr_post_size",
+    "swr_readback_post", "swr_present_post_async", "swr_post_device", "swr_post_device_async",
 ]
 
 _libs = {}
@@ -216,6 +219,15 @@ def load(name: str = None) -> C.CDLL:
         "swr_texture_create_target": (I, [P, I, I, C.POINTER(P)]),
         "swr_texture_update_from_frame": (I, [P, P, P, I, I, I]),
         "swr_texture_readback": (I, [P, P, P]),
+        "swr_post_create": (I, [P, C.c_char_p, C.POINTER(I)]),
+        "swr_post_destroy": (I, [P, I]),
+        "swr_post_set_constants": (I, [P, I, fp, I]),
+        "swr_post_validate": (I, [C.c_char_p, C.c_char_p, I]),
+        "swr_post_size": (I, [P, I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_size_t)]),
+        "swr_readback_post": (I, [P, I, I, I, I, P]),
+        "swr_present_post_async": (I, [P, I, I, I, I, P, C.POINTER(C.c_uint64)]),
+        "swr_post_device": (I, [P, I, I, I, I, P]),
+        "swr_post_device_async": (I, [P, I, I, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

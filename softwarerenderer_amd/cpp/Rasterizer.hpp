@@ -143,6 +143,23 @@ inline swr_uniforms DefaultUniforms() {      // Renderer.cs:39-44
     return u;
 }
 
+// A post-process program (contract in swr.h: swr_post): a per-pixel pass between the frame and its delivery, compiled for `dev`.
+// Compile errors throw std::invalid_argument carrying the compiler's log (post.hip:LINE:).
+class PostProgram {
+public:
+    PostProgram(const Device& dev, const std::string& source) : dev_(dev) { dev_.check(swr_post_create(dev_.ctx(), source.c_str(), &id_)); }
+    ~PostProgram() { if (id_) swr_post_destroy(dev_.ctx(), id_); }            // a present in flight with the program still completes
+    PostProgram(const PostProgram&) = delete;
+    PostProgram& operator=(const PostProgram&) = delete;
+    void SetConstants(const std::vector<float>& values) const {               // captured by each present when it is called
+        dev_.check(swr_post_set_constants(dev_.ctx(), id_, values.empty() ? nullptr : values.data(), (int)values.size()));
+    }
+    int id() const { return id_; }
+private:
+    const Device& dev_;
+    int id_ = 0;
+};
+
 class MainWindow {                            // framebuffer part of MainWindow.cs
 public:
     MainWindow(const Device& dev, int renderWidth, int renderHeight) : dev_(dev) { Resize(renderWidth, renderHeight); }
@@ -159,6 +176,24 @@ public:
         if (color) color->resize(n * 4);
         if (depth) depth->resize(n);
         dev_.check(swr_readback(dev_.ctx(), color ? color->data() : nullptr, depth ? depth->data() : nullptr));
+    }
+    // The frame after `post`, resolved by kx x ky: format SWR_POST_RGB32F fills float triples, SWR_POST_RGB8 / SWR_POST_RGBX8 bytes
+    // (swr_readback_post); `out` is resized to swr_post_size's bytes
+    void PostBuffer(const PostProgram& post, int kx, int ky, int format, std::vector<unsigned char>* out) const {
+        int w = 0, rows = 0; size_t bytes = 0;
+        dev_.check(swr_post_size(dev_.ctx(), kx, ky, format, &w, &rows, &bytes));
+        out->resize(bytes);
+        if (bytes) dev_.check(swr_readback_post(dev_.ctx(), post.id(), kx, ky, format, out->data()));
+    }
+    // ... asynchronously into caller memory that stays put until PresentWait(ticket) (swr_present_post_async; shares the slots and
+    // tickets of every other present)
+    uint64_t PresentPostAsync(const PostProgram& post, int kx, int ky, int format, void* out) const {
+        uint64_t t = 0; dev_.check(swr_present_post_async(dev_.ctx(), post.id(), kx, ky, format, out, &t)); return t;
+    }
+    bool PresentWait(uint64_t ticket) const { int rc = swr_present_wait(dev_.ctx(), ticket); if (rc == SWR_STALE) return false; dev_.check(rc); return true; }
+    // ... or into caller DEVICE memory, 4-byte aligned (swr_post_device; wait = false: swr_post_device_async)
+    void PostTo(const PostProgram& post, int kx, int ky, int format, void* d_out, bool wait = true) const {
+        dev_.check(wait ? swr_post_device(dev_.ctx(), post.id(), kx, ky, format, d_out) : swr_post_device_async(dev_.ctx(), post.id(), kx, ky, format, d_out));
     }
     const Device& device() const { return dev_; }
     int RenderWidth = 0, RenderHeight = 0;

@@ -19,6 +19,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cmath>
 #include <cstdio>
@@ -45,6 +46,7 @@
 #include "swr_resolve.hip.h"
 #include "swr_present8.hip.h"
 #include "swr_rtt.hip.h"
+#include "swr_post.hip.h"
 
 using namespace swr;
 
@@ -67,23 +69,43 @@ int launch_flatten(swr_context* c, float* d_rgb, size_t n) {
 
 // What a present call delivers: the flatten (k_flatten_rgb, one RGB triple per band pixel), the kx x ky box-filter resolve
 // (k_resolve_rgb, one triple per kx x ky block of band pixels), or the resolve quantised to bytes (k_present8: RGB8 or RGBX8, factors
-// (1, 1) being the plain frame).  Every present shape below is defined once over this, in bytes of the payload's format.
+// (1, 1) being the plain frame) -- or, with a post-process program, what the program makes of the resolved frame (k_resolve_rgba unless
+// the factors are (1, 1), then the program's k_post), in any of the three formats.  Every present shape below is defined once over
+// this, in bytes of the payload's format.
 enum PayloadFormat { PAYLOAD_RGB32F, PAYLOAD_RGB8, PAYLOAD_RGBX8, PAYLOAD_NO_FORMAT };
-struct Payload { bool resolve; int kx, ky; PayloadFormat format; };
+struct Payload {
+    bool resolve; int kx, ky; PayloadFormat format;
+    bool posted = false;                 // swr_*_post*: `post` runs on the resolved frame ...
+    const PostProg* post = nullptr;      // ... (null: the id is unknown or destroyed); the context's table holds it for the call
+};
 constexpr Payload FLATTEN = {false, 1, 1, PAYLOAD_RGB32F};
 constexpr Payload resolved(int kx, int ky) { return Payload{true, kx, ky, PAYLOAD_RGB32F}; }
 constexpr Payload quantised(int kx, int ky, int bpp) { return Payload{true, kx, ky, bpp == 3 ? PAYLOAD_RGB8 : bpp == 4 ? PAYLOAD_RGBX8 : PAYLOAD_NO_FORMAT}; }
+// a post program by id and SWR_POST_* format
+Payload posted(const swr_context* c, int post_id, int kx, int ky, int format) {
+    Payload p{true, kx, ky, format == SWR_POST_RGB32F ? PAYLOAD_RGB32F : format == SWR_POST_RGB8 ? PAYLOAD_RGB8 : format == SWR_POST_RGBX8 ? PAYLOAD_RGBX8 : PAYLOAD_NO_FORMAT};
+    p.posted = true;
+    const auto it = c->posts.find(post_id);
+    if (it != c->posts.end()) p.post = it->second.get();
+    return p;
+}
 size_t payload_bpp(const Payload& p) { return p.format == PAYLOAD_RGB32F ? 12 : p.format == PAYLOAD_RGB8 ? 3 : 4; }
 
 bool resolve_factor_ok(int k) { return k == 1 || k == 2 || k == 4 || k == 8; }
 // a zero-size target resolves to nothing under any factor pair; otherwise the frame must divide (then every band's rows do too:
 // the factors divide the tile, and the last tile row holds H - 16 * (tiles_y - 1) pixel rows)
-int payload_check(swr_context* c, const Payload& p) {
+// (delivery false: swr_post_size, which names no program and sizes a band's payload like every *_size call)
+int payload_check(swr_context* c, const Payload& p, bool delivery = true) {
     if (!p.resolve) return SWR_OK;
-    if (p.format == PAYLOAD_NO_FORMAT) return fail(c, SWR_ERR_INVALID_ARG, "bpp must be 3 (RGB8) or 4 (RGBX8)");
+    if (p.format == PAYLOAD_NO_FORMAT)
+        return fail(c, SWR_ERR_INVALID_ARG, p.posted ? "format must be SWR_POST_RGB32F (0), SWR_POST_RGB8 (3) or SWR_POST_RGBX8 (4)" : "bpp must be 3 (RGB8) or 4 (RGBX8)");
     if (!resolve_factor_ok(p.kx) || !resolve_factor_ok(p.ky)) return fail(c, SWR_ERR_INVALID_ARG, "resolve factors must be 1, 2, 4 or 8");
+    if (p.posted && delivery && !p.post) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
     if (c->W <= 0 || c->H <= 0) return SWR_OK;
     if (c->W % p.kx || c->H % p.ky) return fail(c, SWR_ERR_INVALID_ARG, "the render target's width and height must be multiples of the resolve factors");
+    // a post program may fetch any pixel of the frame: a neighbour across a band's edge is not in this context
+    if (p.posted && delivery && (c->band_ty0 != 0 || band_rows(c) != c->H))
+        return fail(c, SWR_ERR_UNSUPPORTED, "the context holds only a band of its frame (swr_set_band*): post programs need the whole frame");
     return SWR_OK;
 }
 int payload_width(const swr_context* c, const Payload& p) { return std::max(0, c->W) / p.kx; }
@@ -114,8 +136,42 @@ int launch_present8(swr_context* c, const Payload& p, uint8_t* d_out) {
     return SWR_OK;
 }
 
+using ResolveRgbaKernel = void (*)(const float4*, float4*, uint32_t, uint32_t);
+ResolveRgbaKernel resolve_rgba_kernel(int kx, int ky) {
+    using K = ResolveRgbaKernel;
+    return with_factor<K>(kx, [&](auto x) -> K { return with_factor<K>(ky, [](auto y) -> K { return k_resolve_rgba<decltype(x)::value, decltype(y)::value>; }); });
+}
+
+// a post program's payload: the frame resolved into the context's RGBA plane (under (1, 1) the frame is that plane), then the
+// program's k_post over it, with the constants as they are now
+int launch_post(swr_context* c, const Payload& p, void* d_out) {
+    const uint32_t ow = (uint32_t)payload_width(c, p), orows = (uint32_t)payload_rows(c, p);    // a frame is at most 65535 x 65535
+    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
+    const dim3 grid((ow + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
+    const float4* plane = c->color;
+    if (p.kx != 1 || p.ky != 1) {
+        const size_t bytes = (size_t)ow * orows * sizeof(float4);
+        if (c->post_plane.cap < bytes) {
+            // growing frees the old block: an earlier present's k_post may still read it (first use / after a resize only)
+            SWR_HIP(c, hipStreamSynchronize(c->stream));
+            int rc = ensure(c, c->post_plane, bytes); if (rc) return rc;
+        }
+        hipLaunchKernelGGL(resolve_rgba_kernel(p.kx, p.ky), grid, block, 0, c->stream, (const float4*)c->color, c->post_plane.as<float4>(), ow, orows);
+        SWR_HIP(c, hipGetLastError());
+        plane = c->post_plane.as<float4>();
+    }
+    const float* depth = c->depth;
+    int kx = p.kx, ky = p.ky;
+    uint32_t w = ow, rows = orows;
+    PostConstants constants = p.post->constants;
+    void* args[] = { &plane, &depth, &d_out, &w, &rows, &kx, &ky, &constants };
+    SWR_HIP(c, hipModuleLaunchKernel(p.post->fn[p.format], grid.x, grid.y, 1, block.x, block.y, 1, 0, c->stream, args, nullptr));
+    return SWR_OK;
+}
+
 // the payload of the band's colour plane in device memory (4-byte aligned), on the context's stream (checked, and not empty)
 int launch_payload(swr_context* c, const Payload& p, void* d_out) {
+    if (p.posted) return launch_post(c, p, d_out);
     if (p.format != PAYLOAD_RGB32F) return launch_present8(c, p, (uint8_t*)d_out);
     float* d_rgb = (float*)d_out;
     if (!p.resolve) return launch_flatten(c, d_rgb, band_pixels(c));
@@ -128,14 +184,14 @@ int launch_payload(swr_context* c, const Payload& p, void* d_out) {
     return SWR_OK;
 }
 
-// swr_flatten_rgb_device / swr_resolve_rgb_device / swr_resolve_rgb8_device [_async].  Stream order puts the payload kernel after the frame's kernels; a batch that
+// swr_flatten_rgb_device / swr_resolve_rgb_device / swr_resolve_rgb8_device / swr_post_device [_async].  Stream order puts the payload kernel after the frame's kernels; a batch that
 // has to be replayed (optimistic flush) is replayed by the caller's swr_sync BEFORE the result is consumed -- and then the kernel must
 // run again, which sync does not know about: so `validate` first (cheap when nothing overflowed: one pinned-flag read after the stream
 // drains)
 int payload_device(swr_context* c, const Payload& p, void* d_out, bool validate) {
     if (!d_out) return fail(c, SWR_ERR_INVALID_ARG, "the device destination is null");
     // k_present8 stores whole dwords (the float kernels' float stores have always needed this much)
-    if (p.format != PAYLOAD_RGB32F && ((uintptr_t)d_out & 3u)) return fail(c, SWR_ERR_INVALID_ARG, "the device destination must be 4-byte aligned");
+    if ((p.format != PAYLOAD_RGB32F || p.posted) && ((uintptr_t)d_out & 3u)) return fail(c, SWR_ERR_INVALID_ARG, "the device destination must be 4-byte aligned");
     int rc = payload_check(c, p); if (rc) return rc;
     if ((rc = flush_locked(c))) return rc;
     if (!payload_pixels(c, p)) return SWR_OK;
@@ -143,7 +199,7 @@ int payload_device(swr_context* c, const Payload& p, void* d_out, bool validate)
     return launch_payload(c, p, d_out);
 }
 
-// swr_readback_rgb / swr_readback_rgb_resolved / swr_readback_rgb8: the payload into host memory (of any alignment: the copy comes
+// swr_readback_rgb / swr_readback_rgb_resolved / swr_readback_rgb8 / swr_readback_post: the payload into host memory (of any alignment: the copy comes
 // from the scratch block), between two host syncs
 int payload_readback(swr_context* c, const Payload& p, void* out) {
     if (!out) return fail(c, SWR_ERR_INVALID_ARG, "the destination is null");
@@ -157,7 +213,7 @@ int payload_readback(swr_context* c, const Payload& p, void* out) {
     return sync_locked(c);
 }
 
-// swr_present_rgb_async / swr_present_rgb_resolved_async / swr_present_rgb8_async: every kind shares the two slots, the tickets and
+// swr_present_rgb_async / swr_present_rgb_resolved_async / swr_present_rgb8_async / swr_present_post_async: every kind shares the two slots, the tickets and
 // the staging buffers (sized in bytes); a ticket does not say which kind it was
 int payload_present(swr_context* c, const Payload& p, void* out, uint64_t* ticket) {
     if (!out || !ticket) return fail(c, SWR_ERR_INVALID_ARG, "the destination or ticket is null");
@@ -283,6 +339,13 @@ int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, 
     }
     return SWR_OK;
 }
+
+// swr_program_validate* / swr_post_validate: the compiler's messages, NUL-terminated and truncated to the caller's buffer
+void copy_log(const std::string& msg, char* log, int log_len) {
+    if (!log || log_len <= 0) return;
+    const size_t n = std::min(msg.size(), (size_t)log_len - 1);
+    memcpy(log, msg.data(), n); log[n] = '\0';
+}
 }  // namespace
 
 extern "C" {
@@ -380,6 +443,7 @@ void swr_destroy(swr_context* c) {
     free_garbage(c);
     c->draws.clear();
     c->progs.clear();                        // (streams idle: the modules unload here)
+    c->posts.clear();
     for (swr_mesh* m : c->mesh_pool) destroy_mesh(m);
     c->mesh_pool.clear();
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
@@ -395,7 +459,7 @@ void swr_destroy(swr_context* c) {
         if (c->present_done[i]) (void)hipEventDestroy(c->present_done[i]);
         release(c->present_buf[i]);
     }
-    DevBuf* bufs[] = { &c->own_color, &c->own_depth, &c->d_slot_tb, &c->d_want, &c->d_ctrl, &c->d_pair_tile, &c->d_tile_list, &c->d_tile_stats,
+    DevBuf* bufs[] = { &c->post_plane, &c->own_color, &c->own_depth, &c->d_slot_tb, &c->d_want, &c->d_ctrl, &c->d_pair_tile, &c->d_tile_list, &c->d_tile_stats,
                        &c->d_counters, &c->d_total, &c->d_scratch, &c->d_ray, &c->d_ray_best, &c->d_char };
     for (DevBuf* b : bufs) release(*b);
     for (auto& s : c->sets) {
@@ -782,10 +846,7 @@ int swr_program_validate_vf(const char* vertex_src, const char* src, char* log, 
     std::shared_ptr<const RtcCode> code;
     std::string msg;
     const int rc = rtc_compile(vertex_src, src, code, msg);
-    if (log && log_len > 0) {
-        const size_t n = std::min(msg.size(), (size_t)log_len - 1);
-        memcpy(log, msg.data(), n); log[n] = '\0';
-    }
+    copy_log(msg, log, log_len);
     return rc;
 }
 
@@ -827,6 +888,77 @@ int swr_program_set_constants(swr_context* c, int program_id, const float* value
     float* k = it->second->constants;
     for (int i = 0; i < 64; ++i) k[i] = i < n ? values[i] : 0.0f;
     return SWR_OK;
+}
+
+int swr_post_validate(const char* src, char* log, int log_len) {
+    if (!src) return SWR_ERR_INVALID_ARG;
+    std::shared_ptr<const RtcCode> code;
+    std::string msg;
+    const int rc = rtc_compile_post(src, code, msg);
+    copy_log(msg, log, log_len);
+    return rc;
+}
+
+int swr_post_create(swr_context* c, const char* src, int* post_id) {
+    SWR_ENTER(c);
+    if (!src || !post_id) return fail(c, SWR_ERR_INVALID_ARG, "null argument to swr_post_create");
+    std::shared_ptr<const RtcCode> code;
+    std::string log;
+    const int rc = rtc_compile_post(src, code, log);
+    if (rc) { c->err = log; return rc; }
+    auto p = std::make_shared<PostProg>();
+    SWR_HIP(c, hipModuleLoadData(&p->mod, code->code.data()));
+    for (int k = 0; k < 3; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
+    static std::atomic<int> next_post{1};                   // one sequence for the process: another context's id is unknown here
+    const int id = next_post++;
+    c->posts[id] = std::move(p);
+    *post_id = id;
+    return SWR_OK;
+}
+
+int swr_post_destroy(swr_context* c, int post_id) {
+    SWR_ENTER(c);
+    auto it = c->posts.find(post_id);
+    if (it == c->posts.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
+    c->post_garbage.push_back(std::move(it->second));      // its k_post may be in flight: the module stays loaded until the streams are idle
+    c->posts.erase(it);
+    return SWR_OK;
+}
+
+int swr_post_set_constants(swr_context* c, int post_id, const float* values, int n) {
+    SWR_ENTER(c);
+    auto it = c->posts.find(post_id);
+    if (it == c->posts.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
+    if (n < 0 || n > SWR_POST_CONSTANTS || (n > 0 && !values)) return fail(c, SWR_ERR_INVALID_ARG, "between 0 and 64 constants");
+    float* k = it->second->constants.v;
+    for (int i = 0; i < SWR_POST_CONSTANTS; ++i) k[i] = i < n ? values[i] : 0.0f;
+    return SWR_OK;
+}
+
+int swr_post_size(swr_context* c, int kx, int ky, int format, int* out_width, int* out_rows, size_t* out_bytes) {
+    SWR_ENTER(c);
+    if (!out_width || !out_rows || !out_bytes) return fail(c, SWR_ERR_INVALID_ARG, "out_width, out_rows or out_bytes is null");
+    const Payload p = posted(c, 0, kx, ky, format);
+    int rc = payload_check(c, p, false); if (rc) return rc;
+    *out_width = payload_width(c, p); *out_rows = payload_rows(c, p); *out_bytes = payload_bytes(c, p);
+    return SWR_OK;
+}
+
+int swr_readback_post(swr_context* c, int post_id, int kx, int ky, int format, void* out) {
+    SWR_ENTER(c);
+    return payload_readback(c, posted(c, post_id, kx, ky, format), out);
+}
+int swr_present_post_async(swr_context* c, int post_id, int kx, int ky, int format, void* out, uint64_t* ticket) {
+    SWR_ENTER(c);
+    return payload_present(c, posted(c, post_id, kx, ky, format), out, ticket);
+}
+int swr_post_device(swr_context* c, int post_id, int kx, int ky, int format, void* d_out) {
+    SWR_ENTER(c);
+    return payload_device(c, posted(c, post_id, kx, ky, format), d_out, true);
+}
+int swr_post_device_async(swr_context* c, int post_id, int kx, int ky, int format, void* d_out) {
+    SWR_ENTER(c);
+    return payload_device(c, posted(c, post_id, kx, ky, format), d_out, false);
 }
 
 int swr_render_mesh_arrays(swr_context* c, const swr_vertex* v, int nv, const uint16_t* idx, int ni,

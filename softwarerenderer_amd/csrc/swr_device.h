@@ -6,7 +6,7 @@
 // -fhip-fp32-correctly-rounded-divide-sqrt); f32 denormals are kept (hipcc default).
 #pragma once
 
-#ifndef __HIPCC_RTC__               // (run-time compiled fragment programs: the prelude of swr_program.hip.h declares these)
+#ifndef __HIPCC_RTC__               // (run-time compiled user programs: swr_user_math.hip.h declares these)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #endif

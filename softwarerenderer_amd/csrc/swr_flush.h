@@ -37,6 +37,7 @@ void free_garbage(swr_context* c) {       // streams must be idle: nothing in fl
     for (swr_mesh* m : c->garbage) pool_mesh(c, m);
     c->garbage.clear();
     c->prog_garbage.clear();
+    c->post_garbage.clear();
     trim_mesh_pool(c);
 }
 

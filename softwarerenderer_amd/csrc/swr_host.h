@@ -76,6 +76,16 @@ struct UserProg {
     ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
 };
 
+// A post-process program loaded on the context's device (swr_post_create): k_post<SWR_POST_RGB32F / _RGB8 / _RGBX8> of its run-time
+// compiled code object (swr_post.hip.h).  A destroyed program is parked (post_garbage) until the streams are idle: a present enqueued
+// with it may still be running.
+struct PostProg {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn[3] = { nullptr, nullptr, nullptr };   // by PayloadFormat: RGB32F, RGB8, RGBX8
+    PostConstants constants = {};                           // swr_post_set_constants: passed by value to each launch
+    ~PostProg() { if (mod) (void)hipModuleUnload(mod); }
+};
+
 struct DrawCmd {
     DrawParams p;
     swr_mesh* mesh;
@@ -139,6 +149,10 @@ struct swr_context {
     std::map<int, std::shared_ptr<UserProg>> progs;     // live user programs by id (swr_program_create / _destroy)
     int next_prog = SWR_PROG_USER_BASE;
     std::vector<std::shared_ptr<UserProg>> prog_garbage; // programs of retired batches whose kernels may still run (see garbage)
+    std::map<int, std::shared_ptr<PostProg>> posts;     // live post-process programs by id (swr_post_create / _destroy)
+    std::vector<std::shared_ptr<PostProg>> post_garbage; // destroyed post programs whose kernel may still run (see garbage)
+    DevBuf post_plane;                        // the resolved RGBA plane k_resolve_rgba hands k_post (factors other than (1, 1)): allocated on
+                                              // first use, grown only with the stream idle; producer and consumer are both on `stream`
     std::vector<swr_mesh*> mesh_pool;         // transient meshes whose batches are KNOWN to be complete: their device buffers are handed to the
     size_t mesh_pool_bytes = 0;               // next swr_render_mesh_arrays call instead of hipFree / hipMalloc (both synchronise the device)
     uint64_t stale_dropped[2] = { 0, 0 };     // present tickets dropped by back-pressure whose pixels predate a replay (swr_present_wait reports them)

@@ -1,0 +1,117 @@
+// swr_post.hip.h -- post-process programs: a user's per-pixel pass between the frame and its delivery.
+//
+// Build-defined (the reference presents the frame as rendered, MainWindow.cs:234-240): the text a caller hands to swr_post_create
+// runs once per OUTPUT pixel of a present, on the resolved frame, and its result leaves the device in the present's format.
+//
+// THE DEFINITION (tests/post_cases.py restates it in numpy).  The user's text defines
+//     __device__ float4 swr_post(const swr_post_in& in, const swr_post_env& env);
+//   in.x, in.y    the output pixel, in window coordinates after the resolve
+//   in.color      the resolved pixel: R, G, B the floats swr_readback_rgb_resolved(kx, ky) delivers (the flatten's under (1, 1)), A the
+//                 frame's alpha through the same balanced pairwise tree and the same multiply by 1 / (kx ky) (resolve_rows4,
+//                 swr_rtt.hip.h)
+//   env.width, env.height   the resolved size;  env.kx, env.ky  the factors
+//   env.constants           64 floats, captured when the present call is made (swr_post_set_constants; zeros if never set)
+//   swr_post_fetch(env, x, y)   the resolved RGBA of output pixel (x, y), x clamped to [0, width - 1] and y to [0, height - 1]
+//   swr_post_depth(env, x, y)   the depth word of sample (x kx, y ky), the top-left sample of the pixel's block, clamped the same way;
+//                               not averaged; float.MinValue where the depth plane was cleared
+//   swr_lerp, swr_max, swr_clamp   swr_user_math.hip.h: the definitions fragment programs call
+// A post program has no textures.  What the result becomes:
+//   SWR_POST_RGB32F   x, y, z stored as they are (no clamp)
+//   SWR_POST_RGB8     quantise8 of x, y, z (swr_present8.hip.h), three bytes
+//   SWR_POST_RGBX8    the same and a fourth byte of 255, one dword
+//   w is ignored.
+//
+//   k_resolve_rgba<KX, KY>  (product library) one thread per OUTPUT pixel on k_resolve_rgb's plain 2-D grid (64 x 4 threads per block, no
+//                           stride loop): resolve_rows4 times 1 / (KX KY) into a window-sized float4 plane of the context.  Not launched
+//                           under (1, 1), where the frame is that plane already.  The plane is deliberate: a program that fetches
+//                           neighbours would otherwise redo a tree of up to 64 samples per tap.
+//   k_post<FORMAT>          (run-time compiled with the user's text, SWR_RTC_POST; three instantiations per program) the same grid: the
+//                           thread loads its pixel of the plane, calls the inlined swr_post and stores as k_resolve_rgb / k_present8 store.
+//                           The constants are a by-value kernel argument: no device buffer outlives the call.
+// No LDS, no scratch, no inline assembly.  A frame is at most 65535 x 65535 (swr_resize), so pixel indices fit 32 bits; offsets are size_t.
+#pragma once
+#include "swr_user_math.hip.h"
+#include "swr_rtt.hip.h"
+
+#define SWR_POST_CONSTANTS 64
+
+namespace swr {
+
+// k_post's last argument, by value: the program's constants as they were when the present call was made
+struct PostConstants { float v[SWR_POST_CONSTANTS]; };
+
+// color: the frame, out_w * KX pixels wide and out_rows * KY rows high; plane: out_rows x out_w float4
+template <int KX, int KY>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_resolve_rgba(const float4* __restrict__ color, float4* __restrict__ plane, uint32_t out_w, uint32_t out_rows) {
+    static_assert((KX == 1 || KX == 2 || KX == 4 || KX == 8) && (KY == 1 || KY == 2 || KY == 4 || KY == 8), "factors divide the tile");
+    const uint32_t ox = blockIdx.x * SWR_RESOLVE_BLOCK_X + threadIdx.x;
+    const uint32_t oy = blockIdx.y * SWR_RESOLVE_BLOCK_Y + threadIdx.y;
+    if (ox >= out_w || oy >= out_rows) return;
+    const size_t pitch = (size_t)out_w * KX;
+    const Rgba s = resolve_rows4<KX, KY>(color + (size_t)oy * KY * pitch + (size_t)ox * KX, pitch);
+    constexpr float scale = 1.0f / (float)(KX * KY);
+    plane[(size_t)oy * out_w + ox] = make_float4(s.r * scale, s.g * scale, s.b * scale, s.a * scale);
+}
+
+}  // namespace swr
+
+#ifdef SWR_RTC_POST
+struct swr_post_in {
+    int x, y;                    // the output pixel
+    float4 color;                // the resolved pixel: swr_post_fetch(env, x, y)
+};
+
+struct swr_post_env {
+    int width, height;           // the resolved size
+    int kx, ky;                  // the resolve factors
+    const float* constants;      // constants[0..63] (swr_post_set_constants when the present call was made; zeros if never set)
+    // the library's own, behind the helpers below:
+    const float4* plane_;        // height x width resolved pixels (the frame itself under (1, 1))
+    const float* depth_;         // the frame's depth plane, height * ky rows of width * kx words
+};
+
+__device__ __forceinline__ int swr_post_clamp_index(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
+__device__ __forceinline__ float4 swr_post_fetch(const swr_post_env& env, int x, int y) {
+    x = swr_post_clamp_index(x, env.width); y = swr_post_clamp_index(y, env.height);
+    return env.plane_[(size_t)y * (size_t)env.width + (size_t)x];
+}
+__device__ __forceinline__ float swr_post_depth(const swr_post_env& env, int x, int y) {
+    x = swr_post_clamp_index(x, env.width); y = swr_post_clamp_index(y, env.height);
+    return env.depth_[(size_t)y * (size_t)env.ky * ((size_t)env.width * (size_t)env.kx) + (size_t)x * (size_t)env.kx];
+}
+
+// the user's program (always inlined into k_post)
+__device__ __attribute__((always_inline)) float4 swr_post(const swr_post_in& in, const swr_post_env& env);
+
+namespace swr {
+
+// plane: out_rows x out_w resolved pixels; depth: the frame's depth plane; out: out_rows * out_w pixels of 12 (RGB32F), 3 or 4 bytes
+template <int FORMAT>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_post(const float4* __restrict__ plane, const float* __restrict__ depth, void* __restrict__ out, uint32_t out_w, uint32_t out_rows,
+            int kx, int ky, const PostConstants constants) {
+    static_assert(FORMAT == SWR_POST_RGB32F || FORMAT == SWR_POST_RGB8 || FORMAT == SWR_POST_RGBX8, "a present format");
+    const uint32_t ox = blockIdx.x * SWR_RESOLVE_BLOCK_X + threadIdx.x;
+    const uint32_t oy = blockIdx.y * SWR_RESOLVE_BLOCK_Y + threadIdx.y;
+    if (ox >= out_w || oy >= out_rows) return;
+    const swr_post_env env = { (int)out_w, (int)out_rows, kx, ky, constants.v, plane, depth };
+    const size_t pixel = (size_t)oy * out_w + ox;
+    const swr_post_in in = { (int)ox, (int)oy, plane[pixel] };
+    const float4 c = swr_post(in, env);
+    if constexpr (FORMAT == SWR_POST_RGB32F) {
+        float* o = static_cast<float*>(out) + pixel * 3;
+        o[0] = c.x; o[1] = c.y; o[2] = c.z;
+    } else {
+        const uint32_t px = quantise8(c.x) | quantise8(c.y) << 8 | quantise8(c.z) << 16 | 0xff000000u;
+        uint8_t* o = static_cast<uint8_t*>(out) + pixel * FORMAT;
+        if constexpr (FORMAT == SWR_POST_RGB8) {
+            o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
+        } else {
+            *reinterpret_cast<uint32_t*>(o) = px;
+        }
+    }
+}
+
+}  // namespace swr
+#endif

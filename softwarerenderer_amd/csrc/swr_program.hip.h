@@ -15,26 +15,12 @@
 // (Renderer.cs:830-846, k_vertex), as for SWR_PROG_DUST2_LAMBERT_FOG, and swr_fs_in::data4 reads (0, 0, 0, 0).
 #pragma once
 
-#ifdef __HIPCC_RTC__
-typedef __INT8_TYPE__ int8_t;
-typedef __UINT8_TYPE__ uint8_t;
-typedef __INT16_TYPE__ int16_t;
-typedef __UINT16_TYPE__ uint16_t;
-typedef __INT32_TYPE__ int32_t;
-typedef __UINT32_TYPE__ uint32_t;
-typedef __INT64_TYPE__ int64_t;
-typedef __UINT64_TYPE__ uint64_t;
-typedef __UINTPTR_TYPE__ uintptr_t;
-#ifndef offsetof
-#define offsetof(T, m) __builtin_offsetof(T, m)
-#endif
-#endif
-
 // include/swr.h calls the 48-byte input vertex `swr_vertex`, the name the contract gives the user's vertex function: in the code
 // object of a program with a vertex half the record goes by another name (only DrawParams::verts refers to it)
 #ifdef SWR_USER_VERTEX
 #define swr_vertex swr_vertex_record
 #endif
+#include "swr_user_math.hip.h"           // hiprtc's fixed-width types; swr_lerp, swr_max, swr_clamp (shared with swr_post.hip.h)
 #include "swr_raster.hip.h"
 #ifdef SWR_USER_VERTEX
 #undef swr_vertex
@@ -69,15 +55,8 @@ __device__ __forceinline__ float4 swr_sample(const swr_fs_env& env, float2 uv) {
     if (!swr_has_texture(env)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     return swr::texture_fetch(env.tex, env.tex_w, env.tex_h, uv.x, uv.y);
 }
-// the build's System.Numerics model (SWR_DOT_PAIRWISE / SWR_NUMERICS_FMA): Vector3.Dot, Lerp's a * (1 - t) + b * t
+// the build's System.Numerics model (SWR_DOT_PAIRWISE): Vector3.Dot.  (swr_lerp, swr_max and swr_clamp: swr_user_math.hip.h)
 __device__ __forceinline__ float swr_dot3(float3 a, float3 b) { return swr::dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
-__device__ __forceinline__ float swr_lerp(float a, float b, float t) { return swr::nm_lerp(a, b, t); }
-__device__ __forceinline__ float4 swr_lerp(float4 a, float4 b, float t) {
-    return make_float4(swr_lerp(a.x, b.x, t), swr_lerp(a.y, b.y, t), swr_lerp(a.z, b.z, t), swr_lerp(a.w, b.w, t));
-}
-// MathF.Max / Math.Clamp as .NET evaluates them
-__device__ __forceinline__ float swr_max(float a, float b) { return swr::mathf_max(a, b); }
-__device__ __forceinline__ float swr_clamp(float v, float lo, float hi) { return swr::math_clamp(v, lo, hi); }
 // a null result: nothing is written (and under BlendMode.None the row's early-out applies)
 __device__ __forceinline__ float4 swr_discard() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 

@@ -1,4 +1,5 @@
-// swr_rtc.h -- user programs: the run-time compiler behind swr_program_create / _validate.  Included by swr_api.hip only, after swr_host.h.
+// swr_rtc.h -- user programs: the run-time compiler behind swr_program_create / _validate and swr_post_create / _validate.  Included by
+// swr_api.hip only, after swr_host.h.
 #pragma once
 
 namespace {
@@ -43,39 +44,33 @@ const RtcLib& rtc_lib() {
     return lib;
 }
 
-// code object + mangled names: k_raster_c<SWR_PROG_CUSTOM> [EARLYOUT], then (vertex half only) k_vertex_user and k_setup
+// code object + mangled names, in the order of the unit's name expressions: k_raster_c<SWR_PROG_CUSTOM> [EARLYOUT], then (vertex half
+// only) k_vertex_user and k_setup; for a post program k_post<SWR_POST_RGB32F / _RGB8 / _RGBX8>
 struct RtcCode { std::vector<char> code; std::string names[4]; bool has_vertex = false; };
 
-// Compiles a user program (vertex_src null: the fragment half alone, over the built-in vertex stage) into a gfx950 code object: SWR_OK,
-// SWR_ERR_INVALID_ARG (log = the compiler's messages, which name the half as vertex.hip:LINE: / fragment.hip:LINE:) or
-// SWR_ERR_UNSUPPORTED.  In-process cache keyed by both texts (the switches are this library's own).
-int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<const RtcCode>& out, std::string& log) {
+// one translation unit for the run-time compiler: what rtc_compile and rtc_compile_post hand to rtc_build
+struct RtcUnit {
+    std::string key;                     // the in-process cache's key
+    std::string src;                     // prelude include, the user's text under its own file name, the kernels
+    std::vector<std::string> defines;    // on top of the Makefile's switches and this build's numerics model
+    std::vector<std::string> exprs;      // the kernels to look up, at most 4
+    bool has_vertex = false;
+};
+
+// Compiles a unit into a gfx950 code object: SWR_OK, SWR_ERR_INVALID_ARG (log = the compiler's messages) or SWR_ERR_UNSUPPORTED.
+// In-process cache keyed by the unit's key (the switches are this library's own).
+int rtc_build(const RtcUnit& u, std::shared_ptr<const RtcCode>& out, std::string& log) {
     const RtcLib& R = rtc_lib();
     if (!R.ok) { log = R.why; return SWR_ERR_UNSUPPORTED; }
 #if defined(SWR_RTC_FLAGS)
     static std::mutex mu;
     static std::map<std::string, std::shared_ptr<const RtcCode>> cache;
-    // (a fragment-only program's key is its text, so `create(fs)` and `create_vf(NULL, fs)` share an entry; '\1' cannot occur in either half's C++)
-    const std::string key = vertex_src ? std::string(vertex_src) + '\1' + user_src : std::string(user_src);
-    if (vertex_src && !strstr(vertex_src, "swr_vertex")) {
-        log = "vertex.hip: the vertex program must define `__device__ void swr_vertex(const swr_vs_in& in, const swr_vs_env& env, swr_vs_out& out)`";
-        return SWR_ERR_INVALID_ARG;
-    }
     {
         std::lock_guard<std::mutex> g(mu);
-        auto it = cache.find(key);
+        auto it = cache.find(u.key);
         if (it != cache.end()) { out = it->second; return SWR_OK; }
     }
-    // prelude (contract + helpers), the user's text under its own file name, then the kernel
-    // (with a vertex half: its text first, and behind the raster kernel the geometry header, which under SWR_USER_VERTEX defines
-    // k_vertex_user instead of k_vertex and a k_setup that carries data4.w through the clipper)
-    const std::string src = std::string("#include \"swr_program.hip.h\"\n") +
-                            (vertex_src ? std::string("#line 1 \"vertex.hip\"\n") + vertex_src + "\n" : std::string()) +
-                            "#line 1 \"fragment.hip\"\n" + user_src +
-                            "\n#line 1 \"swr_program_kernel\"\n#include \"swr_raster_c.hip.h\"\n" +
-                            (vertex_src ? "#include \"swr_geometry.hip.h\"\n" : "");
-    // the Makefile's code-generation switches, this build's System.Numerics model, and the fenced LDS hand-offs (the unfenced ones are
-    // verified per (hipcc, source) pair only, DESIGN.md section 8: a run-time compiled kernel is not that pair)
+    // the Makefile's code-generation switches and this build's System.Numerics model
     std::vector<std::string> opts;
     {
         const std::string f = SWR_RTC_FLAGS;
@@ -88,23 +83,18 @@ int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<co
             i = j + 1;
         }
     }
-    opts.push_back("-DSWR_RTC_PROGRAM=1");
-    opts.push_back("-DSWR_WAVE_LDS_FENCE=1");
     opts.push_back("-DSWR_NUMERICS_FMA=" SWR_STR(SWR_NUMERICS_FMA));
     opts.push_back("-DSWR_DOT_PAIRWISE=" SWR_STR(SWR_DOT_PAIRWISE));
-    if (vertex_src) opts.push_back("-DSWR_USER_VERTEX=1");
+    for (auto& d : u.defines) opts.push_back(d);
     std::vector<const char*> copts;
     for (auto& o : opts) copts.push_back(o.c_str());
-    const std::string expr[4] = { "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, false>",
-                                  "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, true>",
-                                  "swr::k_vertex_user", "swr::k_setup" };
-    const int n_expr = vertex_src ? 4 : 2;
+    const int n_expr = (int)u.exprs.size();
     hiprtcProgram prog = nullptr;
-    if (R.create(&prog, src.c_str(), "swr_user_program.hip", k_rtc_n_headers, k_rtc_headers, k_rtc_header_names) != HIPRTC_SUCCESS) {
+    if (R.create(&prog, u.src.c_str(), "swr_user_program.hip", k_rtc_n_headers, k_rtc_headers, k_rtc_header_names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return SWR_ERR_UNSUPPORTED;
     }
-    for (int k = 0; k < n_expr; ++k) R.add_name(prog, expr[k].c_str());
+    for (int k = 0; k < n_expr; ++k) R.add_name(prog, u.exprs[k].c_str());
     const hiprtcResult cr = R.compile(prog, (int)copts.size(), copts.data());
     size_t ls = 0;
     log.clear();
@@ -115,10 +105,10 @@ int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<co
     }
     auto code = std::make_shared<RtcCode>();
     bool ok = cr == HIPRTC_SUCCESS;
-    code->has_vertex = vertex_src != nullptr;
+    code->has_vertex = u.has_vertex;
     for (int k = 0; ok && k < n_expr; ++k) {
         const char* mangled = nullptr;
-        ok = R.lowered(prog, expr[k].c_str(), &mangled) == HIPRTC_SUCCESS && mangled;
+        ok = R.lowered(prog, u.exprs[k].c_str(), &mangled) == HIPRTC_SUCCESS && mangled;
         if (ok) code->names[k] = mangled;
     }
     size_t cs = 0;
@@ -128,7 +118,7 @@ int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<co
     if (ok) {
         // tools/custom_program_numbers.py: the code object as compiled, for its resource usage (never set in production)
         if (const char* dir = getenv("SWR_PROGRAM_DUMP_DIR")) {
-            const std::string path = std::string(dir) + "/swr_user_program_" + std::to_string(std::hash<std::string>()(key)) + ".co";
+            const std::string path = std::string(dir) + "/swr_user_program_" + std::to_string(std::hash<std::string>()(u.key)) + ".co";
             if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(code->code.data(), 1, code->code.size(), f); fclose(f); }
         }
     }
@@ -137,11 +127,57 @@ int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<co
         return SWR_ERR_INVALID_ARG;
     }
     std::lock_guard<std::mutex> g(mu);
-    out = cache.emplace(key, std::shared_ptr<const RtcCode>(code)).first->second;
+    out = cache.emplace(u.key, std::shared_ptr<const RtcCode>(code)).first->second;
     return SWR_OK;
 #else
-    (void)vertex_src; (void)user_src; (void)out;
+    (void)u; (void)out;
     return SWR_ERR_UNSUPPORTED;
 #endif
+}
+
+// A user program (vertex_src null: the fragment half alone, over the built-in vertex stage).  The compiler's messages name the half as
+// vertex.hip:LINE: / fragment.hip:LINE:.  Cached by both texts.
+int rtc_compile(const char* vertex_src, const char* user_src, std::shared_ptr<const RtcCode>& out, std::string& log) {
+    if (vertex_src && !strstr(vertex_src, "swr_vertex")) {
+        if (!rtc_lib().ok) { log = rtc_lib().why; return SWR_ERR_UNSUPPORTED; }
+        log = "vertex.hip: the vertex program must define `__device__ void swr_vertex(const swr_vs_in& in, const swr_vs_env& env, swr_vs_out& out)`";
+        return SWR_ERR_INVALID_ARG;
+    }
+    RtcUnit u;
+    // (a fragment-only program's key is its text, so `create(fs)` and `create_vf(NULL, fs)` share an entry; '\1' cannot occur in either half's C++)
+    u.key = vertex_src ? std::string(vertex_src) + '\1' + user_src : std::string(user_src);
+    // prelude (contract + helpers), the user's text under its own file name, then the kernel
+    // (with a vertex half: its text first, and behind the raster kernel the geometry header, which under SWR_USER_VERTEX defines
+    // k_vertex_user instead of k_vertex and a k_setup that carries data4.w through the clipper)
+    u.src = std::string("#include \"swr_program.hip.h\"\n") +
+            (vertex_src ? std::string("#line 1 \"vertex.hip\"\n") + vertex_src + "\n" : std::string()) +
+            "#line 1 \"fragment.hip\"\n" + user_src +
+            "\n#line 1 \"swr_program_kernel\"\n#include \"swr_raster_c.hip.h\"\n" +
+            (vertex_src ? "#include \"swr_geometry.hip.h\"\n" : "");
+    // the fenced LDS hand-offs (the unfenced ones are verified per (hipcc, source) pair only, DESIGN.md section 8: a run-time compiled
+    // kernel is not that pair)
+    u.defines = { "-DSWR_RTC_PROGRAM=1", "-DSWR_WAVE_LDS_FENCE=1" };
+    if (vertex_src) u.defines.push_back("-DSWR_USER_VERTEX=1");
+    u.exprs = { "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, false>",
+                "swr::k_raster_c<false, true, " SWR_STR(SWR_PROG_CUSTOM) ", -1, -1, true>" };
+    if (vertex_src) { u.exprs.push_back("swr::k_vertex_user"); u.exprs.push_back("swr::k_setup"); }
+    u.has_vertex = vertex_src != nullptr;
+    return rtc_build(u, out, log);
+}
+
+// A post-process program (swr_post_create / swr_post_validate): the contract and k_post of swr_post.hip.h in front of the user's text,
+// whose lines the compiler's messages name as post.hip:LINE:.  k_post has no LDS: neither SWR_RTC_PROGRAM nor the fences apply.
+int rtc_compile_post(const char* user_src, std::shared_ptr<const RtcCode>& out, std::string& log) {
+    if (!strstr(user_src, "swr_post")) {
+        if (!rtc_lib().ok) { log = rtc_lib().why; return SWR_ERR_UNSUPPORTED; }
+        log = "post.hip: the post program must define `__device__ float4 swr_post(const swr_post_in& in, const swr_post_env& env)`";
+        return SWR_ERR_INVALID_ARG;
+    }
+    RtcUnit u;
+    u.key = std::string("\2") + user_src;           // ('\2' cannot open a fragment or vertex text)
+    u.src = std::string("#include \"swr_post.hip.h\"\n#line 1 \"post.hip\"\n") + user_src + "\n";
+    u.defines = { "-DSWR_RTC_POST=1" };
+    u.exprs = { "swr::k_post<SWR_POST_RGB32F>", "swr::k_post<SWR_POST_RGB8>", "swr::k_post<SWR_POST_RGBX8>" };
+    return rtc_build(u, out, log);
 }
 }  // namespace

@@ -240,6 +240,34 @@ class Device:
         self._ck(self._lib.swr_sync(self._ctx))
 
 
+class PostProgram:
+    """A post-process program (swr_post_create): C++ defining `swr_post` (contract in include/swr.h), compiled for the device at
+    run time and run once per output pixel by MainWindow.PostBuffer / PresentPostAsync / PostTo.  A compile error raises
+    SwrError(SWR_ERR_INVALID_ARG) with the log, which names the text's lines as post.hip:LINE:."""
+
+    def __init__(self, device: Device, source: str, constants=None):
+        self._dev = device
+        self._id = None
+        pid = C.c_int(0)
+        device._ck(device._lib.swr_post_create(device._ctx, source.encode(), C.byref(pid)))
+        self._id = pid.value
+        if constants is not None:
+            self.SetConstants(constants)
+
+    def SetConstants(self, values):
+        """Up to 64 floats the program reads as env.constants[i] (the rest read 0); each present captures them when it is called."""
+        a = _f32(values if values is not None else [], None)
+        self._dev._ck(self._dev._lib.swr_post_set_constants(self._dev._ctx, self._id, _fptr(a) if a.size else None, int(a.size)))
+
+    def close(self):
+        """swr_post_destroy: a present already enqueued with the program still completes."""
+        if self._id is not None and self._dev._ctx:
+            self._dev._ck(self._dev._lib.swr_post_destroy(self._dev._ctx, self._id))
+        self._id = None
+
+    Dispose = close
+
+
 class Texture:
     """Texture(Image<Rgba32>), Texture.cs:31-68: RGBA8 pixels, nearest sampling with wrap."""
 
@@ -616,6 +644,44 @@ class MainWindow:
         """Quantise8To without the validation sync (swr_resolve_rgb8_device_async), as FlattenToAsync."""
         self._activate()
         self._dev._ck(self._dev._lib.swr_resolve_rgb8_device_async(self._dev._ctx, int(kx), int(ky), int(channels), C.c_void_p(device_ptr)))
+
+    @staticmethod
+    def _post_format(channels, dtype) -> int:
+        dt = np.dtype(dtype)
+        if dt == np.float32 and channels == 3:
+            return N.SWR_POST_RGB32F
+        if dt == np.uint8 and channels in (3, 4):
+            return N.SWR_POST_RGB8 if channels == 3 else N.SWR_POST_RGBX8
+        raise ValueError("a post program delivers (3, float32), (3, uint8) or (4, uint8)")
+
+    def PostBuffer(self, post: PostProgram, kx: int = 1, ky: int = 1, channels: int = 3, dtype=np.uint8,
+                   out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The frame after `post` (swr_readback_post): the program runs once per pixel of the resolved frame and its result is
+        delivered as ResolvedColorBuffer delivers (float32, unclamped) or as ColorBuffer8 does (uint8, 3 or 4 channels)."""
+        fmt = self._post_format(channels, dtype)
+        out = self._payload_out(self.ResolvedSize(kx, ky) + (channels,), np.dtype(dtype), out)
+        if out.size:
+            self._dev._ck(self._dev._lib.swr_readback_post(self._dev._ctx, post._id, int(kx), int(ky), fmt, out.ctypes.data))
+        return out
+
+    def PresentPostAsync(self, post: PostProgram, out: np.ndarray, kx: int = 1, ky: int = 1) -> int:
+        """PresentAsync with the program's result (swr_present_post_async); out's dtype and last axis select the format.  Shares
+        PresentAsync's two slots; PresentWait serves the ticket.  The program's constants are captured by this call."""
+        if getattr(out, "ndim", 0) != 3:
+            raise ValueError("out must be a float32 array of shape (rows, width, 3) or a uint8 one of (rows, width, 3 or 4)")
+        fmt = self._post_format(int(out.shape[-1]), out.dtype)
+        out = self._payload_out(self.ResolvedSize(kx, ky) + (int(out.shape[-1]),), out.dtype, out, allow_none=False)
+        t = C.c_uint64(0)
+        self._dev._ck(self._dev._lib.swr_present_post_async(self._dev._ctx, post._id, int(kx), int(ky), fmt, C.c_void_p(out.ctypes.data), C.byref(t)))
+        return int(t.value)
+
+    def PostTo(self, post: PostProgram, device_ptr: int, kx: int = 1, ky: int = 1, channels: int = 3, dtype=np.uint8, wait: bool = True):
+        """PostBuffer into caller-owned DEVICE memory (4-byte aligned; swr_post_device); completes with Device.sync().  wait=False:
+        without the validation sync (swr_post_device_async), as FlattenToAsync."""
+        fmt = self._post_format(channels, dtype)
+        self._activate()
+        fn = self._dev._lib.swr_post_device if wait else self._dev._lib.swr_post_device_async
+        self._dev._ck(fn(self._dev._ctx, post._id, int(kx), int(ky), fmt, C.c_void_p(device_ptr)))
 
     def Upload(self, color=None, depth=None):
         self._activate()
