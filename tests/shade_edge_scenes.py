@@ -603,6 +603,37 @@ def in_range(v, lo=2.0 ** -40, hi=2.0 ** 40):
     return (a >= F32(lo)) & (a <= F32(hi))
 
 
+class Weights:
+    """The head of Interpolate (Rasterizer.cs:576-585) for the covered samples of one (triangle, tile rect): the three weights
+    w * invArea (:498-500), each over its output's clip.w, their sum, its reciprocal and the normalised weights; `persp` is the
+    perspective-correct sum of a Vector2/3/4 member (:587-640), `bary` the weighted sum of a Data key (:680-693).  Shared by Shaded
+    and by program_probe_cases.fs_in_reference.  Call it under np.errstate(all="ignore")."""
+
+    def __init__(self, tri, rect, cw):
+        self.inside, self.depth, w = tri.cover(rect)
+        self.wf = (w * tri.inv_area).astype(F32)[:, self.inside]          # :498-500
+        self.cw = cw
+        wf = self.wf
+        self.ra, self.rb, self.rc = wf[0] / cw[0], wf[1] / cw[1], wf[2] / cw[2]          # :576-578
+        self.inv_sum = (self.ra + self.rb) + self.rc
+        self.w = F32(1.0) / self.inv_sum
+        self.wa, self.wb, self.wc = self.ra * self.w, self.rb * self.w, self.rc * self.w
+
+    def persp(self, a, b, c):
+        return ((a * self.ra + b * self.rb) + c * self.rc) * self.w
+
+    def bary(self, a, b, c):
+        return (a * self.wa + b * self.wb) + c * self.wc
+
+    def world_normal(self, wn3):
+        """InterpolateData of the Vector3 key (:680-688) from the three outputs' world normals (3, 3): (components, len_sq)."""
+        n = [self.bary(wn3[0][i], wn3[1][i], wn3[2][i]) for i in range(3)]
+        len_sq = dot3(n, n)
+        renorm = len_sq > F32(1e-6)                                        # :684-688
+        s = F32(1.0) / np.sqrt(len_sq)
+        return [np.where(renorm, c * s, c) for c in n], len_sq
+
+
 class Shaded:
     """Interpolate + the fragment program for the covered samples of one (triangle, tile rect), with every intermediate the
     fast shaders' `safe` terms look at.  A, B, C = outputs[0..2] = vertices v2, v1, v0 of the triangle."""
@@ -614,34 +645,19 @@ class Shaded:
     def _run(self, draw, stage, vidx, tri, rect, tex, bilinear):
         clip, wnv, wposv = stage
         o = [int(vidx[2]), int(vidx[1]), int(vidx[0])]
-        inside, depth, w = tri.cover(rect)
-        self.inside, self.depth = inside, depth
-        wf = (w * tri.inv_area).astype(F32)[:, inside]                    # :498-500
-        self.wf = wf
-        nfrag = wf.shape[1]
         cw = clip[o, 3]
-        self.cw = cw
+        k = Weights(tri, rect, cw)
+        self.inside, self.depth, self.wf, self.cw, self.inv_sum = k.inside, k.depth, k.wf, cw, k.inv_sum
+        nfrag = k.wf.shape[1]
         u = draw.uniforms
         one = F32(1.0)
-        ra, rb, rc = wf[0] / cw[0], wf[1] / cw[1], wf[2] / cw[2]          # :576-578
-        inv_sum = (ra + rb) + rc
-        w_ = one / inv_sum
-        self.inv_sum = inv_sum
-        def persp(a, b, c):
-            return ((a * ra + b * rb) + c * rc) * w_
+        persp, bary = k.persp, k.bary
         V = draw.vertices
         uv, col = V["uv"][o].astype(F32), V["color"][o].astype(F32)
         tu, tv = persp(uv[0, 0], uv[1, 0], uv[2, 0]), persp(uv[0, 1], uv[1, 1], uv[2, 1])
         color = np.stack([persp(col[0, i], col[1, i], col[2, i]) for i in range(4)], axis=1)
         self.clip_z = persp(clip[o[0], 2], clip[o[1], 2], clip[o[2], 2])
-        wa, wb, wc = ra * w_, rb * w_, rc * w_
-        def bary(a, b, c):
-            return (a * wa + b * wb) + c * wc
-        n = [bary(wnv[o[0], i], wnv[o[1], i], wnv[o[2], i]) for i in range(3)]
-        self.len_sq = dot3(n, n)
-        renorm = self.len_sq > F32(1e-6)                                   # :684-688
-        s = one / np.sqrt(self.len_sq)
-        n = [np.where(renorm, c * s, c) for c in n]
+        n, self.len_sq = k.world_normal(wnv[o])
         wp = [bary(wposv[o[0], i], wposv[o[1], i], wposv[o[2], i]) for i in range(3)]
         self.tx = self.ty = np.zeros(nfrag, np.int64)
         if tex is None:
