@@ -254,14 +254,14 @@ def constants_scene(W=192, H=96):
     return scenes.Scene("probe_constants", W, H, draws, clear_color=CLEAR, near_clip=NEAR)
 
 
-def expected_flat(scene, words_of):
+def expected_flat(scene, words_of, tris=None):
     """(colour, covered samples) of a frame in which every covered pixel of a triangle shows the three words words_of(ProbeTri) (bit
     patterns kept, NaN payloads included) and w = 1, every other pixel the clear colour."""
     out = np.empty((scene.height, scene.width, 4), dtype=F32)
     out[...] = np.asarray(scene.clear_color, dtype=F32)
     bits = out.view(np.uint32)
     count = np.zeros((scene.height, scene.width), dtype=np.int32)
-    for t in probe_tris(scene):
+    for t in (probe_tris(scene) if tris is None else tris):
         w = np.concatenate([np.asarray(words_of(t), dtype=F32).reshape(3), np.ones(1, F32)]).view(np.uint32)
         for sX, eX, sY, eY in t.rects():
             with np.errstate(all="ignore"):
@@ -307,8 +307,8 @@ VARYINGS = ("color", "uv", "normal", "wn")
 @dataclasses.dataclass
 class ProbeTri:
     """One triangle as DrawTriangle receives it.  `out` = its three outputs IN THE ORDER outputs[0..2] = (v2, v1, v0) (:367), per
-    member a (3, k) float32 array: clip, color, uv, normal, wn.  fan = None for a triangle the clipper never saw, else the index
-    triple (0, k, k + 1) into the clipped polygon of `n_poly` vertices."""
+    member a (3, k) float32 array: clip, color, uv, normal, wn and, from a user vertex stage, data4.  fan = None for a triangle the
+    clipper never saw, else the index triple (0, k, k + 1) into the clipped polygon of `n_poly` vertices."""
     draw: int
     index: int                  # triangle number inside the draw
     vid: tuple
@@ -322,23 +322,30 @@ class ProbeTri:
             return [r for _, _, r in self.tri.tiles() if self.tri.cover(r)[0].any()]
 
 
-def probe_tris(scene):
-    """Every triangle of the scene that is drawn, after the near clipper and its fan (0, k, k + 1) (Rasterizer.cs:200-223)."""
+def probe_tris(scene, vertex_stage=None, fused=False):
+    """Every triangle of the scene that is drawn, after the near clipper and its fan (0, k, k + 1) (Rasterizer.cs:200-223).
+    vertex_stage: None = Renderer.VertexShader (S.vertex_stage and the input arrays), else a callable (draw index, draw) -> the
+    per-vertex outputs {clip, color, uv, normal, wn, data4} of a user vertex program (tests/vertex_probe_cases.py): data4 then goes
+    through the clipper as one more varying.  fused: the clipper's lerp of a SWR_NUMERICS_FMA build."""
     out = []
     near = F32(scene.near_clip)
     for j, d in enumerate(scene.draws):
-        clip, wn, _ = S.vertex_stage(d)
-        V = d.vertices
+        if vertex_stage is None:
+            clip, wn, _ = S.vertex_stage(d)
+            V = d.vertices
+            stage = {"clip": clip, "color": V["color"].astype(F32), "uv": V["uv"].astype(F32), "normal": V["normal"].astype(F32), "wn": wn}
+        else:
+            stage = {k: np.asarray(v, dtype=F32) for k, v in vertex_stage(j, d).items()}
+        keys = [k for k in stage if k != "clip"]
         for i, vid in enumerate(d.indices.reshape(-1, 3)):
             vid = [int(v) for v in vid]
-            poly = {"clip": clip[vid], "color": V["color"][vid].astype(F32), "uv": V["uv"][vid].astype(F32),
-                    "normal": V["normal"][vid].astype(F32), "wn": wn[vid]}
+            poly = {k: v[vid] for k, v in stage.items()}
             ec = G.enters_clipper(poly["clip"])
             if ec is None:
                 continue
             fans, n_poly = [None], 0
             if ec:
-                c = G.clip_near(poly["clip"], {k: poly[k] for k in VARYINGS}, near, False)
+                c = G.clip_near(poly["clip"], {k: poly[k] for k in keys}, near, fused)
                 poly = dict(c.vary, clip=c.clips)
                 fans, n_poly = c.fans, c.n
             for f in fans:
@@ -362,6 +369,8 @@ def texture_words(scene, d):
     return (-w if blocked else w), (-h if scene.bilinear else h), 1, w, h
 
 
+# wrong restatements of what a user vertex stage hands over (tests/test_vertex_probe_host.py)
+VERTEX_MUTANTS = ("data4_w_from_z", "normal_world_normal_swapped", "tex_y_from_wn_x", "data4_renormalised")
 MUTANTS = ("clip_w_affine", "barycentric_z_from_sum", "screen_y_from_x", "normal_from_world_normal", "world_normal_always_renormalised")
 
 
@@ -369,10 +378,20 @@ def fs_in_reference(scene, draw, tri, rect, mutant=None):
     """name -> float32 array over the covered samples of (tri, rect), row-major, for every name of TABLE; plus `inside` (the rect's
     coverage mask), `depth`, `weights` (3, n), `len_sq`, `affine_tex_coord.x` and, with a texture, sample.x .. sample.w.
     Rasterizer.Interpolate (Rasterizer.cs:566-693) in the operation order of interpolate_fs_in (csrc/swr_program.hip.h).
-    mutant: one of MUTANTS, a deliberately wrong restatement (tests/test_program_probe_host.py)."""
-    assert mutant is None or mutant in MUTANTS
+    data4: the outputs' own (tri.out["data4"], from a user vertex stage) summed as (a wa + b wb) + c wc, zeros without one.
+    mutant: one of MUTANTS or VERTEX_MUTANTS, a deliberately wrong restatement (tests/test_program_probe_host.py,
+    tests/test_vertex_probe_host.py)."""
+    assert mutant is None or mutant in MUTANTS + VERTEX_MUTANTS
     d = scene.draws[draw]
     t, o = tri.tri, tri.out
+    if mutant in VERTEX_MUTANTS:
+        o = {k: v.copy() for k, v in o.items()}
+        if mutant == "data4_w_from_z":
+            o["data4"][:, 3] = o["data4"][:, 2]
+        elif mutant == "normal_world_normal_swapped":
+            o["normal"], o["wn"] = o["wn"], o["normal"]
+        elif mutant == "tex_y_from_wn_x":
+            o["uv"][:, 1] = o["wn"][:, 0]
     one = F32(1.0)
     with np.errstate(all="ignore"):
         k = S.Weights(t, rect, o["clip"][:, 3])                            # :576-585
@@ -397,7 +416,13 @@ def fs_in_reference(scene, draw, tri, rect, mutant=None):
             raw = [k.bary(o["wn"][0][i], o["wn"][1][i], o["wn"][2][i]) for i in range(3)]
             wn = [c * (one / np.sqrt(len_sq)) for c in raw]
         uv = member(o["uv"])
-        values = clip + member(o["color"]) + uv + normal + screen + bary + wn + [np.zeros(n, F32)] * 4      # data4: no vertex half
+        if "data4" in o:                                                   # Vector4 key: weighted sum, nothing else (:690-693)
+            data4 = [k.bary(o["data4"][0][i], o["data4"][1][i], o["data4"][2][i]) for i in range(4)]
+            if mutant == "data4_renormalised":
+                data4[:3] = [c * (one / np.sqrt(S.dot3(data4[:3], data4[:3]))) for c in data4[:3]]
+        else:
+            data4 = [np.zeros(n, F32)] * 4                                 # no vertex half
+        values = clip + member(o["color"]) + uv + normal + screen + bary + wn + data4
         for (name, _), v in zip(FS_IN, values):
             r[name] = np.asarray(v, dtype=F32)
         r["len_sq"] = len_sq
