@@ -258,6 +258,9 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_present_post_async(IntPtr ctx, int postId, int kx, int ky, int format, void* bytes, out ulong ticket);
         [DllImport(Lib)] public static extern int swr_post_device(IntPtr ctx, int postId, int kx, int ky, int format, IntPtr deviceBytes);
         [DllImport(Lib)] public static extern int swr_post_device_async(IntPtr ctx, int postId, int kx, int ky, int format, IntPtr deviceBytes);
+        // post programs and textures (swr.h: TEXTURES): four slots per program, and a pass's result into a texture
+        [DllImport(Lib)] public static extern int swr_post_set_texture(IntPtr ctx, int postId, int slot, IntPtr texture);
+        [DllImport(Lib)] public static extern int swr_texture_update_from_post(IntPtr ctx, IntPtr texture, IntPtr sourceCtx, int postId, int kx, int ky, int alphaMode);
         [DllImport(Lib)] public static extern int swr_raycast(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
         [DllImport(Lib)] public static extern int swr_raycast_nearest(IntPtr ctx, SwrRay* rays, int nRays, SwrRayTarget* targets, int nTargets, int flags, SwrRayHit* hits);
         [DllImport(Lib)] public static extern int swr_character_ray_counts(SwrCharacterParams* p, out int verticalSteps, out int horizontalRays);
@@ -940,6 +943,12 @@ namespace SoftwareRenderer
         {
             fixed (float* v = values) SwrContext.Check(Native.swr_post_set_constants(SwrContext.Handle, Id, v, values.Length));
         }
+        /// Bind a texture to slot 0 .. 3 (null unbinds): the program reads it with swr_post_sample / swr_post_texel.  Each present
+        /// captures the four slots, and each texture's filter, when it is called.
+        public void SetTexture(int slot, TextureNative? texture)
+        {
+            SwrContext.Check(Native.swr_post_set_texture(SwrContext.Handle, Id, slot, texture?.Handle ?? IntPtr.Zero));
+        }
         public void Dispose()
         {
             if (Id != 0) Native.swr_post_destroy(SwrContext.Handle, Id);       // a present in flight with the program still completes
@@ -986,6 +995,14 @@ namespace SoftwareRenderer
         public void UpdateFrom(int kx = 1, int ky = 1, bool keepAlpha = false, IntPtr sourceContext = default)
         {
             SwrContext.Check(Native.swr_texture_update_from_frame(SwrContext.Handle, Handle, sourceContext, kx, ky, keepAlpha ? 1 : 0));
+        }
+
+        /// A pass's result into the texture: UpdateFrom with `post` -- a program of the source context -- between the resolve and the
+        /// quantiser; alpha 255, or the quantised w of the program's result with keepAlpha.  The texture may not be bound to a slot
+        /// of `post`.  A chain of passes is a sequence of calls: pass 1 writes A, pass 2 samples A (swr_texture_update_from_post).
+        public void UpdateFromPost(PostProgramNative post, int kx = 1, int ky = 1, bool keepAlpha = false, IntPtr sourceContext = default)
+        {
+            SwrContext.Check(Native.swr_texture_update_from_post(SwrContext.Handle, Handle, sourceContext, post.Id, kx, ky, keepAlpha ? 1 : 0));
         }
 
         /// The RGBA8 texels, row-major, Width * Height * 4 bytes; waits for the GPU (screenshots, tests).

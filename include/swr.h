@@ -449,8 +449,18 @@ int  swr_program_validate_vf(const char* vertex_source, const char* fragment_sou
  * swr_post_fetch(env, x, y), the resolved RGBA of output pixel (x, y), and swr_post_depth(env, x, y), the depth word swr_get_depth
  * returns for sample (x * kx, y * ky) -- the top-left sample of the pixel's block, not an average; float.MinValue where the depth
  * plane was cleared -- both with x clamped to [0, width - 1] and y to [0, height - 1]; swr_lerp, swr_max, swr_clamp as in fragment
- * programs.  There are no textures in a post program.  Compiled with this library's switches and its numerics model.
- * What the result's x, y, z become (w is ignored): */
+ * programs.  Compiled with this library's switches and its numerics model.
+ * TEXTURES: a program has SWR_POST_TEXTURES slots (swr_post_set_texture), read through env:
+ *   bool   swr_post_has_texture(env, slot)
+ *   float4 swr_post_sample(env, slot, uv)     Texture.Sample exactly as a draw sees it (swr_sample): nearest with wrap -- or the
+ *          build-defined bilinear filter if the texture was switched to it (swr_texture_set_filter) when the present was CALLED, then
+ *          from the block-linear copy where one exists
+ *   float4 swr_post_texel(env, slot, x, y)    the row-major texel, x clamped to [0, w - 1] and y to [0, h - 1], each byte times the
+ *          float 1 / 255 (Texture.cs:57-62): no filter, so a pixel-aligned read does not depend on a uv rounding
+ *   int2   swr_post_texture_size(env, slot)
+ * An unbound slot, and a slot outside 0 .. SWR_POST_TEXTURES - 1, has no texture: it samples and reads (1, 1, 1, 1), as swr_sample
+ * does without a texture, and measures (0, 0).
+ * What the result's x, y, z become (w is ignored, except by swr_texture_update_from_post): */
 enum { SWR_POST_RGB32F = 0,     /* three floats as they are, no clamp: the payload of swr_readback_rgb_resolved */
        SWR_POST_RGB8 = 3,       /* the 8-bit present's quantiser (above), three bytes: the payload of swr_readback_rgb8(.., 3) */
        SWR_POST_RGBX8 = 4 };    /* the same and a fourth byte of 255: the payload of swr_readback_rgb8(.., 4) */
@@ -463,6 +473,15 @@ int  swr_post_destroy(swr_context* ctx, int post_id);
 /* up to 64 floats the program reads as env.constants[i] (the rest read 0).  A present takes a copy when it is CALLED: two
  * presents in flight each keep their own */
 int  swr_post_set_constants(swr_context* ctx, int post_id, const float* values, int n);
+/* Bind a texture of this context to slot 0 .. SWR_POST_TEXTURES - 1 of a program of this context (NULL unbinds).  A present, of any of
+ * the four deliveries, takes a copy of the four slots -- and of each texture's filter -- when it is CALLED, as it takes the constants:
+ * two presents in flight each keep their own.  The texels it reads are what the work enqueued before it leaves: a
+ * swr_texture_update_from_frame / _from_post before the present is seen, one after it is not (textures and presents of a context
+ * share its stream: no host wait).  swr_texture_destroy clears the texture out of every live post program of its context: a later
+ * present reads "no texture" there.  SWR_ERR_INVALID_ARG, the slots staying as they were: an unknown or destroyed id (or another
+ * context's), a slot outside 0 .. SWR_POST_TEXTURES - 1. */
+#define SWR_POST_TEXTURES 4
+int  swr_post_set_texture(swr_context* ctx, int post_id, int slot, const swr_texture* tex /* NULL unbinds */);
 /* compile only, without a context or a device, as swr_program_validate */
 int  swr_post_validate(const char* source, char* log, int log_len);
 /* host only: swr_resolved_size plus out_bytes = out_rows * out_width * (12, 3 or 4 by format) */
@@ -480,6 +499,22 @@ int  swr_readback_post(swr_context* ctx, int post_id, int kx, int ky, int format
 int  swr_present_post_async(swr_context* ctx, int post_id, int kx, int ky, int format, void* out, uint64_t* ticket);
 int  swr_post_device(swr_context* ctx, int post_id, int kx, int ky, int format, void* d_out);
 int  swr_post_device_async(swr_context* ctx, int post_id, int kx, int ky, int format, void* d_out);
+/* A pass's result into a texture: swr_texture_update_from_frame with the program between the resolve and the quantiser.  `post_id` is
+ * a program of `src` (of ctx when src is NULL).  Texel (x, y) of the w x h texture is the program's result for output pixel (x, y) of
+ * src's frame, which measures w * kx by h * ky: R, G, B quantise8 of x, y, z -- the bytes swr_readback_post(.., SWR_POST_RGBX8)
+ * delivers -- and A 255 under SWR_TEXTURE_ALPHA_OPAQUE, quantise8(w) under SWR_TEXTURE_ALPHA_KEEP (the one place where a post result's
+ * w is read).  Everything else is swr_texture_update_from_frame's contract: immediate-mode semantics (draws and presents recorded or
+ * called earlier see the old texels, later ones the new), both contexts' recorded draws are flushed, the kernels go onto ctx's
+ * stream, nothing waits for the GPU in the steady state (src's resolved plane is allocated or grown on first use and after a resize,
+ * behind a wait for src's stream), two contexts are ordered by the same two events -- src's later work, a present of src or an
+ * update of a texture the program samples included, runs behind the kernels -- swr_set_stream and a bound framebuffer are honoured,
+ * the block-linear copy of a bilinear target is fresh, and the note on optimistic flushes applies.  A chain of passes is a sequence of
+ * calls: pass 1 writes texture A, pass 2 samples A.
+ * Refused, with nothing written and both contexts usable: whatever swr_texture_update_from_frame refuses, with its codes; an unknown
+ * or destroyed id, or one of a context other than src (SWR_ERR_INVALID_ARG); and `tex` bound to a slot of the program at the call
+ * (SWR_ERR_INVALID_ARG): a pass may not sample the texture it writes -- ping-pong between two textures is the supported feedback. */
+int  swr_texture_update_from_post(swr_context* ctx, swr_texture* tex, swr_context* src, int post_id,
+                                  int kx, int ky, int alpha_mode);
 
 int  swr_flush(swr_context* ctx);    /* execute recorded draws (asynchronous on the stream) */
 int  swr_sync(swr_context* ctx);     /* flush + wait for the stream */

@@ -25,6 +25,7 @@ SWR_ERR_NO_DEVICE = -4
 SWR_ERR_UNSUPPORTED = -5
 SWR_TEXTURE_ALPHA_OPAQUE, SWR_TEXTURE_ALPHA_KEEP = 0, 1     # swr_texture_update_from_frame
 SWR_POST_RGB32F, SWR_POST_RGB8, SWR_POST_RGBX8 = 0, 3, 4     # swr_readback_post & co: what a post program's result becomes
+SWR_POST_TEXTURES = 4                                        # swr_post_set_texture: slots 0 .. 3
 SWR_STALE = 1          # swr_present_wait: not an error -- the copied frame predates a replayed batch, present again
 
 
@@ -117,6 +118,7 @@ EXPORTS = [
     "swr_texture_create_target", "swr_texture_update_from_frame", "swr_texture_readback",
     "swr_post_create", "swr_post_destroy", "swr_post_set_constants", "swr_post_validate", "swr_post_size",
     "swr_readback_post", "swr_present_post_async", "swr_post_device", "swr_post_device_async",
+    "swr_post_set_texture", "swr_texture_update_from_post",
 ]
 
 _libs = {}
@@ -228,6 +230,8 @@ def load(name: str = None) -> C.CDLL:
         "swr_present_post_async": (I, [P, I, I, I, I, P, C.POINTER(C.c_uint64)]),
         "swr_post_device": (I, [P, I, I, I, I, P]),
         "swr_post_device_async": (I, [P, I, I, I, I, P]),
+        "swr_post_set_texture": (I, [P, I, I, P]),
+        "swr_texture_update_from_post": (I, [P, P, P, I, I, I, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

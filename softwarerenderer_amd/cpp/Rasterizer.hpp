@@ -79,6 +79,7 @@ struct Shaders {
 static_assert(sizeof(Shaders::VertexInput) == 48, "VertexInput must match Shaders.cs:10-24");
 
 class MainWindow;
+class PostProgram;
 class Texture {                               // Texture.cs:31-68
 public:
     Texture(const Device& dev, const uint8_t* rgba8, int width, int height) : dev_(dev), Width(width), Height(height) {
@@ -90,6 +91,9 @@ public:
     // the texels become the window's frame of Width * kx by Height * ky pixels, box-filtered and quantised as the 8-bit present; the
     // window may belong to another Device on the same GPU.  Immediate-mode semantics, no wait for the GPU
     inline void UpdateFrom(const MainWindow& window, int kx = 1, int ky = 1, bool keepAlpha = false);
+    // ... with `post`, a program of the window's Device, between the resolve and the quantiser (swr_texture_update_from_post): alpha
+    // 255, or the quantised w of the program's result.  The texture may not be bound to a slot of `post`
+    inline void UpdateFromPost(const MainWindow& window, const PostProgram& post, int kx = 1, int ky = 1, bool keepAlpha = false);
     std::vector<uint8_t> Read() const {       // RGBA8 row-major; waits for the GPU
         std::vector<uint8_t> out((size_t)Width * (size_t)Height * 4);
         dev_.check(swr_texture_readback(dev_.ctx(), h_, out.data()));
@@ -154,6 +158,11 @@ public:
     void SetConstants(const std::vector<float>& values) const {               // captured by each present when it is called
         dev_.check(swr_post_set_constants(dev_.ctx(), id_, values.empty() ? nullptr : values.data(), (int)values.size()));
     }
+    // a texture of `dev` in slot 0 .. SWR_POST_TEXTURES - 1 (null unbinds), read with swr_post_sample / swr_post_texel; captured,
+    // with the texture's filter, by each present when it is called
+    void SetTexture(int slot, const Texture* texture) const {
+        dev_.check(swr_post_set_texture(dev_.ctx(), id_, slot, texture ? texture->handle() : nullptr));
+    }
     int id() const { return id_; }
 private:
     const Device& dev_;
@@ -204,6 +213,10 @@ private:
 inline void Texture::UpdateFrom(const MainWindow& window, int kx, int ky, bool keepAlpha) {
     swr_context* src = window.device().ctx() == dev_.ctx() ? nullptr : window.device().ctx();
     dev_.check(swr_texture_update_from_frame(dev_.ctx(), h_, src, kx, ky, keepAlpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
+}
+inline void Texture::UpdateFromPost(const MainWindow& window, const PostProgram& post, int kx, int ky, bool keepAlpha) {
+    swr_context* src = window.device().ctx() == dev_.ctx() ? nullptr : window.device().ctx();
+    dev_.check(swr_texture_update_from_post(dev_.ctx(), h_, src, post.id(), kx, ky, keepAlpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
 }
 
 class Rasterizer {                            // public static class Rasterizer, Rasterizer.cs:12

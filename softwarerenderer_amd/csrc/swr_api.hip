@@ -142,32 +142,47 @@ ResolveRgbaKernel resolve_rgba_kernel(int kx, int ky) {
     return with_factor<K>(kx, [&](auto x) -> K { return with_factor<K>(ky, [](auto y) -> K { return k_resolve_rgba<decltype(x)::value, decltype(y)::value>; }); });
 }
 
-// a post program's payload: the frame resolved into the context's RGBA plane (under (1, 1) the frame is that plane), then the
-// program's k_post over it, with the constants as they are now
-int launch_post(swr_context* c, const Payload& p, void* d_out) {
-    const uint32_t ow = (uint32_t)payload_width(c, p), orows = (uint32_t)payload_rows(c, p);    // a frame is at most 65535 x 65535
+// a program's texture slots as they are NOW, in the encoding a draw records (swr_flush.h: h < 0 the bilinear filter, w < 0 as well
+// the block-linear copy)
+void capture_post_textures(const PostProg* post, PostConstants& k) {
+    for (int i = 0; i < SWR_POST_TEXTURES; ++i) {
+        const swr_texture* t = post->tex[i];
+        PostTexture& o = k.tex[i];
+        o = PostTexture{ t ? t->d_rgba : nullptr, t ? t->w : 0, t ? (t->bilinear ? -t->h : t->h) : 0 };
+        if (t && t->bilinear && t->d_blocked) { o.texels = t->d_blocked; o.w = -t->w; }
+    }
+}
+
+// A post program over s's whole frame, on c's stream (s == c for a present): the frame resolved into s's RGBA plane (under (1, 1) the
+// frame is that plane), then k_post `fn` of the program over it, with the constants and the texture slots as they are now.
+// d_blocked: the texel formats' second destination, or null.
+int launch_post_over(swr_context* c, swr_context* s, const PostProg* post, int fn, int kx, int ky, void* d_out, uint32_t* d_blocked) {
+    const uint32_t ow = (uint32_t)(std::max(0, s->W) / kx), orows = (uint32_t)(band_rows(s) / ky);    // a frame is at most 65535 x 65535
     const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
     const dim3 grid((ow + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
-    const float4* plane = c->color;
-    if (p.kx != 1 || p.ky != 1) {
+    const float4* plane = s->color;
+    if (kx != 1 || ky != 1) {
         const size_t bytes = (size_t)ow * orows * sizeof(float4);
-        if (c->post_plane.cap < bytes) {
-            // growing frees the old block: an earlier present's k_post may still read it (first use / after a resize only)
-            SWR_HIP(c, hipStreamSynchronize(c->stream));
-            int rc = ensure(c, c->post_plane, bytes); if (rc) return rc;
+        if (s->post_plane.cap < bytes) {
+            // growing frees the old block: an earlier k_post may still read it (first use / after a resize only).  s's stream is behind
+            // every such reader: its own presents, and another context's swr_texture_update_from_post through rtt_done_ev
+            SWR_HIP(c, hipStreamSynchronize(s->stream));
+            int rc = ensure(c, s->post_plane, bytes); if (rc) return rc;
         }
-        hipLaunchKernelGGL(resolve_rgba_kernel(p.kx, p.ky), grid, block, 0, c->stream, (const float4*)c->color, c->post_plane.as<float4>(), ow, orows);
+        hipLaunchKernelGGL(resolve_rgba_kernel(kx, ky), grid, block, 0, c->stream, (const float4*)s->color, s->post_plane.as<float4>(), ow, orows);
         SWR_HIP(c, hipGetLastError());
-        plane = c->post_plane.as<float4>();
+        plane = s->post_plane.as<float4>();
     }
-    const float* depth = c->depth;
-    int kx = p.kx, ky = p.ky;
+    const float* depth = s->depth;
     uint32_t w = ow, rows = orows;
-    PostConstants constants = p.post->constants;
+    PostConstants constants = post->constants;
+    capture_post_textures(post, constants);
+    constants.blocked = d_blocked;
     void* args[] = { &plane, &depth, &d_out, &w, &rows, &kx, &ky, &constants };
-    SWR_HIP(c, hipModuleLaunchKernel(p.post->fn[p.format], grid.x, grid.y, 1, block.x, block.y, 1, 0, c->stream, args, nullptr));
+    SWR_HIP(c, hipModuleLaunchKernel(post->fn[fn], grid.x, grid.y, 1, block.x, block.y, 1, 0, c->stream, args, nullptr));
     return SWR_OK;
 }
+int launch_post(swr_context* c, const Payload& p, void* d_out) { return launch_post_over(c, c, p.post, p.format, p.kx, p.ky, d_out, nullptr); }
 
 // the payload of the band's colour plane in device memory (4-byte aligned), on the context's stream (checked, and not empty)
 int launch_payload(swr_context* c, const Payload& p, void* d_out) {
@@ -304,8 +319,9 @@ int texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_textu
     return SWR_OK;
 }
 
-// Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream.
-int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
+// Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream (but a first use or growth of src's resolved
+// plane, launch_post_over).  posted: swr_texture_update_from_post -- program post_id of src runs between the resolve and the quantiser.
+int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode, bool posted = false, int post_id = 0) {
     if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
     if (alpha_mode != SWR_TEXTURE_ALPHA_OPAQUE && alpha_mode != SWR_TEXTURE_ALPHA_KEEP)
         return fail(c, SWR_ERR_INVALID_ARG, "alpha_mode must be SWR_TEXTURE_ALPHA_OPAQUE (0) or SWR_TEXTURE_ALPHA_KEEP (1)");
@@ -315,6 +331,14 @@ int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, 
         return fail(c, SWR_ERR_UNSUPPORTED, "the source context holds only a band of its frame (swr_set_band*)");
     if ((long long)t->w * kx != (long long)src->W || (long long)t->h * ky != (long long)src->H)
         return fail(c, SWR_ERR_INVALID_ARG, "the source frame must measure texture width * kx by texture height * ky");
+    const PostProg* post = nullptr;
+    if (posted) {
+        const auto it = src->posts.find(post_id);
+        if (it == src->posts.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
+        post = it->second.get();
+        for (const swr_texture* bound : post->tex)
+            if (bound == t) return fail(c, SWR_ERR_INVALID_ARG, "the texture is bound to a slot of the program: a pass may not sample the texture it writes");
+    }
     int rc;
     // the frame is complete behind this point of src's stream, and c's recorded draws are in front of the kernel on c's stream: they
     // sample the old texels (raster kernels and k_texture_sample, the only readers of a texture, run on `stream`, never on the front stream)
@@ -328,9 +352,15 @@ int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, 
     const bool blocked = t->d_blocked != nullptr;         // (made by swr_texture_set_filter: both sides are multiples of 4)
     const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
     const dim3 grid(((uint32_t)t->w + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, ((uint32_t)t->h + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
-    hipLaunchKernelGGL(rtt_kernel(kx, ky, alpha_mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
-                       (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
-    SWR_HIP(c, hipGetLastError());
+    if (post) {
+        // (the resolve writes src's plane and the program may sample src's textures: both behind rtt_frame_ev, and src's later work --
+        // a present, an update of such a texture -- behind rtt_done_ev)
+        if ((rc = launch_post_over(c, src, post, alpha_mode == SWR_TEXTURE_ALPHA_KEEP ? 4 : 3, kx, ky, t->d_rgba, (uint32_t*)t->d_blocked))) return rc;
+    } else {
+        hipLaunchKernelGGL(rtt_kernel(kx, ky, alpha_mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
+                           (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
+        SWR_HIP(c, hipGetLastError());
+    }
     if (src != c && src->stream != c->stream) {
         // src's next raster, clear or upload may not overwrite the frame under the kernel
         if (!c->rtt_done_ev) SWR_HIP(c, hipEventCreateWithFlags(&c->rtt_done_ev, hipEventDisableTiming));
@@ -695,17 +725,27 @@ int swr_texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_t
 }
 int swr_texture_create_target(swr_context* c, int w, int h, swr_texture** out) { SWR_ENTER(c); return texture_create(c, nullptr, w, h, out, "texture allocation failed: "); }
 
-int swr_texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
+namespace {
+// swr_texture_update_from_frame / _from_post under the mutexes of both contexts
+int texture_update_locked(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode, bool posted, int post_id) {
     if (!c) return SWR_ERR_INVALID_ARG;
     if (!src || src == c) {
         std::lock_guard<std::mutex> lock_(c->mu);
         (void)hipSetDevice(c->device);
-        return texture_update_from_frame(c, t, c, kx, ky, alpha_mode);
+        return texture_update_from_frame(c, t, c, kx, ky, alpha_mode, posted, post_id);
     }
     std::lock(c->mu, src->mu);                            // (both, in an order that cannot deadlock against the opposite call)
     std::lock_guard<std::mutex> lock_c(c->mu, std::adopt_lock), lock_s(src->mu, std::adopt_lock);
     (void)hipSetDevice(c->device);
-    return texture_update_from_frame(c, t, src, kx, ky, alpha_mode);
+    return texture_update_from_frame(c, t, src, kx, ky, alpha_mode, posted, post_id);
+}
+}  // namespace
+
+int swr_texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
+    return texture_update_locked(c, t, src, kx, ky, alpha_mode, false, 0);
+}
+int swr_texture_update_from_post(swr_context* c, swr_texture* t, swr_context* src, int post_id, int kx, int ky, int alpha_mode) {
+    return texture_update_locked(c, t, src, kx, ky, alpha_mode, true, post_id);
 }
 
 int swr_texture_readback(swr_context* c, const swr_texture* t, uint8_t* rgba8) {
@@ -734,6 +774,8 @@ int swr_texture_destroy(swr_context* c, swr_texture* t) {
     SWR_ENTER(c);
     if (!t) return SWR_OK;
     int rc = flush_and_sync_locked(c); if (rc) return rc;
+    for (auto& p : c->posts)                              // a later present reads "no texture" there
+        for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
     if (t->d_rgba) (void)hipFree(t->d_rgba);
     if (t->d_blocked) (void)hipFree(t->d_blocked);
     delete t;
@@ -908,7 +950,7 @@ int swr_post_create(swr_context* c, const char* src, int* post_id) {
     if (rc) { c->err = log; return rc; }
     auto p = std::make_shared<PostProg>();
     SWR_HIP(c, hipModuleLoadData(&p->mod, code->code.data()));
-    for (int k = 0; k < 3; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
+    for (int k = 0; k < 5; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
     static std::atomic<int> next_post{1};                   // one sequence for the process: another context's id is unknown here
     const int id = next_post++;
     c->posts[id] = std::move(p);
@@ -932,6 +974,15 @@ int swr_post_set_constants(swr_context* c, int post_id, const float* values, int
     if (n < 0 || n > SWR_POST_CONSTANTS || (n > 0 && !values)) return fail(c, SWR_ERR_INVALID_ARG, "between 0 and 64 constants");
     float* k = it->second->constants.v;
     for (int i = 0; i < SWR_POST_CONSTANTS; ++i) k[i] = i < n ? values[i] : 0.0f;
+    return SWR_OK;
+}
+
+int swr_post_set_texture(swr_context* c, int post_id, int slot, const swr_texture* tex) {
+    SWR_ENTER(c);
+    auto it = c->posts.find(post_id);
+    if (it == c->posts.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
+    if (slot < 0 || slot >= SWR_POST_TEXTURES) return fail(c, SWR_ERR_INVALID_ARG, "a post program has texture slots 0 to 3");
+    it->second->tex[slot] = tex;          // read, with the texture's filter, when a present is called
     return SWR_OK;
 }
 

@@ -76,13 +76,14 @@ struct UserProg {
     ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
 };
 
-// A post-process program loaded on the context's device (swr_post_create): k_post<SWR_POST_RGB32F / _RGB8 / _RGBX8> of its run-time
-// compiled code object (swr_post.hip.h).  A destroyed program is parked (post_garbage) until the streams are idle: a present enqueued
+// A post-process program loaded on the context's device (swr_post_create): k_post<SWR_POST_RGB32F / _RGB8 / _RGBX8> and the two texel
+// formats of swr_texture_update_from_post, of its run-time compiled code object (swr_post.hip.h).  A destroyed program is parked (post_garbage) until the streams are idle: a present enqueued
 // with it may still be running.
 struct PostProg {
     hipModule_t mod = nullptr;
-    hipFunction_t fn[3] = { nullptr, nullptr, nullptr };   // by PayloadFormat: RGB32F, RGB8, RGBX8
+    hipFunction_t fn[5] = {};                               // by PayloadFormat: RGB32F, RGB8, RGBX8; then the texel formats, OPAQUE and KEEP
     PostConstants constants = {};                           // swr_post_set_constants: passed by value to each launch
+    const swr_texture* tex[SWR_POST_TEXTURES] = {};         // swr_post_set_texture: read (with each texture's filter) at each launch
     ~PostProg() { if (mod) (void)hipModuleUnload(mod); }
 };
 

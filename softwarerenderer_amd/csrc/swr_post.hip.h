@@ -15,30 +15,47 @@
 //   swr_post_depth(env, x, y)   the depth word of sample (x kx, y ky), the top-left sample of the pixel's block, clamped the same way;
 //                               not averaged; float.MinValue where the depth plane was cleared
 //   swr_lerp, swr_max, swr_clamp   swr_user_math.hip.h: the definitions fragment programs call
-// A post program has no textures.  What the result becomes:
+//   swr_post_has_texture / _sample / _texel / _texture_size (env, slot, ..)   the program's SWR_POST_TEXTURES texture slots as they were
+//                               when the present call was made (tests/post_texture_cases.py restates them)
+// What the result becomes:
 //   SWR_POST_RGB32F   x, y, z stored as they are (no clamp)
 //   SWR_POST_RGB8     quantise8 of x, y, z (swr_present8.hip.h), three bytes
 //   SWR_POST_RGBX8    the same and a fourth byte of 255, one dword
-//   w is ignored.
+//   w is ignored -- except by swr_texture_update_from_post (SWR_POST_TEXELS_KEEP below), where quantise8(w) is the texel's alpha.
 //
 //   k_resolve_rgba<KX, KY>  (product library) one thread per OUTPUT pixel on k_resolve_rgb's plain 2-D grid (64 x 4 threads per block, no
 //                           stride loop): resolve_rows4 times 1 / (KX KY) into a window-sized float4 plane of the context.  Not launched
 //                           under (1, 1), where the frame is that plane already.  The plane is deliberate: a program that fetches
 //                           neighbours would otherwise redo a tree of up to 64 samples per tap.
-//   k_post<FORMAT>          (run-time compiled with the user's text, SWR_RTC_POST; three instantiations per program) the same grid: the
+//   k_post<FORMAT>          (run-time compiled with the user's text, SWR_RTC_POST; five instantiations per program) the same grid: the
 //                           thread loads its pixel of the plane, calls the inlined swr_post and stores as k_resolve_rgb / k_present8 store.
-//                           The constants are a by-value kernel argument: no device buffer outlives the call.
+//                           The constants and the texture slots are a by-value kernel argument: no device buffer outlives the call.
+//                           SWR_POST_TEXELS_OPAQUE / _KEEP (swr_texture_update_from_post; not present formats): the dword RGBX8 stores,
+//                           row-major into `out`, its alpha 255 or quantise8(w) -- and, where the argument carries a block-linear
+//                           copy, the same dword at bilinear_texel_offset<true> as k_frame_to_texture stores it (swr_rtt.hip.h).
 // No LDS, no scratch, no inline assembly.  A frame is at most 65535 x 65535 (swr_resize), so pixel indices fit 32 bits; offsets are size_t.
 #pragma once
 #include "swr_user_math.hip.h"
 #include "swr_rtt.hip.h"
 
 #define SWR_POST_CONSTANTS 64
+// k_post's internal formats behind swr_texture_update_from_post: RGBA8 texels, alpha 255 or the result's w
+#define SWR_POST_TEXELS_OPAQUE 16
+#define SWR_POST_TEXELS_KEEP 17
 
 namespace swr {
 
-// k_post's last argument, by value: the program's constants as they were when the present call was made
-struct PostConstants { float v[SWR_POST_CONSTANTS]; };
+// one texture slot as a present captured it: what a draw's DrawParams hold (swr_flush.h) -- h < 0: the bilinear filter; w < 0 as well:
+// `texels` is the block-linear copy; texels null: nothing bound
+struct PostTexture { const uint8_t* texels; int w, h; };
+
+// k_post's last argument, by value: the program's constants and texture slots as they were when the present call was made, and for
+// the texel formats the target's block-linear copy (null: it has none)
+struct PostConstants {
+    float v[SWR_POST_CONSTANTS];
+    PostTexture tex[SWR_POST_TEXTURES];
+    uint32_t* blocked;
+};
 
 // color: the frame, out_w * KX pixels wide and out_rows * KY rows high; plane: out_rows x out_w float4
 template <int KX, int KY>
@@ -69,6 +86,7 @@ struct swr_post_env {
     // the library's own, behind the helpers below:
     const float4* plane_;        // height x width resolved pixels (the frame itself under (1, 1))
     const float* depth_;         // the frame's depth plane, height * ky rows of width * kx words
+    const swr::PostTexture* textures_;    // the SWR_POST_TEXTURES slots (kernel arguments: constant memory)
 };
 
 __device__ __forceinline__ int swr_post_clamp_index(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
@@ -81,27 +99,61 @@ __device__ __forceinline__ float swr_post_depth(const swr_post_env& env, int x, 
     return env.depth_[(size_t)y * (size_t)env.ky * ((size_t)env.width * (size_t)env.kx) + (size_t)x * (size_t)env.kx];
 }
 
+// The texture slots.  A slot outside 0 .. SWR_POST_TEXTURES - 1 is an unbound one.
+__device__ __forceinline__ bool swr_post_has_texture(const swr_post_env& env, int slot) {
+    return (unsigned)slot < (unsigned)SWR_POST_TEXTURES && env.textures_[slot].texels != nullptr;
+}
+// Texture.Sample as a draw sees it (swr_sample): nearest with wrap, or the build-defined bilinear filter if the texture was switched to
+// it when the present call was made; (1, 1, 1, 1) from an unbound slot
+__device__ __forceinline__ float4 swr_post_sample(const swr_post_env& env, int slot, float2 uv) {
+    if (!swr_post_has_texture(env, slot)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const swr::PostTexture t = env.textures_[slot];
+    return swr::texture_fetch(t.texels, t.w, t.h, uv.x, uv.y);
+}
+__device__ __forceinline__ int2 swr_post_texture_size(const swr_post_env& env, int slot) {
+    if (!swr_post_has_texture(env, slot)) return make_int2(0, 0);
+    const swr::PostTexture t = env.textures_[slot];
+    return make_int2(t.w < 0 ? -t.w : t.w, t.h < 0 ? -t.h : t.h);
+}
+// texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1], each byte times the float 1 / 255 (Texture.cs:57-62): no filter, no uv
+__device__ __forceinline__ float4 swr_post_texel(const swr_post_env& env, int slot, int x, int y) {
+    if (!swr_post_has_texture(env, slot)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const swr::PostTexture t = env.textures_[slot];
+    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
+    x = swr_post_clamp_index(x, w); y = swr_post_clamp_index(y, h);
+    const uint32_t* __restrict__ t32 = reinterpret_cast<const uint32_t*>(t.texels);
+    return swr::texture_unpack(t32[t.w < 0 ? swr::bilinear_texel_offset<true>(w, x, y) : swr::bilinear_texel_offset<false>(w, x, y)]);
+}
+
 // the user's program (always inlined into k_post)
 __device__ __attribute__((always_inline)) float4 swr_post(const swr_post_in& in, const swr_post_env& env);
 
 namespace swr {
 
 // plane: out_rows x out_w resolved pixels; depth: the frame's depth plane; out: out_rows * out_w pixels of 12 (RGB32F), 3 or 4 bytes
+// (the texel formats: 4, a texture's d_rgba)
 template <int FORMAT>
 __global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
 void k_post(const float4* __restrict__ plane, const float* __restrict__ depth, void* __restrict__ out, uint32_t out_w, uint32_t out_rows,
             int kx, int ky, const PostConstants constants) {
-    static_assert(FORMAT == SWR_POST_RGB32F || FORMAT == SWR_POST_RGB8 || FORMAT == SWR_POST_RGBX8, "a present format");
+    static_assert(FORMAT == SWR_POST_RGB32F || FORMAT == SWR_POST_RGB8 || FORMAT == SWR_POST_RGBX8 || FORMAT == SWR_POST_TEXELS_OPAQUE ||
+                  FORMAT == SWR_POST_TEXELS_KEEP, "a present format or a texel format");
     const uint32_t ox = blockIdx.x * SWR_RESOLVE_BLOCK_X + threadIdx.x;
     const uint32_t oy = blockIdx.y * SWR_RESOLVE_BLOCK_Y + threadIdx.y;
     if (ox >= out_w || oy >= out_rows) return;
-    const swr_post_env env = { (int)out_w, (int)out_rows, kx, ky, constants.v, plane, depth };
+    const swr_post_env env = { (int)out_w, (int)out_rows, kx, ky, constants.v, plane, depth, constants.tex };
     const size_t pixel = (size_t)oy * out_w + ox;
     const swr_post_in in = { (int)ox, (int)oy, plane[pixel] };
     const float4 c = swr_post(in, env);
     if constexpr (FORMAT == SWR_POST_RGB32F) {
         float* o = static_cast<float*>(out) + pixel * 3;
         o[0] = c.x; o[1] = c.y; o[2] = c.z;
+    } else if constexpr (FORMAT == SWR_POST_TEXELS_OPAQUE || FORMAT == SWR_POST_TEXELS_KEEP) {
+        // (a texture has fewer than 2^30 texels: 32-bit texel indices, as in k_frame_to_texture)
+        const uint32_t a = FORMAT == SWR_POST_TEXELS_KEEP ? quantise8(c.w) << 24 : 0xff000000u;
+        const uint32_t px = quantise8(c.x) | quantise8(c.y) << 8 | quantise8(c.z) << 16 | a;
+        static_cast<uint32_t*>(out)[oy * out_w + ox] = px;
+        if (constants.blocked) constants.blocked[bilinear_texel_offset<true>((int)out_w, (int)ox, (int)oy)] = px;
     } else {
         const uint32_t px = quantise8(c.x) | quantise8(c.y) << 8 | quantise8(c.z) << 16 | 0xff000000u;
         uint8_t* o = static_cast<uint8_t*>(out) + pixel * FORMAT;

@@ -259,6 +259,11 @@ class PostProgram:
         a = _f32(values if values is not None else [], None)
         self._dev._ck(self._dev._lib.swr_post_set_constants(self._dev._ctx, self._id, _fptr(a) if a.size else None, int(a.size)))
 
+    def SetTexture(self, slot: int, texture: Optional["Texture"]):
+        """Bind a Texture of this Device to slot 0 .. 3 (None unbinds): the program reads it with swr_post_sample / swr_post_texel.
+        Each present captures the four slots, and each texture's filter, when it is called."""
+        self._dev._ck(self._dev._lib.swr_post_set_texture(self._dev._ctx, self._id, int(slot), texture._h if texture is not None else None))
+
     def close(self):
         """swr_post_destroy: a present already enqueued with the program still completes."""
         if self._id is not None and self._dev._ctx:
@@ -299,6 +304,15 @@ class Texture:
         src = window._dev._ctx if window._dev is not self._dev else None
         self._dev._ck(self._dev._lib.swr_texture_update_from_frame(
             self._dev._ctx, self._h, src, int(kx), int(ky), N.SWR_TEXTURE_ALPHA_KEEP if keep_alpha else N.SWR_TEXTURE_ALPHA_OPAQUE))
+
+    def UpdateFromPost(self, window: "MainWindow", post: PostProgram, kx: int = 1, ky: int = 1, keep_alpha: bool = False):
+        """A pass's result into the texture (swr_texture_update_from_post): UpdateFrom with `post`, a program of the window's Device,
+        between the resolve and the quantiser; alpha 255, or the quantised w of the program's result with keep_alpha.  The texture
+        may not be bound to a slot of `post`.  A chain of passes is a sequence of calls: pass 1 writes A, pass 2 samples A."""
+        window._activate()
+        src = window._dev._ctx if window._dev is not self._dev else None
+        self._dev._ck(self._dev._lib.swr_texture_update_from_post(
+            self._dev._ctx, self._h, src, post._id, int(kx), int(ky), N.SWR_TEXTURE_ALPHA_KEEP if keep_alpha else N.SWR_TEXTURE_ALPHA_OPAQUE))
 
     def Read(self) -> np.ndarray:
         """The texels as (Height, Width, 4) uint8 (swr_texture_readback); waits for the GPU."""
