@@ -245,6 +245,7 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_program_create(IntPtr ctx, byte* fragmentSource, out int programId);
         [DllImport(Lib)] public static extern int swr_program_destroy(IntPtr ctx, int programId);
         [DllImport(Lib)] public static extern int swr_program_set_constants(IntPtr ctx, int programId, float* values, int n);
+        [DllImport(Lib)] public static extern int swr_program_set_texture(IntPtr ctx, int programId, int slot, IntPtr texture);
         [DllImport(Lib)] public static extern int swr_program_validate(byte* fragmentSource, byte* log, int logLen);
         [DllImport(Lib)] public static extern int swr_program_create_vf(IntPtr ctx, byte* vertexSource, byte* fragmentSource, out int programId);
         [DllImport(Lib)] public static extern int swr_program_validate_vf(byte* vertexSource, byte* fragmentSource, byte* log, int logLen);
@@ -709,6 +710,21 @@ namespace SoftwareRenderer
                 programs[m] = id;
                 return true;
             }
+        }
+
+        // The closure's FURTHER Texture fields (a lightmap, a normal map, a mask): slot 1 .. 3 of the registered method's program, read
+        // in its restatement as swr_sample(env, slot, uv) (swr_program_set_texture; null unbinds).  Slot 0 stays the Texture the closure
+        // passes as the draw's.  Each draw captures the slots, and each texture's filter, when it is recorded.  The program is compiled
+        // here if it has not been used yet.
+        public static void SetTexture(Shaders.FragmentShader method, int slot, TextureNative? texture)
+        {
+            if (!TryUserProgram(method, out int id)) throw new ArgumentException("the fragment method is not registered");
+            SwrContext.Check(Native.swr_program_set_texture(SwrContext.Handle, id, slot, texture?.Handle ?? IntPtr.Zero));
+        }
+        public static void SetTexture(Shaders.VertexShader vertexMethod, Shaders.FragmentShader fragmentMethod, int slot, TextureNative? texture)
+        {
+            if (!TryUserPair(vertexMethod, fragmentMethod, out int id)) throw new ArgumentException("the (vertex, fragment) pair is not registered");
+            SwrContext.Check(Native.swr_program_set_texture(SwrContext.Handle, id, slot, texture?.Handle ?? IntPtr.Zero));
         }
 
         public static bool TryResolve(Shaders.VertexShader vs, Shaders.FragmentShader fs, out SwrProgram program, out SwrUniforms uniforms, out IntPtr texture)

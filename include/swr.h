@@ -412,6 +412,24 @@ int  swr_program_destroy(swr_context* ctx, int program_id);
 /* up to 64 floats the program reads as env.constants[i] (the rest read 0).  A draw takes a copy when it is RECORDED, as a C# closure
  * captures its fields: later calls do not change recorded draws */
 int  swr_program_set_constants(swr_context* ctx, int program_id, const float* values, int n);
+/* TEXTURE SLOTS: a user program reads SWR_PROGRAM_TEXTURES textures per draw, in both halves, through env:
+ *     bool   swr_has_texture(env, slot)
+ *     float4 swr_sample(env, slot, uv)        Texture.Sample exactly as swr_sample(env, uv) computes it: nearest with wrap, or the
+ *                                             bilinear extension if the texture was switched to it when the draw was recorded
+ *     float4 swr_texel(env, slot, x, y)       texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1], each byte times the float 1 / 255
+ *     int2   swr_texture_size(env, slot)      (w, h), positive whatever the filter
+ * Slot 0 is and stays the `texture` argument of the render call.  Slots 1 .. SWR_PROGRAM_TEXTURES - 1 belong to the program, as its
+ * constants do: a draw copies each slot's pointer, size and filter (the block-linear copy where the texture has one) when it is
+ * RECORDED; later swr_program_set_texture and swr_texture_set_filter calls do not change recorded draws.  An unbound slot, and a slot
+ * outside 0 .. SWR_PROGRAM_TEXTURES - 1, has no texture: it samples and reads (1, 1, 1, 1) and measures (0, 0).  The slot may be
+ * computed per fragment.  Two draws share fragment-stage state only if their captured constants and slots are bitwise equal.
+ * ORDER against texture updates: swr_texture_update_from_frame / _from_post flush the recorded draws first, so draws recorded before
+ * an update of a texture bound to slot 1 .. 3 sample the old texels, and later draws sample the new ones.
+ * swr_texture_destroy clears the texture out of every live user program of its context: a later draw reads "no texture" there.
+ * Bind a texture of this context to slot 1 .. SWR_PROGRAM_TEXTURES - 1 of a user program (NULL unbinds).  SWR_ERR_INVALID_ARG, with
+ * the slots left as they were: an unknown or destroyed id, an id below SWR_PROG_USER_BASE, a slot outside 1 .. 3. */
+#define SWR_PROGRAM_TEXTURES 4
+int  swr_program_set_texture(swr_context* ctx, int program_id, int slot, const swr_texture* tex /* NULL unbinds */);
 /* compile only, without a context or a device: SWR_OK, SWR_ERR_INVALID_ARG (log = compiler messages, NUL-terminated, truncated to
  * log_len) or SWR_ERR_UNSUPPORTED */
 int  swr_program_validate(const char* fragment_source, char* log, int log_len);

@@ -26,6 +26,7 @@ SWR_ERR_UNSUPPORTED = -5
 SWR_TEXTURE_ALPHA_OPAQUE, SWR_TEXTURE_ALPHA_KEEP = 0, 1     # swr_texture_update_from_frame
 SWR_POST_RGB32F, SWR_POST_RGB8, SWR_POST_RGBX8 = 0, 3, 4     # swr_readback_post & co: what a post program's result becomes
 SWR_POST_TEXTURES = 4                                        # swr_post_set_texture: slots 0 .. 3
+SWR_PROGRAM_TEXTURES = 4                                     # user programs: slot 0 the draw's texture, swr_program_set_texture: slots 1 .. 3
 SWR_STALE = 1          # swr_present_wait: not an error -- the copied frame predates a replayed batch, present again
 
 
@@ -111,6 +112,7 @@ EXPORTS = [
     "swr_render_mesh_arrays", "swr_mesh_bounds", "swr_is_sphere_in_frustum", "swr_render_mesh_culled", "swr_flush", "swr_sync", "swr_interpolate", "swr_get_stats", "swr_reset_stats",
     "swr_profile_enable", "swr_profile_get", "swr_profile_reset", "swr_profile_raster_samples", "swr_device_name", "swr_debug_counters", "swr_selftest_division",
     "swr_program_create", "swr_program_destroy", "swr_program_set_constants", "swr_program_validate",
+    "swr_program_set_texture",
     "swr_program_create_vf", "swr_program_validate_vf",
     "swr_raycast", "swr_raycast_nearest", "swr_character_ray_counts", "swr_character_update",
     "swr_resolved_size", "swr_readback_rgb_resolved", "swr_present_rgb_resolved_async", "swr_resolve_rgb_device", "swr_resolve_rgb_device_async",
@@ -201,6 +203,7 @@ def load(name: str = None) -> C.CDLL:
         "swr_program_create": (I, [P, C.c_char_p, C.POINTER(I)]),
         "swr_program_destroy": (I, [P, I]),
         "swr_program_set_constants": (I, [P, I, fp, I]),
+        "swr_program_set_texture": (I, [P, I, I, P]),
         "swr_program_validate": (I, [C.c_char_p, C.c_char_p, I]),
         "swr_program_create_vf": (I, [P, C.c_char_p, C.c_char_p, C.POINTER(I)]),
         "swr_program_validate_vf": (I, [C.c_char_p, C.c_char_p, C.c_char_p, I]),

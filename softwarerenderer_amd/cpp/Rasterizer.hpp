@@ -28,6 +28,7 @@ struct SwrError : std::runtime_error {
 using Matrix4x4 = std::array<float, 16>;     // M11..M44 row-major, row-vector convention (System.Numerics layout)
 using Vector4 = std::array<float, 4>;
 
+class Texture;
 class Device {                                // one swr_context = one GPU
 public:
     explicit Device(int device_id = 0) {
@@ -58,11 +59,13 @@ public:
     void SetProgramConstants(int id, const std::vector<float>& values) const {
         check(swr_program_set_constants(ctx_, id, values.empty() ? nullptr : values.data(), (int)values.size()));
     }
+    // a texture of this device in slot 1 .. SWR_PROGRAM_TEXTURES - 1 of a user program (null unbinds; slot 0 is the draw's texture),
+    // read in both halves with swr_sample / swr_texel(env, slot, ..); captured, with the texture's filter, by each draw when recorded
+    inline void SetProgramTexture(int id, int slot, const Texture* texture) const;
 private:
     swr_context* ctx_ = nullptr;
 };
 
-class Texture;
 struct ShaderProgram;
 struct Shaders {
     using VertexInput = swr_vertex;           // Shaders.cs:10-24, 48 bytes
@@ -120,7 +123,12 @@ struct ShaderProgram {                        // stands in for (VertexShader, Fr
     swr_uniforms uniforms{};
     const Texture* texture = nullptr;
     std::vector<float> constants;             // user programs: set before each draw (each draw captures them when recorded)
+    const Texture* textures[SWR_PROGRAM_TEXTURES - 1] = {};   // ... and slots 1 .. 3, likewise (`texture` is slot 0)
 };
+
+inline void Device::SetProgramTexture(int id, int slot, const Texture* texture) const {
+    check(swr_program_set_texture(ctx_, id, slot, texture ? texture->handle() : nullptr));
+}
 
 inline ShaderProgram Shaders::Custom(const Device& dev, const std::string& source, const swr_uniforms& uniforms,
                                      const Texture* texture, std::vector<float> constants) {
@@ -240,7 +248,10 @@ public:
                            BlendMode blendMode = BlendMode::Alpha) {
         const Device& d = window.device();
         d.check(swr_set_state(d.ctx(), NearClip, FarClip, (int)RenderDebugMode));
-        if ((int)shader.program >= SWR_PROG_USER_BASE) d.SetProgramConstants((int)shader.program, shader.constants);
+        if ((int)shader.program >= SWR_PROG_USER_BASE) {
+            d.SetProgramConstants((int)shader.program, shader.constants);
+            for (int k = 1; k < SWR_PROGRAM_TEXTURES; ++k) d.SetProgramTexture((int)shader.program, k, shader.textures[k - 1]);
+        }
         d.check(swr_render_mesh_arrays(d.ctx(), vertices.data(), (int)vertices.size(), indices.data(), (int)indices.size(),
                                        model.data(), view.data(), projection.data(), (int)shader.program, &shader.uniforms,
                                        shader.texture ? shader.texture->handle() : nullptr,

@@ -145,12 +145,7 @@ ResolveRgbaKernel resolve_rgba_kernel(int kx, int ky) {
 // a program's texture slots as they are NOW, in the encoding a draw records (swr_flush.h: h < 0 the bilinear filter, w < 0 as well
 // the block-linear copy)
 void capture_post_textures(const PostProg* post, PostConstants& k) {
-    for (int i = 0; i < SWR_POST_TEXTURES; ++i) {
-        const swr_texture* t = post->tex[i];
-        PostTexture& o = k.tex[i];
-        o = PostTexture{ t ? t->d_rgba : nullptr, t ? t->w : 0, t ? (t->bilinear ? -t->h : t->h) : 0 };
-        if (t && t->bilinear && t->d_blocked) { o.texels = t->d_blocked; o.w = -t->w; }
-    }
+    for (int i = 0; i < SWR_POST_TEXTURES; ++i) k.tex[i] = texture_slot_of(post->tex[i]);
 }
 
 // A post program over s's whole frame, on c's stream (s == c for a present): the frame resolved into s's RGBA plane (under (1, 1) the
@@ -776,6 +771,8 @@ int swr_texture_destroy(swr_context* c, swr_texture* t) {
     int rc = flush_and_sync_locked(c); if (rc) return rc;
     for (auto& p : c->posts)                              // a later present reads "no texture" there
         for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
+    for (auto& p : c->progs)                              // a later draw captures "no texture" there (recorded ones were flushed above)
+        for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
     if (t->d_rgba) (void)hipFree(t->d_rgba);
     if (t->d_blocked) (void)hipFree(t->d_blocked);
     delete t;
@@ -929,6 +926,16 @@ int swr_program_set_constants(swr_context* c, int program_id, const float* value
     if (n < 0 || n > 64 || (n > 0 && !values)) return fail(c, SWR_ERR_INVALID_ARG, "between 0 and 64 constants");
     float* k = it->second->constants;
     for (int i = 0; i < 64; ++i) k[i] = i < n ? values[i] : 0.0f;
+    return SWR_OK;
+}
+
+int swr_program_set_texture(swr_context* c, int program_id, int slot, const swr_texture* tex) {
+    SWR_ENTER(c);
+    auto it = c->progs.find(program_id);         // (user ids only: a built-in id is never in the table)
+    if (it == c->progs.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed user program id");
+    if (slot < 1 || slot >= SWR_PROGRAM_TEXTURES)
+        return fail(c, SWR_ERR_INVALID_ARG, "a user program owns texture slots 1 to 3 (slot 0 is the render call's texture)");
+    it->second->tex[slot - 1] = tex;      // read, with the texture's filter, when a draw is recorded
     return SWR_OK;
 }
 

@@ -587,4 +587,36 @@ __device__ __forceinline__ float4 texture_fetch(const uint8_t* __restrict__ tex,
     return w_signed < 0 ? texture_sample_bilinear<true>(tex, -w_signed, -h_signed, tu, tv) : texture_sample_bilinear<false>(tex, w_signed, -h_signed, tu, tv);
 }
 
+// One texture slot of a run-time compiled program as a draw (user programs, slots 1 .. SWR_PROGRAM_TEXTURES - 1) or a present (post
+// programs) captured it, in texture_fetch's sign convention, which is also DrawParams::tex / tex_w / tex_h's: h < 0: the bilinear
+// filter; w < 0 as well: `texels` is the block-linear copy; texels null: nothing bound.  The host fills it (texture_slot_of, swr_host.h).
+struct TextureSlot { const uint8_t* texels; int w, h; };
+static_assert(sizeof(TextureSlot) == 16 && alignof(TextureSlot) == 8, "three of them follow the 64 constants of a user block");
+__device__ __forceinline__ bool texture_slot_bound(const TextureSlot& t) { return t.texels != nullptr; }
+// Texture.Sample of a slot; (1, 1, 1, 1) from an unbound one, as a draw without a texture samples
+__device__ __forceinline__ float4 texture_slot_sample(const TextureSlot& t, float tu, float tv) {
+    if (!texture_slot_bound(t)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    return texture_fetch(t.texels, t.w, t.h, tu, tv);
+}
+// the size, positive whatever the filter and the layout; (0, 0) of an unbound slot
+__device__ __forceinline__ int2 texture_slot_size(const TextureSlot& t) {
+    if (!texture_slot_bound(t)) return make_int2(0, 0);
+    return make_int2(t.w < 0 ? -t.w : t.w, t.h < 0 ? -t.h : t.h);
+}
+// texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1], each byte times the float 1 / 255 (Texture.cs:57-62): no filter, no uv
+__device__ __forceinline__ float4 texture_slot_texel(const TextureSlot& t, int x, int y) {
+    if (!texture_slot_bound(t)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
+    x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x); y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+    const uint32_t* __restrict__ t32 = reinterpret_cast<const uint32_t*>(t.texels);
+    return texture_unpack(t32[t.w < 0 ? bilinear_texel_offset<true>(w, x, y) : bilinear_texel_offset<false>(w, x, y)]);
+}
+
+// The per-draw block of a user-program batch (RasterArgs::user_consts, k_vertex_user's last argument): the draw's 64 captured constants,
+// then its captured texture slots 1 .. SWR_PROGRAM_TEXTURES - 1 as TextureSlot records (slot 0 is the draw's texture, in DrawParams).
+// Only run-time compiled kernels read it.  76 words, 304 bytes: every block and every record in it is 16-byte aligned.
+#define SWR_USER_CONSTANTS 64
+#define SWR_USER_BLOCK_WORDS (SWR_USER_CONSTANTS + 4 * (SWR_PROGRAM_TEXTURES - 1))
+static_assert(SWR_USER_BLOCK_WORDS == 64 + 3 * 4 && SWR_USER_BLOCK_WORDS % 4 == 0, "64 constants and three 16-byte slots");
+
 }  // namespace swr

@@ -65,8 +65,9 @@ int sync_locked(swr_context* c) {
 
 enum { MODE_SYNC = 0, MODE_ASYNC = 1 };
 // The upload block of a batch (RasterSet::d_upload and its pinned staging copy): draws | vertex block map | triangle block map
-// | bounds pointers | visibility words | captured constants (64 floats per draw), every part on a 256-byte boundary.  The bounds
-// pointers and visibility words are there only when some draw is frustum-culled, the constants only in a user-program batch.
+// | bounds pointers | visibility words | captured user blocks (UserBlock: SWR_USER_BLOCK_WORDS words per draw), every part on a
+// 256-byte boundary.  The bounds pointers and visibility words are there only when some draw is frustum-culled, the user blocks only
+// in a user-program batch.
 struct UploadLayout { size_t off_vb, off_tb, off_bp, off_vis, off_consts, bytes; };
 static UploadLayout upload_layout(size_t nd, size_t v_blocks, size_t t_blocks, bool any_cull, bool user) {
     const auto r256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -77,7 +78,7 @@ static UploadLayout upload_layout(size_t nd, size_t v_blocks, size_t t_blocks, b
     u.off_vis = r256(u.off_bp + (any_cull ? nd * sizeof(void*) : 0));
     const size_t vis_end = u.off_vis + (any_cull ? nd * 4 : 0);
     u.off_consts = r256(vis_end);
-    u.bytes = user ? u.off_consts + nd * 64 * sizeof(float) : vis_end;
+    u.bytes = user ? u.off_consts + nd * sizeof(UserBlock) : vis_end;
     return u;
 }
 template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
@@ -360,13 +361,15 @@ static BatchGeometry batch_geometry(const Batch& b) {
         for (uint32_t f = 0; f < p.n_tris; f += SWR_GEOM_BLOCK) g.tblocks.push_back({ (uint32_t)i, f });
         g.V += p.n_verts; g.T += p.n_tris;
         g.any_cull = g.any_cull || b.draws[i].frustum_cull;
-        // fragment-stage identity: draws that differ only in geometry / matrices / cull mode share one set of fragment constants
+        // fragment-stage identity: draws that differ only in geometry / matrices / cull mode share one set of fragment constants.
+        // A user draw's captured block is compared bit for bit: as float VALUES, constants (or the words of a slot's pointer) that
+        // differ only as +0 / -0 do would be merged, and a NaN constant would never match itself
         p.frag_draw = (uint32_t)i;
         for (uint32_t j : frag_reps) {
             const DrawParams& q = g.hp[j];
             if (q.program == p.program && q.blend == p.blend && q.depth_test == p.depth_test && q.tex == p.tex && q.tex_w == p.tex_w &&
                 q.tex_h == p.tex_h && memcmp(&q.u, &p.u, sizeof p.u) == 0 &&
-                (p.program < SWR_PROG_USER_BASE || *b.draws[j].uconsts == *b.draws[i].uconsts)) { p.frag_draw = j; break; }
+                (p.program < SWR_PROG_USER_BASE || memcmp(b.draws[j].ublock.get(), b.draws[i].ublock.get(), sizeof(UserBlock)) == 0)) { p.frag_draw = j; break; }
         }
         // a representative must have its k_vertex block 0 run (it writes fog_r1 / fog_den): it has vertices and is not subject to the
         // device-side frustum test; the list is bounded so that a batch of thousands of distinct materials stays linear
@@ -513,9 +516,9 @@ int execute_batch(swr_context* c, const Batch& b, int mode, int count_stats) {
         const float4** bp = at<const float4*>(stage, P.up.off_bp);
         for (size_t i = 0; i < nd; ++i) bp[i] = b.draws[i].frustum_cull ? b.draws[i].mesh->d_bounds : nullptr;
     }
-    if (b_has_user_program(b)) {                  // each draw's captured constants (k_raster_c reads those of the draw's frag_draw)
-        float* uc = at<float>(stage, P.up.off_consts);
-        for (size_t i = 0; i < nd; ++i) memcpy(uc + 64 * i, b.draws[i].uconsts->data(), 64 * sizeof(float));
+    if (b_has_user_program(b)) {                  // each draw's captured block (k_raster_c reads that of the draw's frag_draw)
+        UserBlock* ub = at<UserBlock>(stage, P.up.off_consts);
+        for (size_t i = 0; i < nd; ++i) ub[i] = *b.draws[i].ublock;
     }
     SWR_HIP(c, hipMemcpyAsync(S.d_upload.p, stage, P.up.bytes, hipMemcpyHostToDevice, F));
     if ((rc = launch_geometry(c, P, g, n_tiles, count_stats))) return rc;
@@ -745,8 +748,12 @@ int record_draw(swr_context* c, swr_mesh* mesh, const float* model, const float*
     d.p.nm_flags = c->nm_flags;
     d.mesh = mesh;
     d.frustum_cull = frustum_cull;
-    if (uprog) {       // the constants as they are NOW (a C# closure's captured fields): later set_constants calls leave this draw alone
-        d.uconsts = std::make_shared<const std::vector<float>>(uprog->constants, uprog->constants + 64);
+    if (uprog) {       // the constants and the slots' textures as they are NOW (a C# closure's captured fields): later set_constants,
+                       // set_texture and set_filter calls leave this draw alone
+        auto ub = std::make_shared<UserBlock>();
+        memcpy(ub->constants, uprog->constants, sizeof ub->constants);
+        for (int s = 0; s < SWR_PROGRAM_TEXTURES - 1; ++s) ub->tex[s] = texture_slot_of(uprog->tex[s]);
+        d.ublock = std::move(ub);
         d.prog = std::move(uprog);
     }
     if (frustum_cull) { int rc = ensure_bounds(c, mesh); if (rc) return rc; }

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_vertex_user(const DrawParams
                                                 float4* __restrict__ vnorm /* never null here */,
                                                 uint32_t* __restrict__ zero_words, uint32_t n_zero,
                                                 uint32_t* __restrict__ zero_hist,
-                                                const float* __restrict__ user_consts /* 64 captured constants per draw */) {
+                                                const float* __restrict__ user_consts /* SWR_USER_BLOCK_WORDS per draw: 64 captured constants, the texture slots */) {
     SWR_FRONT_ENTER();
     for (uint32_t i = blockIdx.x * (uint32_t)SWR_GEOM_BLOCK + threadIdx.x; i < n_zero; i += gridDim.x * (uint32_t)SWR_GEOM_BLOCK) zero_words[i] = 0u;
     if (blockIdx.x == 0) for (uint32_t i = threadIdx.x; i < 512u; i += (uint32_t)SWR_GEOM_BLOCK) zero_hist[i] = 0u;
@@ -153,7 +153,9 @@ __global__ __launch_bounds__(SWR_GEOM_BLOCK) void k_vertex_user(const DrawParams
         in.normal = make_float3(q1.y, q1.z, q1.w);
         in.color = q2;
         // all uniform over the block: the matrices, the uniform block and the constants are read with scalar loads
-        const swr_vs_env env = { dp->model, dp->view, dp->proj, dp->u, user_consts + 64u * bm.draw, dp->nm_flags };
+        const float* ublock = user_consts + (uint32_t)SWR_USER_BLOCK_WORDS * bm.draw;
+        const swr_vs_env env = { dp->model, dp->view, dp->proj, dp->u, ublock, dp->nm_flags, dp,
+                                 reinterpret_cast<const TextureSlot*>(ublock + SWR_USER_CONSTANTS) };
         swr_vs_out out;
         out.clip_position = make_float4(0.f, 0.f, 0.f, 0.f); out.color = make_float4(0.f, 0.f, 0.f, 0.f);
         out.tex_coord = make_float2(0.f, 0.f); out.normal = make_float3(0.f, 0.f, 0.f);

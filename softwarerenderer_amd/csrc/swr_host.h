@@ -28,6 +28,14 @@ namespace {
 
 thread_local std::string g_create_error;
 
+// A texture as it is NOW, as a program's texture slot captures it (TextureSlot, swr_device.h): pointer, size and filter, the
+// block-linear copy where the texture has one -- what record_draw writes into DrawParams for a draw's own texture.  Null: unbound.
+TextureSlot texture_slot_of(const swr_texture* t) {
+    if (!t) return TextureSlot{ nullptr, 0, 0 };
+    if (t->bilinear && t->d_blocked) return TextureSlot{ t->d_blocked, -t->w, -t->h };
+    return TextureSlot{ t->d_rgba, t->w, t->bilinear ? -t->h : t->h };
+}
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -72,7 +80,8 @@ struct UserProg {
     hipModule_t mod = nullptr;
     hipFunction_t fn[2] = { nullptr, nullptr };     // [EARLYOUT]
     hipFunction_t vertex_fn = nullptr, setup_fn = nullptr;   // programs with a vertex half only: launched instead of k_vertex / k_setup
-    float constants[64] = {};                        // swr_program_set_constants: copied into each draw when it is recorded
+    float constants[SWR_USER_CONSTANTS] = {};        // swr_program_set_constants: copied into each draw when it is recorded
+    const swr_texture* tex[SWR_PROGRAM_TEXTURES - 1] = {};   // swr_program_set_texture, slots 1 ..: captured (texture_slot_of) by each draw likewise
     ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
 };
 
@@ -87,12 +96,21 @@ struct PostProg {
     ~PostProg() { if (mod) (void)hipModuleUnload(mod); }
 };
 
+// the per-draw block of a user-program batch as the device reads it (SWR_USER_BLOCK_WORDS, swr_device.h).  Two draws share their
+// fragment-stage state only if their blocks are bitwise equal (batch_geometry), so it has no padding and is compared with memcmp.
+struct UserBlock {
+    float constants[SWR_USER_CONSTANTS];
+    TextureSlot tex[SWR_PROGRAM_TEXTURES - 1];
+};
+static_assert(sizeof(UserBlock) == SWR_USER_BLOCK_WORDS * sizeof(float) && offsetof(UserBlock, tex) == SWR_USER_CONSTANTS * sizeof(float),
+              "the block k_raster_c and k_vertex_user index by SWR_USER_BLOCK_WORDS");
+
 struct DrawCmd {
     DrawParams p;
     swr_mesh* mesh;
     bool frustum_cull = false;                 // render only if IsSphereInFrustum(mesh bounds, model, view, proj)
     std::shared_ptr<UserProg> prog;            // user programs only: the program ...
-    std::shared_ptr<const std::vector<float>> uconsts;   // ... and its 64 constants as they were when the draw was recorded
+    std::shared_ptr<const UserBlock> ublock;   // ... and its constants and texture slots 1 .. as they were when the draw was recorded
 };
 
 // one flush = one batch; kept until the host has seen that it fitted (optimistic execution, see swr::Ctrl)

@@ -45,15 +45,11 @@
 
 namespace swr {
 
-// one texture slot as a present captured it: what a draw's DrawParams hold (swr_flush.h) -- h < 0: the bilinear filter; w < 0 as well:
-// `texels` is the block-linear copy; texels null: nothing bound
-struct PostTexture { const uint8_t* texels; int w, h; };
-
-// k_post's last argument, by value: the program's constants and texture slots as they were when the present call was made, and for
-// the texel formats the target's block-linear copy (null: it has none)
+// k_post's last argument, by value: the program's constants and texture slots (TextureSlot, swr_device.h) as they were when the present
+// call was made, and for the texel formats the target's block-linear copy (null: it has none)
 struct PostConstants {
     float v[SWR_POST_CONSTANTS];
-    PostTexture tex[SWR_POST_TEXTURES];
+    TextureSlot tex[SWR_POST_TEXTURES];
     uint32_t* blocked;
 };
 
@@ -86,7 +82,7 @@ struct swr_post_env {
     // the library's own, behind the helpers below:
     const float4* plane_;        // height x width resolved pixels (the frame itself under (1, 1))
     const float* depth_;         // the frame's depth plane, height * ky rows of width * kx words
-    const swr::PostTexture* textures_;    // the SWR_POST_TEXTURES slots (kernel arguments: constant memory)
+    const swr::TextureSlot* textures_;    // the SWR_POST_TEXTURES slots (kernel arguments: constant memory)
 };
 
 __device__ __forceinline__ int swr_post_clamp_index(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
@@ -107,22 +103,16 @@ __device__ __forceinline__ bool swr_post_has_texture(const swr_post_env& env, in
 // it when the present call was made; (1, 1, 1, 1) from an unbound slot
 __device__ __forceinline__ float4 swr_post_sample(const swr_post_env& env, int slot, float2 uv) {
     if (!swr_post_has_texture(env, slot)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-    const swr::PostTexture t = env.textures_[slot];
-    return swr::texture_fetch(t.texels, t.w, t.h, uv.x, uv.y);
+    return swr::texture_slot_sample(env.textures_[slot], uv.x, uv.y);
 }
 __device__ __forceinline__ int2 swr_post_texture_size(const swr_post_env& env, int slot) {
     if (!swr_post_has_texture(env, slot)) return make_int2(0, 0);
-    const swr::PostTexture t = env.textures_[slot];
-    return make_int2(t.w < 0 ? -t.w : t.w, t.h < 0 ? -t.h : t.h);
+    return swr::texture_slot_size(env.textures_[slot]);
 }
 // texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1], each byte times the float 1 / 255 (Texture.cs:57-62): no filter, no uv
 __device__ __forceinline__ float4 swr_post_texel(const swr_post_env& env, int slot, int x, int y) {
     if (!swr_post_has_texture(env, slot)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-    const swr::PostTexture t = env.textures_[slot];
-    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
-    x = swr_post_clamp_index(x, w); y = swr_post_clamp_index(y, h);
-    const uint32_t* __restrict__ t32 = reinterpret_cast<const uint32_t*>(t.texels);
-    return swr::texture_unpack(t32[t.w < 0 ? swr::bilinear_texel_offset<true>(w, x, y) : swr::bilinear_texel_offset<false>(w, x, y)]);
+    return swr::texture_slot_texel(env.textures_[slot], x, y);
 }
 
 // the user's program (always inlined into k_post)

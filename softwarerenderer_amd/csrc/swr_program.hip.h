@@ -45,7 +45,9 @@ struct swr_fs_env {
     const float* constants;      // constants[0..63] (swr_program_set_constants when the draw was recorded; zeros if never set)
     int x, y;                    // pixel
     const uint8_t* tex;          // the draw's texture (null: none) in the layout texture_fetch reads
-    int tex_w, tex_h;
+    int tex_w, tex_h;            // (their signs carry the filter and the layout: swr_texture_size(env, 0) is the size)
+    // the library's own, behind the slot helpers below:
+    const swr::TextureSlot* slots_;      // the draw's captured texture slots 1 .. SWR_PROGRAM_TEXTURES - 1
 };
 
 // Texture.Sample (Texture.cs:43-63): nearest, or the build-defined bilinear filter when the texture was switched to it -- the function
@@ -55,6 +57,27 @@ __device__ __forceinline__ float4 swr_sample(const swr_fs_env& env, float2 uv) {
     if (!swr_has_texture(env)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     return swr::texture_fetch(env.tex, env.tex_w, env.tex_h, uv.x, uv.y);
 }
+// THE TEXTURE SLOTS (swr_program_set_texture).  Slot 0 is the draw's texture, slots 1 .. SWR_PROGRAM_TEXTURES - 1
+// are the program's, as they were when the draw was recorded.  An unbound slot, and a slot outside 0 .. SWR_PROGRAM_TEXTURES - 1, has no
+// texture: it samples and reads (1, 1, 1, 1) and measures (0, 0).  The slot may be computed per fragment.  A program that calls none of
+// these loads nothing of the slots.
+//   swr_has_texture(env, slot)
+//   swr_sample(env, slot, uv)         Texture.Sample exactly as swr_sample(env, uv) computes it for slot 0 (swr::texture_fetch)
+//   swr_texel(env, slot, x, y)        the row-major texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1], each byte times 1 / 255
+//   swr_texture_size(env, slot)       (w, h), positive whatever the filter
+// swr_slot_: the slot's record, for either half's env (slot0 = the draw's texture as that half holds it)
+__device__ __forceinline__ swr::TextureSlot swr_slot_(const swr::TextureSlot& slot0, const swr::TextureSlot* slots, int slot) {
+    if (slot == 0) return slot0;
+    if ((unsigned)(slot - 1) < (unsigned)(SWR_PROGRAM_TEXTURES - 1)) return slots[slot - 1];
+    return swr::TextureSlot{ nullptr, 0, 0 };
+}
+__device__ __forceinline__ swr::TextureSlot swr_slot_(const swr_fs_env& env, int slot) {
+    return swr_slot_(swr::TextureSlot{ swr_has_texture(env) ? env.tex : nullptr, env.tex_w, env.tex_h }, env.slots_, slot);
+}
+__device__ __forceinline__ bool swr_has_texture(const swr_fs_env& env, int slot) { return swr::texture_slot_bound(swr_slot_(env, slot)); }
+__device__ __forceinline__ float4 swr_sample(const swr_fs_env& env, int slot, float2 uv) { return swr::texture_slot_sample(swr_slot_(env, slot), uv.x, uv.y); }
+__device__ __forceinline__ float4 swr_texel(const swr_fs_env& env, int slot, int x, int y) { return swr::texture_slot_texel(swr_slot_(env, slot), x, y); }
+__device__ __forceinline__ int2 swr_texture_size(const swr_fs_env& env, int slot) { return swr::texture_slot_size(swr_slot_(env, slot)); }
 // the build's System.Numerics model (SWR_DOT_PAIRWISE): Vector3.Dot.  (swr_lerp, swr_max and swr_clamp: swr_user_math.hip.h)
 __device__ __forceinline__ float swr_dot3(float3 a, float3 b) { return swr::dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 // a null result: nothing is written (and under BlendMode.None the row's early-out applies)
@@ -80,7 +103,19 @@ struct swr_vs_env {
     const float* constants;      // constants[0..63]: the SAME captured constants the fragment half reads
     uint32_t nm_flags;           // the context's System.Numerics model of Transform / TransformNormal (swr_set_transform_fma) when the
                                  // draw was recorded: the helpers below read it
+    // the library's own, behind the slot helpers below:
+    const swr::DrawParams* draw_;        // slot 0: the draw's texture
+    const swr::TextureSlot* slots_;      // the draw's captured texture slots 1 .. SWR_PROGRAM_TEXTURES - 1
 };
+// The texture slots in the vertex half: the four functions of the fragment half over the same four slots, the same bytes and the same
+// sampler -- a value sampled here and one sampled in the fragment half at the same uv are the same words.
+__device__ __forceinline__ swr::TextureSlot swr_slot_(const swr_vs_env& env, int slot) {
+    return swr_slot_(swr::TextureSlot{ env.draw_->tex_h != 0 ? env.draw_->tex : nullptr, env.draw_->tex_w, env.draw_->tex_h }, env.slots_, slot);
+}
+__device__ __forceinline__ bool swr_has_texture(const swr_vs_env& env, int slot) { return swr::texture_slot_bound(swr_slot_(env, slot)); }
+__device__ __forceinline__ float4 swr_sample(const swr_vs_env& env, int slot, float2 uv) { return swr::texture_slot_sample(swr_slot_(env, slot), uv.x, uv.y); }
+__device__ __forceinline__ float4 swr_texel(const swr_vs_env& env, int slot, int x, int y) { return swr::texture_slot_texel(swr_slot_(env, slot), x, y); }
+__device__ __forceinline__ int2 swr_texture_size(const swr_vs_env& env, int slot) { return swr::texture_slot_size(swr_slot_(env, slot)); }
 // new Shaders.VertexOutput() (Shaders.cs:26-47): zero-initialised before swr_vertex is called, Interpolate = true
 struct swr_vs_out {
     float4 clip_position;        // ClipPosition

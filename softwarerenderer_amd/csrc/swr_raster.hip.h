@@ -18,7 +18,7 @@ struct RasterArgs {
     const uint32_t* __restrict__ tile_start;
     const uint32_t* __restrict__ tile_count;
     const float4* __restrict__ vnorm;          // VertexOutput.Normal per VOut entry (DEBUG_VARYINGS / user-program batches only, else null)
-    const float* __restrict__ user_consts;     // user-program batches: 64 captured constants per draw (swr_program_set_constants), else null
+    const float* __restrict__ user_consts;     // user-program batches: SWR_USER_BLOCK_WORDS per draw (64 captured constants, then the texture slots), else null
     uint32_t vout_bytes;                       // size of the VOut array (< 4 GiB: k_raster_c addresses it with 32-bit byte offsets)
     const uint4* __restrict__ pair_refs;       // per pair {record index, vertex refs of outputs[0..2]} (k_cover)
     const uint4* __restrict__ tile_order;      // per dispatch position, heaviest first: {band-local tile, first list entry, pairs, -} (tile_place_block)

@@ -587,7 +587,10 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
             const float sx[3] = { r0.x, r0.y, r0.z }, sy[3] = { r0.w, r1.x, r1.y };
             const float inv_w = 1.0f / (float)(a.fp.width - 1), inv_h = 1.0f / (float)(a.fp.height - 1);      // Rasterizer.cs:362-363
             const swr_fs_in in = interpolate_fs_in(w0f, w1f, w2f, clip, col, uvn, wnz, nrm, d4, sx, sy, inv_w, inv_h);
-            const swr_fs_env env = { a.draws[draw].u, a.user_consts + 64u * draw, px, py, dc.tex, dc.tex_w, dc.tex_h };
+            // (the draw's block: its constants, then its texture slots, which an inlined program that calls no slot helper never loads)
+            const float* ublock = a.user_consts + (uint32_t)SWR_USER_BLOCK_WORDS * draw;
+            const swr_fs_env env = { a.draws[draw].u, ublock, px, py, dc.tex, dc.tex_w, dc.tex_h,
+                                     reinterpret_cast<const TextureSlot*>(ublock + SWR_USER_CONSTANTS) };
             return swr_fragment(in, env);
         }
 #endif

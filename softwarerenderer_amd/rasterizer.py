@@ -230,6 +230,12 @@ class Device:
         a = _f32(values if values is not None else [], None)
         self._ck(self._lib.swr_program_set_constants(self._ctx, int(program_id), _fptr(a) if a.size else None, int(a.size)))
 
+    def set_program_texture(self, program_id: int, slot: int, texture: Optional["Texture"]):
+        """Bind a Texture of this Device to slot 1 .. 3 of a user program (None unbinds; slot 0 is the draw's own texture): both
+        halves read it with swr_sample / swr_texel(env, slot, ..).  Each draw captures the slots, and each texture's filter, when
+        it is recorded."""
+        self._ck(self._lib.swr_program_set_texture(self._ctx, int(program_id), int(slot), texture._h if texture is not None else None))
+
     def set_stream(self, hip_stream: int):
         self._ck(self._lib.swr_set_stream(self._ctx, C.c_void_p(hip_stream)))
 
@@ -365,15 +371,20 @@ class ShaderProgram:
 
 class CustomProgram(ShaderProgram):
     """A user program given as source (Shaders.Custom): the fragment half and, optionally, the vertex half; compiled once per Device
-    on first use; `constants` (up to 64 floats, the fields the C# closures capture, read by both halves) are set before every draw,
-    so each draw renders with the values it was given."""
+    on first use; `constants` (up to 64 floats, the fields the C# closures capture, read by both halves) and `textures` (up to three
+    Textures or None for slots 1 .. 3, the closures' further Texture fields; `texture` is slot 0) are set before every draw, so each
+    draw renders with what it was given."""
 
     def __init__(self, source: str, uniforms: Optional[N.Uniforms] = None, texture: Optional[Texture] = None, constants=None,
-                 vertex_source: Optional[str] = None):
+                 vertex_source: Optional[str] = None, textures=None):
         super().__init__(Program.FlatColor, uniforms, texture)
         self.source = source
         self.vertex_source = vertex_source
         self.constants = constants
+        textures = tuple(textures) if textures is not None else ()
+        if len(textures) > N.SWR_PROGRAM_TEXTURES - 1:
+            raise ValueError("a user program owns three texture slots (1 .. 3); slot 0 is `texture`")
+        self.textures = textures
         self._ids = {}          # id(Device) -> (Device, program id)
 
     def _program_for(self, dev: "Device") -> int:
@@ -383,6 +394,8 @@ class CustomProgram(ShaderProgram):
             self._ids[id(dev)] = hit
         pid = hit[1]
         dev.set_program_constants(pid, self.constants)
+        for k in range(N.SWR_PROGRAM_TEXTURES - 1):
+            dev.set_program_texture(pid, k + 1, self.textures[k] if k < len(self.textures) else None)
         return pid
 
 
@@ -411,10 +424,10 @@ class Shaders:
         return ShaderProgram(Program.Phong4Point, uniforms, texture)
 
     @staticmethod
-    def Custom(source: str, uniforms=None, texture=None, constants=None, vertex_source=None):
+    def Custom(source: str, uniforms=None, texture=None, constants=None, vertex_source=None, textures=None):
         """Any Shaders.FragmentShader -- with `vertex_source`, any (Shaders.VertexShader, Shaders.FragmentShader) pair -- restated in
-        C++ against the contract of include/swr.h (swr_program_create_vf)."""
-        return CustomProgram(source, uniforms, texture, constants, vertex_source)
+        C++ against the contract of include/swr.h (swr_program_create_vf).  `textures`: slots 1 .. 3 (swr_program_set_texture)."""
+        return CustomProgram(source, uniforms, texture, constants, vertex_source, textures)
 
 
 class MainWindow:
