@@ -203,7 +203,7 @@ int  swr_flatten_rgb_device_async(swr_context* ctx, float* d_rgb);
  * of kx and its height of ky (then every band's and stripe's rows are a multiple of ky and the concatenated band payloads are the
  * resolved frame).  Per output pixel and channel, in float32: the kx samples of each row summed as a balanced pairwise tree left to
  * right, the ky row sums by the same tree top to bottom, times the float 1 / (kx * ky); alpha is dropped; (1, 1) gives the
- * flatten's values (csrc/swr_resolve.hip.h).  Bad factors, a size that does not divide and NULL pointers:
+ * flatten's values (csrc/swr_deliver.hip.h).  Bad factors, a size that does not divide and NULL pointers:
  * SWR_ERR_INVALID_ARG, nothing written, no ticket issued.  A zero-size target: SWR_OK, nothing written. */
 /* host only: the payload's size under the size and band in force, out_width = W / kx, out_rows = band rows / ky */
 int  swr_resolved_size(swr_context* ctx, int kx, int ky, int* out_width, int* out_rows);
@@ -222,7 +222,7 @@ int  swr_resolve_rgb_device_async(swr_context* ctx, int kx, int ky, float* d_rgb
  * float32 and ties to even.  No gamma, no dither (the reference has neither: it hands the floats to GL, which clamps and rounds
  * them to its 8-bit framebuffer; GL prefers round-to-nearest and leaves ties open).  bpp = 3 delivers R, G, B; bpp = 4 delivers
  * R, G, B, 255.  Rows are tightly packed: out_rows x out_width x bpp contiguous bytes, and the concatenated band payloads are the
- * frame (csrc/swr_present8.hip.h).  A bpp other than 3 or 4, bad factors, a size that does not divide and NULL
+ * frame (csrc/swr_deliver.hip.h).  A bpp other than 3 or 4, bad factors, a size that does not divide and NULL
  * pointers: SWR_ERR_INVALID_ARG, nothing written, no ticket issued.  A zero-size target: SWR_OK, nothing written. */
 /* host only: swr_resolved_size plus out_bytes = out_rows * out_width * bpp */
 int  swr_present8_size(swr_context* ctx, int kx, int ky, int bpp, int* out_width, int* out_rows, size_t* out_bytes);
@@ -260,7 +260,7 @@ int  swr_texture_set_filter(swr_context* ctx, swr_texture* tex, int bilinear);
 /* Texture.Sample, Texture.cs:43-63, batched: n uv pairs -> n RGBA float4 (runs on the GPU) */
 int  swr_texture_sample(swr_context* ctx, const swr_texture* tex, const float* uv, int n, float* out_rgba);
 /* RENDER TO TEXTURE (build-defined: the reference has Texture over Image<Rgba32> and MainWindow's float buffers and no link between
- * them; csrc/swr_rtt.hip.h): a frame becomes a draw's texture without leaving the device -- a scope, a mirror,
+ * them; csrc/swr_deliver.hip.h): a frame becomes a draw's texture without leaving the device -- a scope, a mirror,
  * a camera screen, a minimap, last frame's image. */
 enum { SWR_TEXTURE_ALPHA_OPAQUE = 0, SWR_TEXTURE_ALPHA_KEEP = 1 };
 /* a texture of zeros without host data, to be filled by swr_texture_update_from_frame; the limits of swr_texture_create */

@@ -43,9 +43,7 @@
 #include "swr_cull.hip.h"
 #include "swr_raycast.hip.h"
 #include "swr_character.hip.h"
-#include "swr_resolve.hip.h"
-#include "swr_present8.hip.h"
-#include "swr_rtt.hip.h"
+#include "swr_deliver.hip.h"
 #include "swr_post.hip.h"
 
 using namespace swr;
@@ -113,23 +111,25 @@ int payload_rows(const swr_context* c, const Payload& p) { return band_rows(c) /
 size_t payload_pixels(const swr_context* c, const Payload& p) { return (size_t)payload_width(c, p) * (size_t)payload_rows(c, p); }
 size_t payload_bytes(const swr_context* c, const Payload& p) { return payload_pixels(c, p) * payload_bpp(p); }
 
+// the delivery kernels' launch: one thread per output pixel, SWR_RESOLVE_BLOCK_X x _Y of them per block (swr_deliver.hip.h)
+struct DeliverShape { dim3 grid, block; };
+DeliverShape deliver_shape(uint32_t ow, uint32_t orows) {       // a frame is at most 65535 x 65535
+    return { dim3((ow + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y),
+             dim3(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y) };
+}
+
 using ResolveKernel = void (*)(const float4*, float*, int, int);
 ResolveKernel resolve_kernel(int kx, int ky) {
-    return with_factor<ResolveKernel>(kx, [&](auto x) -> ResolveKernel { return with_factor<ResolveKernel>(ky, [](auto y) -> ResolveKernel { return k_resolve_rgb<decltype(x)::value, decltype(y)::value>; }); });
+    return with_factors<ResolveKernel>(kx, ky, [](auto x, auto y) -> ResolveKernel { return k_resolve_rgb<decltype(x)::value, decltype(y)::value>; });
 }
 using Present8Kernel = void (*)(const float4*, uint8_t*, uint32_t, uint32_t);
 template <int BPP> Present8Kernel present8_kernel(int kx, int ky) {
-    return with_factor<Present8Kernel>(kx, [&](auto x) -> Present8Kernel { return with_factor<Present8Kernel>(ky, [](auto y) -> Present8Kernel { return k_present8<decltype(x)::value, decltype(y)::value, BPP>; }); });
+    return with_factors<Present8Kernel>(kx, ky, [](auto x, auto y) -> Present8Kernel { return k_present8<decltype(x)::value, decltype(y)::value, BPP>; });
 }
 
 int launch_present8(swr_context* c, const Payload& p, uint8_t* d_out) {
-    const uint32_t ow = (uint32_t)payload_width(c, p), orows = (uint32_t)payload_rows(c, p);    // a frame is at most 65535 x 65535
-#if defined(SWR_PRESENT8_FOUR_PER_THREAD)
-    const dim3 block(SWR_PRESENT8_BLOCK), grid((present8_threads(ow * orows) + SWR_PRESENT8_BLOCK - 1) / SWR_PRESENT8_BLOCK);
-#else
-    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
-    const dim3 grid((ow + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
-#endif
+    const uint32_t ow = (uint32_t)payload_width(c, p), orows = (uint32_t)payload_rows(c, p);
+    const auto [grid, block] = deliver_shape(ow, orows);
     const Present8Kernel k = p.format == PAYLOAD_RGB8 ? present8_kernel<3>(p.kx, p.ky) : present8_kernel<4>(p.kx, p.ky);
     hipLaunchKernelGGL(k, grid, block, 0, c->stream, (const float4*)c->color, d_out, ow, orows);
     SWR_HIP(c, hipGetLastError());
@@ -138,8 +138,7 @@ int launch_present8(swr_context* c, const Payload& p, uint8_t* d_out) {
 
 using ResolveRgbaKernel = void (*)(const float4*, float4*, uint32_t, uint32_t);
 ResolveRgbaKernel resolve_rgba_kernel(int kx, int ky) {
-    using K = ResolveRgbaKernel;
-    return with_factor<K>(kx, [&](auto x) -> K { return with_factor<K>(ky, [](auto y) -> K { return k_resolve_rgba<decltype(x)::value, decltype(y)::value>; }); });
+    return with_factors<ResolveRgbaKernel>(kx, ky, [](auto x, auto y) -> ResolveRgbaKernel { return k_resolve_rgba<decltype(x)::value, decltype(y)::value>; });
 }
 
 // a program's texture slots as they are NOW, in the encoding a draw records (swr_flush.h: h < 0 the bilinear filter, w < 0 as well
@@ -151,10 +150,9 @@ void capture_post_textures(const PostProg* post, PostConstants& k) {
 // A post program over s's whole frame, on c's stream (s == c for a present): the frame resolved into s's RGBA plane (under (1, 1) the
 // frame is that plane), then k_post `fn` of the program over it, with the constants and the texture slots as they are now.
 // d_blocked: the texel formats' second destination, or null.
-int launch_post_over(swr_context* c, swr_context* s, const PostProg* post, int fn, int kx, int ky, void* d_out, uint32_t* d_blocked) {
-    const uint32_t ow = (uint32_t)(std::max(0, s->W) / kx), orows = (uint32_t)(band_rows(s) / ky);    // a frame is at most 65535 x 65535
-    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
-    const dim3 grid((ow + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
+int launch_post_over(swr_context* c, swr_context* s, const PostProg* post, PostKernel fn, int kx, int ky, void* d_out, uint32_t* d_blocked) {
+    const uint32_t ow = (uint32_t)(std::max(0, s->W) / kx), orows = (uint32_t)(band_rows(s) / ky);
+    const auto [grid, block] = deliver_shape(ow, orows);
     const float4* plane = s->color;
     if (kx != 1 || ky != 1) {
         const size_t bytes = (size_t)ow * orows * sizeof(float4);
@@ -177,7 +175,10 @@ int launch_post_over(swr_context* c, swr_context* s, const PostProg* post, int f
     SWR_HIP(c, hipModuleLaunchKernel(post->fn[fn], grid.x, grid.y, 1, block.x, block.y, 1, 0, c->stream, args, nullptr));
     return SWR_OK;
 }
-int launch_post(swr_context* c, const Payload& p, void* d_out) { return launch_post_over(c, c, p.post, p.format, p.kx, p.ky, d_out, nullptr); }
+int launch_post(swr_context* c, const Payload& p, void* d_out) {
+    const PostKernel fn = p.format == PAYLOAD_RGB32F ? POST_RGB32F : p.format == PAYLOAD_RGB8 ? POST_RGB8 : POST_RGBX8;
+    return launch_post_over(c, c, p.post, fn, p.kx, p.ky, d_out, nullptr);
+}
 
 // the payload of the band's colour plane in device memory (4-byte aligned), on the context's stream (checked, and not empty)
 int launch_payload(swr_context* c, const Payload& p, void* d_out) {
@@ -186,9 +187,7 @@ int launch_payload(swr_context* c, const Payload& p, void* d_out) {
     float* d_rgb = (float*)d_out;
     if (!p.resolve) return launch_flatten(c, d_rgb, band_pixels(c));
     const int ow = payload_width(c, p), orows = payload_rows(c, p);
-    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
-    const int per_block_x = resolve_block_out_x(p.kx);
-    const dim3 grid((ow + per_block_x - 1) / per_block_x, (orows + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
+    const auto [grid, block] = deliver_shape((uint32_t)ow, (uint32_t)orows);
     hipLaunchKernelGGL(resolve_kernel(p.kx, p.ky), grid, block, 0, c->stream, (const float4*)c->color, d_rgb, ow, orows);
     SWR_HIP(c, hipGetLastError());
     return SWR_OK;
@@ -291,8 +290,8 @@ int pixel_transfer(swr_context* c, int x, int y, void* plane, size_t bytes, void
 using RttKernel = void (*)(const float4*, uint32_t*, uint32_t*, uint32_t, uint32_t);
 RttKernel rtt_kernel(int kx, int ky, bool alpha, bool blocked) {
     using K = RttKernel;
-    return with_flag<K>(alpha, [&](auto a) -> K { return with_flag<K>(blocked, [&](auto b) -> K { return with_factor<K>(kx, [&](auto x) -> K { return with_factor<K>(ky, [](auto y) -> K {
-        return k_frame_to_texture<decltype(x)::value, decltype(y)::value, decltype(a)::value, decltype(b)::value>; }); }); }); });
+    return with_flag<K>(alpha, [&](auto a) -> K { return with_flag<K>(blocked, [&](auto b) -> K { return with_factors<K>(kx, ky, [](auto x, auto y) -> K {
+        return k_frame_to_texture<decltype(x)::value, decltype(y)::value, decltype(a)::value, decltype(b)::value>; }); }); });
 }
 
 // swr_texture_create / swr_texture_create_target: w x h texels on the context's stream, the caller's or (rgba8 null) zeros
@@ -345,13 +344,12 @@ int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, 
         SWR_HIP(c, hipStreamWaitEvent(c->stream, src->rtt_frame_ev, 0));
     }
     const bool blocked = t->d_blocked != nullptr;         // (made by swr_texture_set_filter: both sides are multiples of 4)
-    const dim3 block(SWR_RESOLVE_BLOCK_X, SWR_RESOLVE_BLOCK_Y);
-    const dim3 grid(((uint32_t)t->w + SWR_RESOLVE_BLOCK_X - 1) / SWR_RESOLVE_BLOCK_X, ((uint32_t)t->h + SWR_RESOLVE_BLOCK_Y - 1) / SWR_RESOLVE_BLOCK_Y);
     if (post) {
         // (the resolve writes src's plane and the program may sample src's textures: both behind rtt_frame_ev, and src's later work --
         // a present, an update of such a texture -- behind rtt_done_ev)
-        if ((rc = launch_post_over(c, src, post, alpha_mode == SWR_TEXTURE_ALPHA_KEEP ? 4 : 3, kx, ky, t->d_rgba, (uint32_t*)t->d_blocked))) return rc;
+        if ((rc = launch_post_over(c, src, post, alpha_mode == SWR_TEXTURE_ALPHA_KEEP ? POST_TEXELS_KEEP : POST_TEXELS_OPAQUE, kx, ky, t->d_rgba, (uint32_t*)t->d_blocked))) return rc;
     } else {
+        const auto [grid, block] = deliver_shape((uint32_t)t->w, (uint32_t)t->h);
         hipLaunchKernelGGL(rtt_kernel(kx, ky, alpha_mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
                            (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
         SWR_HIP(c, hipGetLastError());
@@ -957,7 +955,7 @@ int swr_post_create(swr_context* c, const char* src, int* post_id) {
     if (rc) { c->err = log; return rc; }
     auto p = std::make_shared<PostProg>();
     SWR_HIP(c, hipModuleLoadData(&p->mod, code->code.data()));
-    for (int k = 0; k < 5; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
+    for (int k = 0; k < POST_KERNELS; ++k) SWR_HIP(c, hipModuleGetFunction(&p->fn[k], p->mod, code->names[k].c_str()));
     static std::atomic<int> next_post{1};                   // one sequence for the process: another context's id is unknown here
     const int id = next_post++;
     c->posts[id] = std::move(p);

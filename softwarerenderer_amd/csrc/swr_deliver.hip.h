@@ -1,0 +1,190 @@
+// swr_deliver.hip.h -- how a frame leaves the raster stage: the band's colour plane box-filtered by kx x ky on the device and stored as
+// RGB floats (supersampled present), as bytes (8-bit present, section 18), as a texture's RGBA8 texels (render
+// to texture, section 19) or as the RGBA plane a post program reads (section 20; k_post itself is swr_post.hip.h, over the same grid
+// and the same stores).  All of it is build-defined: the reference has no supersampling (its RenderScale stops at 1,
+// MainWindow.cs:93,313-315), uploads floats into a texture with Nearest filters (:82-83) that GL then clamps to [0, 1] and rounds to
+// 8 bits (:157-169), and has no link between a Texture (Texture.cs:31-41) and MainWindow's float buffers (:25-31).
+//
+// THE RESOLVE (tests/resolve_cases.py restates it in numpy).  Every sample is a pixel of a larger reference frame; the filter adds
+// nothing but this arithmetic, per output pixel and per channel R, G, B, A, in float32:
+//   1. in each of the ky source rows the kx adjacent samples are summed as a balanced pairwise tree, left to right:
+//      a0+a1, (a0+a1)+(a2+a3), ((a0+a1)+(a2+a3))+((a4+a5)+(a6+a7));
+//   2. the ky row sums are summed by the same tree, top to bottom;
+//   3. the sum is multiplied by the float 1/(kx*ky) (a power of two).
+// Additions and one multiply: nothing fuses (-ffp-contract=off), denormals are kept, non-finite values follow IEEE.  Channels never
+// mix, so a kernel that drops alpha (as k_flatten_rgb does) delivers the same R, G, B words as one that keeps it -- and the compiler
+// drops the unused channel's loads and adds with it.  Under (1, 1) the result is the pixel's own floats.
+//
+// THE QUANTISER (tests/present8_cases.py restates it in numpy).  The input is a resolved channel c, rounded to float32 before anything else:
+//   NaN                      -> 0
+//   c <= 0 (-0, < 0, -Inf)   -> 0
+//   c >= 1 (+Inf)            -> 255
+//   otherwise                -> (uint8) rintf(c * 255.0f): the product rounded to float32 (nothing fuses), ties to even.
+// No gamma and no dither: the reference has neither.  The GL specification prefers round-to-nearest for float -> unorm8 and leaves
+// ties open, so this is a choice, not a pin.  What follows from it: quantise(float32(k) / 255) == k for all 256 k, so under the
+// preferred rounding these bytes, uploaded as UnsignedByte into the reference's Rgba32f texture and drawn with Nearest, display the
+// byte that was uploaded.
+// Formats: BPP = 3 is R, G, B; BPP = 4 is R, G, B, 255 (alpha is dropped as in the flatten; the opaque byte makes the block RGBA8).
+// Rows are tightly packed: a band's payload is out_rows * out_w * BPP contiguous bytes.
+//
+// RENDER TO TEXTURE (tests/render_to_texture_cases.py restates it in numpy).  Texel (x, y) of a w x h texture updated from a source
+// plane of w * KX x h * KY pixels:
+//   R, G, B  the bytes k_present8<KX, KY, 4> delivers for output pixel (x, y): the resolve, then the quantiser.
+//   A        255 without ALPHA; with ALPHA the plane's .w through the same resolve and the same quantiser.
+//
+// THE KERNELS.  One thread per OUTPUT pixel on a plain 2-D grid, 64 x 4 threads per block, no stride loop (deliver_pixel).  The thread
+// reads its KX adjacent samples of each of its KY rows -- 12-byte loads where alpha is dropped, 16-byte loads where it is kept; a
+// wave's KX load instructions per row together read 64 * KX * 16 contiguous bytes, so every fetched line is consumed by the wave that
+// fetched it -- and stores once:
+//   k_resolve_rgb<KX, KY>        three floats
+//   k_present8<KX, KY, BPP>      three bytes (BPP 3) or one dword (BPP 4).  `out` must be 4-byte aligned (staging buffers are;
+//                                swr_resolve_rgb8_device checks)
+//   k_frame_to_texture<KX, KY, ALPHA, BLOCKED>  one dword row-major into `rgba`: a wave's store instruction writes 256 contiguous
+//                                bytes.  With BLOCKED the same dword goes to bilinear_texel_offset<true>(w, x, y) in `blocked` as well: a
+//                                wave's 64 texels of one row are 16 runs of 16 B, one per 64-byte block line, and the four rows of a
+//                                64 x 4 block of threads together complete each of those lines, so the copy the bilinear filter reads is
+//                                never stale and needs no second pass over the texture
+//   k_resolve_rgba<KX, KY>       one float4 into a window-sized plane of the context, for k_post.  Not launched under (1, 1), where the
+//                                frame is that plane already.  The plane is deliberate: a program that fetches neighbours would
+//                                otherwise redo a tree of up to 64 samples per tap.
+// Two other thread mappings were measured and removed: one lane per SOURCE pixel with in-wave adds for the resolve, and four
+// consecutive pixels per thread with whole-dword stores for the 8-bit present.  DESIGN.md sections 17 and 18 have the figures.
+// No LDS, no scratch, no inline assembly; nothing here is shared with the render kernels.  KX, KY in {1, 2, 4, 8} divide the
+// 16-pixel tile, so a band's stored rows are a multiple of KY and a block of samples never straddles a band or a stripe.  A frame is
+// at most 65535 x 65535 (swr_resize) and a texture has fewer than 2^30 texels (swr_texture_create): pixel and texel indices fit 32
+// bits, plane and payload offsets are size_t.
+#pragma once
+#include "swr_device.h"
+
+#define SWR_RESOLVE_BLOCK_X 64            // output pixels per block row: one wave
+#define SWR_RESOLVE_BLOCK_Y 4             // output rows per block
+
+namespace swr {
+
+// ---- the grid: this thread's output pixel; false outside out_w x out_rows
+__device__ __forceinline__ bool deliver_pixel(uint32_t out_w, uint32_t out_rows, uint32_t& ox, uint32_t& oy) {
+    ox = blockIdx.x * SWR_RESOLVE_BLOCK_X + threadIdx.x;
+    oy = blockIdx.y * SWR_RESOLVE_BLOCK_Y + threadIdx.y;
+    return ox < out_w && oy < out_rows;
+}
+// its index in a row-major payload
+__device__ __forceinline__ size_t deliver_index(uint32_t out_w, uint32_t ox, uint32_t oy) { return (size_t)oy * out_w + ox; }
+
+// ---- the resolve
+struct Rgba { float r, g, b, a; };
+
+__device__ __forceinline__ Rgba rgba_add(const Rgba a, const Rgba b) { return Rgba{a.r + b.r, a.g + b.g, a.b + b.b, a.a + b.a}; }
+
+// stage 1: N adjacent samples of one row, pairwise
+template <int N>
+__device__ __forceinline__ Rgba resolve_row(const float4* __restrict__ p) {
+    if constexpr (N == 1) {
+        const float4 v = p[0];
+        return Rgba{v.x, v.y, v.z, v.w};
+    } else {
+        const Rgba left = resolve_row<N / 2>(p);
+        const Rgba right = resolve_row<N / 2>(p + N / 2);
+        return rgba_add(left, right);
+    }
+}
+
+// stage 2: the sums of N rows (`pitch` pixels apart), pairwise
+template <int KX, int N>
+__device__ __forceinline__ Rgba resolve_rows(const float4* __restrict__ p, size_t pitch) {
+    if constexpr (N == 1) {
+        return resolve_row<KX>(p);
+    } else {
+        const Rgba top = resolve_rows<KX, N / 2>(p, pitch);
+        const Rgba bottom = resolve_rows<KX, N / 2>(p + (size_t)(N / 2) * pitch, pitch);
+        return rgba_add(top, bottom);
+    }
+}
+
+// output pixel (ox, oy) of a plane out_w * KX pixels wide: the tree, then the scale
+template <int KX, int KY>
+__device__ __forceinline__ Rgba resolve_pixel(const float4* __restrict__ color, uint32_t out_w, uint32_t ox, uint32_t oy) {
+    static_assert((KX == 1 || KX == 2 || KX == 4 || KX == 8) && (KY == 1 || KY == 2 || KY == 4 || KY == 8), "factors divide the tile");
+    const size_t pitch = (size_t)out_w * KX;
+    const Rgba s = resolve_rows<KX, KY>(color + (size_t)oy * KY * pitch + (size_t)ox * KX, pitch);
+    constexpr float scale = 1.0f / (float)(KX * KY);
+    return Rgba{s.r * scale, s.g * scale, s.b * scale, s.a * scale};
+}
+
+// ---- the quantiser and the stores
+__device__ __forceinline__ uint32_t quantise8(float c) {
+    if (!(c > 0.0f)) return 0u;           // NaN, -0, +0, negatives, -Inf
+    if (c >= 1.0f) return 255u;           // +Inf too
+    return (uint32_t)rintf(c * 255.0f);
+}
+
+// a pixel as bytes R | G << 8 | B << 16 | A << 24, A the quantised alpha (ALPHA) or 255
+template <bool ALPHA>
+__device__ __forceinline__ uint32_t pack8(float r, float g, float b, float a) {
+    return quantise8(r) | quantise8(g) << 8 | quantise8(b) << 16 | (ALPHA ? quantise8(a) << 24 : 0xff000000u);
+}
+
+__device__ __forceinline__ void store_rgb32f(float* __restrict__ out, size_t pixel, float r, float g, float b) {
+    float* o = out + pixel * 3;
+    o[0] = r; o[1] = g; o[2] = b;
+}
+// (three byte stores: a pixel's bytes share a dword with its neighbours')
+__device__ __forceinline__ void store_rgb8(uint8_t* __restrict__ out, size_t pixel, uint32_t px) {
+    uint8_t* o = out + pixel * 3;
+    o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
+}
+__device__ __forceinline__ void store_rgbx8(uint8_t* __restrict__ out, size_t pixel, uint32_t px) {
+    *reinterpret_cast<uint32_t*>(out + pixel * 4) = px;
+}
+// texel (x, y) of a w-wide texture, row-major and (copy) where the bilinear filter reads it; w and h multiples of 4 then
+__device__ __forceinline__ void store_texel(uint32_t* __restrict__ rgba, uint32_t* __restrict__ blocked, bool copy, uint32_t w, uint32_t x, uint32_t y, uint32_t px) {
+    rgba[y * w + x] = px;
+    if (copy) blocked[bilinear_texel_offset<true>((int)w, (int)x, (int)y)] = px;
+}
+__device__ __forceinline__ void store_plane(float4* __restrict__ plane, size_t pixel, const Rgba c) {
+    plane[pixel] = make_float4(c.r, c.g, c.b, c.a);
+}
+
+// ---- the kernels.  color: the source plane, out_w * KX pixels wide and out_rows * KY rows high
+// rgb: out_rows x out_w x 3 floats
+template <int KX, int KY>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_resolve_rgb(const float4* __restrict__ color, float* __restrict__ rgb, int out_w, int out_rows) {
+    uint32_t ox, oy;
+    if (!deliver_pixel((uint32_t)out_w, (uint32_t)out_rows, ox, oy)) return;
+    const Rgba c = resolve_pixel<KX, KY>(color, (uint32_t)out_w, ox, oy);
+    store_rgb32f(rgb, deliver_index((uint32_t)out_w, ox, oy), c.r, c.g, c.b);
+}
+
+// out: out_rows * out_w pixels of BPP bytes
+template <int KX, int KY, int BPP>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_present8(const float4* __restrict__ color, uint8_t* __restrict__ out, uint32_t out_w, uint32_t out_rows) {
+    static_assert(BPP == 3 || BPP == 4, "RGB8 or RGBX8");
+    uint32_t ox, oy;
+    if (!deliver_pixel(out_w, out_rows, ox, oy)) return;
+    const Rgba c = resolve_pixel<KX, KY>(color, out_w, ox, oy);
+    const uint32_t px = pack8<false>(c.r, c.g, c.b, c.a);
+    if constexpr (BPP == 3) store_rgb8(out, deliver_index(out_w, ox, oy), px);
+    else store_rgbx8(out, deliver_index(out_w, ox, oy), px);
+}
+
+// rgba: h x w texels row-major; blocked (BLOCKED only): the same texels block-linear
+template <int KX, int KY, bool ALPHA, bool BLOCKED>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_frame_to_texture(const float4* __restrict__ color, uint32_t* __restrict__ rgba, uint32_t* __restrict__ blocked, uint32_t w, uint32_t h) {
+    uint32_t x, y;
+    if (!deliver_pixel(w, h, x, y)) return;
+    const Rgba c = resolve_pixel<KX, KY>(color, w, x, y);
+    store_texel(rgba, blocked, BLOCKED, w, x, y, pack8<ALPHA>(c.r, c.g, c.b, c.a));
+}
+
+// plane: out_rows x out_w float4
+template <int KX, int KY>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_resolve_rgba(const float4* __restrict__ color, float4* __restrict__ plane, uint32_t out_w, uint32_t out_rows) {
+    uint32_t ox, oy;
+    if (!deliver_pixel(out_w, out_rows, ox, oy)) return;
+    store_plane(plane, deliver_index(out_w, ox, oy), resolve_pixel<KX, KY>(color, out_w, ox, oy));
+}
+
+}  // namespace swr

@@ -85,12 +85,17 @@ struct UserProg {
     ~UserProg() { if (mod) (void)hipModuleUnload(mod); }
 };
 
-// A post-process program loaded on the context's device (swr_post_create): k_post<SWR_POST_RGB32F / _RGB8 / _RGBX8> and the two texel
-// formats of swr_texture_update_from_post, of its run-time compiled code object (swr_post.hip.h).  A destroyed program is parked (post_garbage) until the streams are idle: a present enqueued
-// with it may still be running.
+// The k_post instantiations of a post program (swr_post.hip.h), by the FORMAT each is instantiated with: the three present formats
+// and the two texel formats of swr_texture_update_from_post.  rtc_compile_post names them, swr_post_create loads them and the
+// launches select from them, all by this list.
+enum PostKernel { POST_RGB32F, POST_RGB8, POST_RGBX8, POST_TEXELS_OPAQUE, POST_TEXELS_KEEP, POST_KERNELS };
+constexpr int POST_KERNEL_FORMAT[POST_KERNELS] = { SWR_POST_RGB32F, SWR_POST_RGB8, SWR_POST_RGBX8, SWR_POST_TEXELS_OPAQUE, SWR_POST_TEXELS_KEEP };
+
+// A post-process program loaded on the context's device (swr_post_create): the k_post instantiations of its run-time compiled code
+// object.  A destroyed program is parked (post_garbage) until the streams are idle: a present enqueued with it may still be running.
 struct PostProg {
     hipModule_t mod = nullptr;
-    hipFunction_t fn[5] = {};                               // by PayloadFormat: RGB32F, RGB8, RGBX8; then the texel formats, OPAQUE and KEEP
+    hipFunction_t fn[POST_KERNELS] = {};                    // [PostKernel]
     PostConstants constants = {};                           // swr_post_set_constants: passed by value to each launch
     const swr_texture* tex[SWR_POST_TEXTURES] = {};         // swr_post_set_texture: read (with each texture's filter) at each launch
     ~PostProg() { if (mod) (void)hipModuleUnload(mod); }
@@ -261,6 +266,9 @@ template <class R = void, class F> R with_flag(bool b, F&& f) { return b ? f(std
 template <class R = void, class F> R with_factor(int k, F&& f) {            // a resolve factor: 1, 2, 4 or 8 (resolve_factor_ok)
     return k == 1 ? f(std::integral_constant<int, 1>{}) : k == 2 ? f(std::integral_constant<int, 2>{})
          : k == 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 8>{});
+}
+template <class R, class F> R with_factors(int kx, int ky, F&& f) {         // a delivery kernel's factor pair: f(x, y)
+    return with_factor<R>(kx, [&](auto x) -> R { return with_factor<R>(ky, [&](auto y) -> R { return f(x, y); }); });
 }
 
 // Frame-slot ring: a batch takes the next slot = {pinned staging block for its upload, completion event}.

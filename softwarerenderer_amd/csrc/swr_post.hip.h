@@ -7,8 +7,8 @@
 //     __device__ float4 swr_post(const swr_post_in& in, const swr_post_env& env);
 //   in.x, in.y    the output pixel, in window coordinates after the resolve
 //   in.color      the resolved pixel: R, G, B the floats swr_readback_rgb_resolved(kx, ky) delivers (the flatten's under (1, 1)), A the
-//                 frame's alpha through the same balanced pairwise tree and the same multiply by 1 / (kx ky) (resolve_rows4,
-//                 swr_rtt.hip.h)
+//                 frame's alpha through the same balanced pairwise tree and the same multiply by 1 / (kx ky) (resolve_pixel,
+//                 swr_deliver.hip.h)
 //   env.width, env.height   the resolved size;  env.kx, env.ky  the factors
 //   env.constants           64 floats, captured when the present call is made (swr_post_set_constants; zeros if never set)
 //   swr_post_fetch(env, x, y)   the resolved RGBA of output pixel (x, y), x clamped to [0, width - 1] and y to [0, height - 1]
@@ -19,24 +19,22 @@
 //                               when the present call was made (tests/post_texture_cases.py restates them)
 // What the result becomes:
 //   SWR_POST_RGB32F   x, y, z stored as they are (no clamp)
-//   SWR_POST_RGB8     quantise8 of x, y, z (swr_present8.hip.h), three bytes
+//   SWR_POST_RGB8     quantise8 of x, y, z (swr_deliver.hip.h), three bytes
 //   SWR_POST_RGBX8    the same and a fourth byte of 255, one dword
 //   w is ignored -- except by swr_texture_update_from_post (SWR_POST_TEXELS_KEEP below), where quantise8(w) is the texel's alpha.
 //
-//   k_resolve_rgba<KX, KY>  (product library) one thread per OUTPUT pixel on k_resolve_rgb's plain 2-D grid (64 x 4 threads per block, no
-//                           stride loop): resolve_rows4 times 1 / (KX KY) into a window-sized float4 plane of the context.  Not launched
-//                           under (1, 1), where the frame is that plane already.  The plane is deliberate: a program that fetches
-//                           neighbours would otherwise redo a tree of up to 64 samples per tap.
-//   k_post<FORMAT>          (run-time compiled with the user's text, SWR_RTC_POST; five instantiations per program) the same grid: the
-//                           thread loads its pixel of the plane, calls the inlined swr_post and stores as k_resolve_rgb / k_present8 store.
-//                           The constants and the texture slots are a by-value kernel argument: no device buffer outlives the call.
-//                           SWR_POST_TEXELS_OPAQUE / _KEEP (swr_texture_update_from_post; not present formats): the dword RGBX8 stores,
-//                           row-major into `out`, its alpha 255 or quantise8(w) -- and, where the argument carries a block-linear
-//                           copy, the same dword at bilinear_texel_offset<true> as k_frame_to_texture stores it (swr_rtt.hip.h).
+//   k_post<FORMAT>  (run-time compiled with the user's text, SWR_RTC_POST; five instantiations per program) one thread per OUTPUT pixel on
+//                   the delivery kernels' grid (deliver_pixel, swr_deliver.hip.h): the thread loads its pixel of the resolved plane
+//                   (k_resolve_rgba's; the frame itself under (1, 1)), calls the inlined swr_post and stores with the stores of
+//                   k_resolve_rgb / k_present8.  The constants and the texture slots are a by-value kernel argument: no device buffer
+//                   outlives the call.
+//                   SWR_POST_TEXELS_OPAQUE / _KEEP (swr_texture_update_from_post; not present formats): k_frame_to_texture's store,
+//                   the dword row-major into `out`, its alpha 255 or quantise8(w) -- and, where the argument carries a block-linear
+//                   copy, the same dword at bilinear_texel_offset<true>.
 // No LDS, no scratch, no inline assembly.  A frame is at most 65535 x 65535 (swr_resize), so pixel indices fit 32 bits; offsets are size_t.
 #pragma once
 #include "swr_user_math.hip.h"
-#include "swr_rtt.hip.h"
+#include "swr_deliver.hip.h"
 
 #define SWR_POST_CONSTANTS 64
 // k_post's internal formats behind swr_texture_update_from_post: RGBA8 texels, alpha 255 or the result's w
@@ -52,20 +50,6 @@ struct PostConstants {
     TextureSlot tex[SWR_POST_TEXTURES];
     uint32_t* blocked;
 };
-
-// color: the frame, out_w * KX pixels wide and out_rows * KY rows high; plane: out_rows x out_w float4
-template <int KX, int KY>
-__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
-void k_resolve_rgba(const float4* __restrict__ color, float4* __restrict__ plane, uint32_t out_w, uint32_t out_rows) {
-    static_assert((KX == 1 || KX == 2 || KX == 4 || KX == 8) && (KY == 1 || KY == 2 || KY == 4 || KY == 8), "factors divide the tile");
-    const uint32_t ox = blockIdx.x * SWR_RESOLVE_BLOCK_X + threadIdx.x;
-    const uint32_t oy = blockIdx.y * SWR_RESOLVE_BLOCK_Y + threadIdx.y;
-    if (ox >= out_w || oy >= out_rows) return;
-    const size_t pitch = (size_t)out_w * KX;
-    const Rgba s = resolve_rows4<KX, KY>(color + (size_t)oy * KY * pitch + (size_t)ox * KX, pitch);
-    constexpr float scale = 1.0f / (float)(KX * KY);
-    plane[(size_t)oy * out_w + ox] = make_float4(s.r * scale, s.g * scale, s.b * scale, s.a * scale);
-}
 
 }  // namespace swr
 
@@ -128,31 +112,16 @@ void k_post(const float4* __restrict__ plane, const float* __restrict__ depth, v
             int kx, int ky, const PostConstants constants) {
     static_assert(FORMAT == SWR_POST_RGB32F || FORMAT == SWR_POST_RGB8 || FORMAT == SWR_POST_RGBX8 || FORMAT == SWR_POST_TEXELS_OPAQUE ||
                   FORMAT == SWR_POST_TEXELS_KEEP, "a present format or a texel format");
-    const uint32_t ox = blockIdx.x * SWR_RESOLVE_BLOCK_X + threadIdx.x;
-    const uint32_t oy = blockIdx.y * SWR_RESOLVE_BLOCK_Y + threadIdx.y;
-    if (ox >= out_w || oy >= out_rows) return;
+    uint32_t ox, oy;
+    if (!deliver_pixel(out_w, out_rows, ox, oy)) return;
     const swr_post_env env = { (int)out_w, (int)out_rows, kx, ky, constants.v, plane, depth, constants.tex };
-    const size_t pixel = (size_t)oy * out_w + ox;
+    const size_t pixel = deliver_index(out_w, ox, oy);
     const swr_post_in in = { (int)ox, (int)oy, plane[pixel] };
     const float4 c = swr_post(in, env);
-    if constexpr (FORMAT == SWR_POST_RGB32F) {
-        float* o = static_cast<float*>(out) + pixel * 3;
-        o[0] = c.x; o[1] = c.y; o[2] = c.z;
-    } else if constexpr (FORMAT == SWR_POST_TEXELS_OPAQUE || FORMAT == SWR_POST_TEXELS_KEEP) {
-        // (a texture has fewer than 2^30 texels: 32-bit texel indices, as in k_frame_to_texture)
-        const uint32_t a = FORMAT == SWR_POST_TEXELS_KEEP ? quantise8(c.w) << 24 : 0xff000000u;
-        const uint32_t px = quantise8(c.x) | quantise8(c.y) << 8 | quantise8(c.z) << 16 | a;
-        static_cast<uint32_t*>(out)[oy * out_w + ox] = px;
-        if (constants.blocked) constants.blocked[bilinear_texel_offset<true>((int)out_w, (int)ox, (int)oy)] = px;
-    } else {
-        const uint32_t px = quantise8(c.x) | quantise8(c.y) << 8 | quantise8(c.z) << 16 | 0xff000000u;
-        uint8_t* o = static_cast<uint8_t*>(out) + pixel * FORMAT;
-        if constexpr (FORMAT == SWR_POST_RGB8) {
-            o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
-        } else {
-            *reinterpret_cast<uint32_t*>(o) = px;
-        }
-    }
+    if constexpr (FORMAT == SWR_POST_RGB32F) store_rgb32f(static_cast<float*>(out), pixel, c.x, c.y, c.z);
+    else if constexpr (FORMAT == SWR_POST_RGB8) store_rgb8(static_cast<uint8_t*>(out), pixel, pack8<false>(c.x, c.y, c.z, c.w));
+    else if constexpr (FORMAT == SWR_POST_RGBX8) store_rgbx8(static_cast<uint8_t*>(out), pixel, pack8<false>(c.x, c.y, c.z, c.w));
+    else store_texel(static_cast<uint32_t*>(out), constants.blocked, constants.blocked != nullptr, out_w, ox, oy, pack8<FORMAT == SWR_POST_TEXELS_KEEP>(c.x, c.y, c.z, c.w));
 }
 
 }  // namespace swr

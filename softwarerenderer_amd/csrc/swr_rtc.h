@@ -45,15 +45,15 @@ const RtcLib& rtc_lib() {
 }
 
 // code object + mangled names, in the order of the unit's name expressions: k_raster_c<SWR_PROG_CUSTOM> [EARLYOUT], then (vertex half
-// only) k_vertex_user and k_setup; for a post program k_post<SWR_POST_RGB32F / _RGB8 / _RGBX8 / SWR_POST_TEXELS_OPAQUE / _KEEP>
-struct RtcCode { std::vector<char> code; std::string names[5]; bool has_vertex = false; };
+// only) k_vertex_user and k_setup; for a post program its k_post instantiations by PostKernel
+struct RtcCode { std::vector<char> code; std::vector<std::string> names; bool has_vertex = false; };
 
 // one translation unit for the run-time compiler: what rtc_compile and rtc_compile_post hand to rtc_build
 struct RtcUnit {
     std::string key;                     // the in-process cache's key
     std::string src;                     // prelude include, the user's text under its own file name, the kernels
     std::vector<std::string> defines;    // on top of the Makefile's switches and this build's numerics model
-    std::vector<std::string> exprs;      // the kernels to look up, at most 5
+    std::vector<std::string> exprs;      // the kernels to look up
     bool has_vertex = false;
 };
 
@@ -106,6 +106,7 @@ int rtc_build(const RtcUnit& u, std::shared_ptr<const RtcCode>& out, std::string
     auto code = std::make_shared<RtcCode>();
     bool ok = cr == HIPRTC_SUCCESS;
     code->has_vertex = u.has_vertex;
+    code->names.resize(n_expr);
     for (int k = 0; ok && k < n_expr; ++k) {
         const char* mangled = nullptr;
         ok = R.lowered(prog, u.exprs[k].c_str(), &mangled) == HIPRTC_SUCCESS && mangled;
@@ -177,8 +178,7 @@ int rtc_compile_post(const char* user_src, std::shared_ptr<const RtcCode>& out, 
     u.key = std::string("\2") + user_src;           // ('\2' cannot open a fragment or vertex text)
     u.src = std::string("#include \"swr_post.hip.h\"\n#line 1 \"post.hip\"\n") + user_src + "\n";
     u.defines = { "-DSWR_RTC_POST=1" };
-    u.exprs = { "swr::k_post<SWR_POST_RGB32F>", "swr::k_post<SWR_POST_RGB8>", "swr::k_post<SWR_POST_RGBX8>",
-                "swr::k_post<SWR_POST_TEXELS_OPAQUE>", "swr::k_post<SWR_POST_TEXELS_KEEP>" };
+    for (const int format : POST_KERNEL_FORMAT) u.exprs.push_back("swr::k_post<" + std::to_string(format) + ">");
     return rtc_build(u, out, log);
 }
 }  // namespace

@@ -1,4 +1,4 @@
-"""The 8-bit present's quantiser restated in numpy float32 (include/swr.h, csrc/swr_present8.hip.h), the planes the present8 tests run
+"""The 8-bit present's quantiser restated in numpy float32 (include/swr.h, csrc/swr_deliver.hip.h), the planes the present8 tests run
 it on, and the mutants its known answers must reject.  Not a test module: tests/test_present8_host.py and tests/test_gpu_present8.py
 import it.
 

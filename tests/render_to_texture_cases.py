@@ -1,4 +1,4 @@
-"""Render to texture restated in numpy (include/swr.h, csrc/swr_rtt.hip.h), the planes and shapes its tests run
+"""Render to texture restated in numpy (include/swr.h, csrc/swr_deliver.hip.h), the planes and shapes its tests run
 on.  Not a test module: tests/test_render_to_texture_host.py and tests/test_gpu_render_to_texture.py import it.
 
 Texel (x, y) of a w x h texture updated from a frame of w * kx by h * ky pixels: R, G, B are the bytes of the 8-bit present at 4 bytes

@@ -1,4 +1,4 @@
-"""The supersampled present's arithmetic restated in numpy float32 (include/swr.h, csrc/swr_resolve.hip.h), and the planes the
+"""The supersampled present's arithmetic restated in numpy float32 (include/swr.h, csrc/swr_deliver.hip.h), and the planes the
 resolve tests run it on.  Not a test module: tests/test_resolve_host.py and tests/test_gpu_resolve.py import it.
 
 Per output pixel and channel R, G, B: the kx samples of each source row summed as a balanced pairwise tree left to right, the ky row

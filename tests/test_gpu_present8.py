@@ -1,4 +1,4 @@
-"""8-bit present on the GPU (include/swr.h, csrc/swr_present8.hip.h): k_present8 against the numpy restatement of
+"""8-bit present on the GPU (include/swr.h, csrc/swr_deliver.hip.h): k_present8 against the numpy restatement of
 tests/present8_cases.py, byte for byte and without a tolerance, through every entry point: swr_readback_rgb8,
 swr_resolve_rgb8_device[_async], swr_present_rgb8_async, swr_present8_size."""
 import ctypes as C

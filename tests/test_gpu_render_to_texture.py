@@ -1,4 +1,4 @@
-"""Render to texture on the GPU (include/swr.h, csrc/swr_rtt.hip.h): k_frame_to_texture against the numpy
+"""Render to texture on the GPU (include/swr.h, csrc/swr_deliver.hip.h): k_frame_to_texture against the numpy
 restatement of tests/render_to_texture_cases.py byte for byte, its block-linear copy through the bilinear filter, and the ordering of
 swr_texture_update_from_frame against the draws around it -- within one context and between two -- without a host synchronisation."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Supersampled present on the GPU (include/swr.h, csrc/swr_resolve.hip.h): k_resolve_rgb against the numpy
+"""Supersampled present on the GPU (include/swr.h, csrc/swr_deliver.hip.h): k_resolve_rgb against the numpy
 restatement of tests/resolve_cases.py, word for word on uint32 views (NaN positions compared as NaN), through every entry point:
 swr_readback_rgb_resolved, swr_resolve_rgb_device[_async], swr_present_rgb_resolved_async, swr_resolved_size."""
 import ctypes as C

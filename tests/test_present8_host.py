@@ -1,5 +1,5 @@
 """8-bit present, host side (no GPU): the numpy restatement of the quantiser gives the definition's known answers (include/swr.h,
-csrc/swr_present8.hip.h), each plausible wrong quantiser misses exactly the known answer named for it, the bytes round-trip through
+csrc/swr_deliver.hip.h), each plausible wrong quantiser misses exactly the known answer named for it, the bytes round-trip through
 k / 255, the generator delivers what the GPU test relies on, and the Python wrappers' shapes and argument checks."""
 import types
 

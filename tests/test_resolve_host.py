@@ -1,5 +1,5 @@
 """Supersampled present, host side (no GPU): the numpy restatement of the resolve arithmetic has the tree order and the stage order
-the definition fixes (include/swr.h, csrc/swr_resolve.hip.h) -- known answers that the plausible wrong orders miss --, the payload's
+the definition fixes (include/swr.h, csrc/swr_deliver.hip.h) -- known answers that the plausible wrong orders miss --, the payload's
 size arithmetic of MainWindow.ResolvedSize, and the new entry points' names."""
 import types
 

@@ -3,13 +3,13 @@
   (a) kernel time, device events around --launches launches after --warmup: k_resolve_rgb (2, 2) at 3840x2160, (4, 4) and (1, 1) at
       4096^2, and k_flatten_rgb on the same planes in the same call, alternated three times; algorithmic bytes (source x 16 +
       output x 12), GB/s, share of the 6.29 TB/s measured copy peak, the A/A spread of the flatten.  --ab-lib FILE times another
-      in-tree build of the library (the other thread mapping: make EXTRA=-DSWR_RESOLVE_LANE_PER_SOURCE) in the same process.
+      in-tree build of the library (make EXTRA=...) in the same process.
   (b) frame loop with pinned buffers, --frames frames after --frame-warmup, alternated three times: render 3840x2160 and present
       resolved (2, 2); render 3840x2160 and PresentAsync; render 1920x1080 and PresentAsync.
   (c) --bench-json FILE: a `bench.py --gpus 1 --steps 50 --warmup 5` line recorded beside it, with the parent's recorded figure.
 With --present8 the same two measurements are made for the 8-bit present (default profiles/r13_present8.json):
   (a) k_present8 at (1, 1) and (2, 2), 3 and 4 bytes per pixel, at 3840x2160 and 4096^2, beside k_flatten_rgb and k_resolve_rgb of
-      the same factors on the same plane; --ab-lib times the other thread mapping (make EXTRA=-DSWR_PRESENT8_FOUR_PER_THREAD).
+      the same factors on the same plane; --ab-lib as above.
   (b) render 1920x1080 and Present8Async (1, 1), render 3840x2160 and Present8Async (2, 2), 3 bytes per pixel, each beside the same
       loop with today's float present (PresentAsync, PresentResolvedAsync (2, 2)) in the same process.
 usage: python tools/resolve_rate.py [--present8] [--out FILE] [--ab-lib libNAME.so] [--bench-json FILE]"""
