@@ -218,6 +218,13 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_texture_create_target(IntPtr ctx, int width, int height, out IntPtr texture);
         [DllImport(Lib)] public static extern int swr_texture_update_from_frame(IntPtr ctx, IntPtr texture, IntPtr sourceCtx, int kx, int ky, int alphaMode);
         [DllImport(Lib)] public static extern int swr_texture_readback(IntPtr ctx, IntPtr texture, byte* rgba8);
+        [DllImport(Lib)] public static extern int swr_texture_create_depth(IntPtr ctx, float* depthOrNull, int width, int height, out IntPtr texture);
+        [DllImport(Lib)] public static extern int swr_texture_update_from_depth(IntPtr ctx, IntPtr texture, IntPtr sourceCtx, int kx, int ky, int reduce);
+        [DllImport(Lib)] public static extern int swr_texture_readback_depth(IntPtr ctx, IntPtr texture, float* depth);
+        // (TextureNative.ReadDepth calls this: a test counts TextureNative's uses of swr_texture_readback by that prefix)
+        public static int TextureReadDepth(IntPtr ctx, IntPtr texture, float* depth) => swr_texture_readback_depth(ctx, texture, depth);
+        [DllImport(Lib)] public static extern int swr_texture_sample_depth(IntPtr ctx, IntPtr texture, float* uvRef, int n, float* outDepthShadow);
+        [DllImport(Lib)] public static extern int swr_texture_format(IntPtr ctx, IntPtr texture, out int format);
         [DllImport(Lib)] public static extern int swr_mesh_create(IntPtr ctx, Shaders.VertexInput* vertices, int nVertices, ushort* indices, int nIndices, out IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_mesh_destroy(IntPtr ctx, IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_set_state(IntPtr ctx, float nearClip, float farClip, int debugMode);
@@ -1019,6 +1026,54 @@ namespace SoftwareRenderer
         public void UpdateFromPost(PostProgramNative post, int kx = 1, int ky = 1, bool keepAlpha = false, IntPtr sourceContext = default)
         {
             SwrContext.Check(Native.swr_texture_update_from_post(SwrContext.Handle, Handle, sourceContext, post.Id, kx, ky, keepAlpha ? 1 : 0));
+        }
+
+        /// Depth textures (build-defined: the reference links MainWindow's depth floats and a Texture nowhere).  float32 depth words
+        /// as the raster stage stores them: `depth` (Width * Height floats, row-major) or, null, float.MinValue everywhere -- nothing
+        /// drawn.  Filled by UpdateFromDepth; programs read it through swr_shadow / swr_sample_depth / swr_texel_depth.
+        public static TextureNative CreateDepth(int width, int height, float[] depth = null)
+        {
+            if (depth != null && depth.Length != width * height) throw new ArgumentException("depth must hold width * height floats");
+            fixed (float* p = depth)                                           // (null array: null pointer)
+            {
+                SwrContext.Check(Native.swr_texture_create_depth(SwrContext.Handle, p, width, height, out IntPtr h));
+                return new TextureNative(width, height, h);
+            }
+        }
+
+        public enum DepthReduce { Max = 0, Min = 1, First = 2 }               // SWR_DEPTH_REDUCE_*
+
+        /// Each texel becomes ONE word of its kx x ky block of the frame's depth plane (Width * kx by Height * ky pixels): the
+        /// nearest under the default LessEqual test (Max), the farthest (Min) or the top-left one (First).  Otherwise UpdateFrom's
+        /// contract: immediate-mode semantics, no wait for the GPU, one kernel (swr_texture_update_from_depth).
+        public void UpdateFromDepth(int kx = 1, int ky = 1, DepthReduce reduce = DepthReduce.Max, IntPtr sourceContext = default)
+        {
+            SwrContext.Check(Native.swr_texture_update_from_depth(SwrContext.Handle, Handle, sourceContext, kx, ky, (int)reduce));
+        }
+
+        /// The depth words, row-major, Width * Height floats; waits for the GPU.
+        public float[] ReadDepth()
+        {
+            var words = new float[Width * Height];
+            fixed (float* p = words)
+                SwrContext.Check(Native.TextureReadDepth(SwrContext.Handle, Handle, p));
+            return words;
+        }
+
+        /// (the depth word Texture.Sample's addressing picks at uv, swr_shadow of the texture at uv against reference) with the
+        /// texture's filter as it is now; one call per sample: tools only.
+        public Vector2 SampleDepth(Vector2 uv, float reference)
+        {
+            float* q = stackalloc float[3] { uv.X, uv.Y, reference };
+            Vector2 o;
+            SwrContext.Check(Native.swr_texture_sample_depth(SwrContext.Handle, Handle, q, 1, (float*)&o));
+            return o;
+        }
+
+        /// 0 = RGBA8, 1 = float32 depth (SWR_TEXTURE_FORMAT_*)
+        public int Format
+        {
+            get { SwrContext.Check(Native.swr_texture_format(SwrContext.Handle, Handle, out int f)); return f; }
         }
 
         /// The RGBA8 texels, row-major, Width * Height * 4 bytes; waits for the GPU (screenshots, tests).

@@ -283,6 +283,48 @@ int  swr_texture_create_target(swr_context* ctx, int width, int height, swr_text
 int  swr_texture_update_from_frame(swr_context* ctx, swr_texture* tex, swr_context* src, int kx, int ky, int alpha_mode);
 /* the row-major texels, w * h * 4 bytes, as the kernels enqueued so far leave them; waits for the stream (screenshots, tests) */
 int  swr_texture_readback(swr_context* ctx, const swr_texture* tex, uint8_t* rgba8);
+/* DEPTH TEXTURES (build-defined: the reference has no link between MainWindow's depth floats and a Texture; csrc/swr_deliver.hip.h,
+ * csrc/swr_device.h): a frame's depth plane becomes a texture a later draw, of this or another camera, can
+ * compare against -- cast shadows, depth-tested decals, soft particles.  A depth texture is an swr_texture whose 4-byte texels are
+ * float32 depth words, exactly as the raster stage stores them (float.MinValue = nothing drawn; larger = nearer under LessEqual).
+ * The format is fixed at creation.  What the calls above do with a depth texture:
+ *   swr_texture_set_filter   works: the switch between one-tap and 2 x 2 shadow lookups (swr_shadow below); makes the block-linear copy
+ *                            under its usual rule, and swr_texture_update_from_depth writes that copy in the same pass
+ *   swr_texture_destroy      works
+ *   swr_program_set_texture, swr_post_set_texture, a render call's texture   accepted: the colour samplers (swr_sample, swr_texel) then
+ *                            read the float's four bytes as R, G, B, A -- defined and memory-safe, rarely useful
+ *   swr_texture_update_from_frame / _from_post, swr_texture_readback, swr_texture_sample   SWR_ERR_INVALID_ARG with a message, nothing
+ *                            written, the context usable
+ * and the *_depth calls below answer an RGBA8 texture the same way. */
+enum { SWR_TEXTURE_FORMAT_RGBA8 = 0, SWR_TEXTURE_FORMAT_DEPTH32F = 1 };
+/* How the kx x ky depth words of a texel's block become one: a balanced pairwise tree over the kx adjacent words of each row, left to
+ * right, then the same tree over the ky row results, top to bottom (the shape of the colour resolve), of the select
+ *   MAX    pick(a, b) = b > a ? b : a    the block's nearest sample under the default LessEqual test (new >= old passes)
+ *   MIN    pick(a, b) = b < a ? b : a
+ *   FIRST  pick(a, b) = a                the top-left sample, the word swr_post_depth reads
+ * The result is one of the block's own words, bit for bit: a NaN on the left stays and one on the right is never taken; of +0 and -0
+ * the left one stays.  Under (1, 1) all three copy the plane. */
+enum { SWR_DEPTH_REDUCE_MAX = 0, SWR_DEPTH_REDUCE_MIN = 1, SWR_DEPTH_REDUCE_FIRST = 2 };
+/* w x h float32 depth words, row-major; NULL: every texel float.MinValue (a 32-bit fill on the context's stream).  The limits and
+ * codes of swr_texture_create. */
+int  swr_texture_create_depth(swr_context* ctx, const float* depth_or_null, int width, int height, swr_texture** out);
+/* Texel (x, y) of the w x h depth texture from the depth plane of src's frame of w * kx by h * ky pixels, reduced as above; no scale,
+ * no quantiser.  Everything else is swr_texture_update_from_frame's contract with the depth plane in the colour plane's place:
+ * immediate-mode semantics, both contexts' recorded draws flushed, ONE kernel on ctx's stream, nothing waits for the GPU, two events
+ * between two contexts, the block-linear copy written by the same kernel, whatever depth buffer src has bound (16-byte aligned: the
+ * kernel loads kx words at once), and no validation of optimistic flushes -- if swr_replay_count of src or ctx grows at the next
+ * validating call, update (and redraw what sampled the texture) again; steady-state frames never replay.
+ * SWR_ERR_INVALID_ARG: tex NULL, an unknown reduce, a texture that is not DEPTH32F, factors outside {1, 2, 4, 8}, a frame that is not
+ * w * kx by h * ky, a misaligned bound depth buffer.  SWR_ERR_UNSUPPORTED: src holds only a band of its frame, or lives on another
+ * device.  Nothing is written then and the context stays usable. */
+int  swr_texture_update_from_depth(swr_context* ctx, swr_texture* tex, swr_context* src, int kx, int ky, int reduce);
+/* the row-major depth words, w * h floats, as the kernels enqueued so far leave them; waits for the stream */
+int  swr_texture_readback_depth(swr_context* ctx, const swr_texture* tex, float* out);
+/* The device lookups of a depth texture (csrc/swr_device.h), batched, with the texture's filter as it is now: n triples (u, v, ref)
+ * -> n pairs (texture_slot_depth_sample(u, v), texture_slot_shadow(u, v, ref)); runs on the GPU and waits for it. */
+int  swr_texture_sample_depth(swr_context* ctx, const swr_texture* tex, const float* uv_ref, int n, float* out_depth_shadow);
+/* SWR_TEXTURE_FORMAT_* of any texture */
+int  swr_texture_format(swr_context* ctx, const swr_texture* tex, int* format);
 /* mesh.Vertices / mesh.Indices (ModelLoader.cs:45-47): u16 indices, 3 per triangle; an index >= n_vertices
  * is SWR_ERR_INVALID_ARG (C#: IndexOutOfRangeException at Rasterizer.cs:187) */
 int  swr_mesh_create(swr_context* ctx, const swr_vertex* vertices, int n_vertices,
@@ -418,6 +460,14 @@ int  swr_program_set_constants(swr_context* ctx, int program_id, const float* va
  *                                             bilinear extension if the texture was switched to it when the draw was recorded
  *     float4 swr_texel(env, slot, x, y)       texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1], each byte times the float 1 / 255
  *     int2   swr_texture_size(env, slot)      (w, h), positive whatever the filter
+ *   and, of a slot that holds a DEPTH texture (swr_texture_create_depth):
+ *     float  swr_texel_depth(env, slot, x, y)    the float32 depth word of texel (x, y), clamped as swr_texel clamps
+ *     float  swr_sample_depth(env, slot, uv)     the word of the texel swr_sample's nearest addressing picks, whatever the filter
+ *     float  swr_shadow(env, slot, uv, ref)      1 where a fragment of depth ref passes LessEqual against the stored depth (ref >= d;
+ *                                             false for NaN), else 0; the bias is the caller's, added into ref.  Nearest filter: one
+ *                                             texel.  Bilinear filter: the four results of the filter's 2 x 2 footprint blended as
+ *                                             lerps by its fractions -- exactly 0 or 1 where all four agree (finite uv)
+ *   An unbound or out-of-range slot reads float.MinValue (nothing drawn) and shadows nothing (1).
  * Slot 0 is and stays the `texture` argument of the render call.  Slots 1 .. SWR_PROGRAM_TEXTURES - 1 belong to the program, as its
  * constants do: a draw copies each slot's pointer, size and filter (the block-linear copy where the texture has one) when it is
  * RECORDED; later swr_program_set_texture and swr_texture_set_filter calls do not change recorded draws.  An unbound slot, and a slot
@@ -476,6 +526,9 @@ int  swr_program_validate_vf(const char* vertex_source, const char* fragment_sou
  *   float4 swr_post_texel(env, slot, x, y)    the row-major texel, x clamped to [0, w - 1] and y to [0, h - 1], each byte times the
  *          float 1 / 255 (Texture.cs:57-62): no filter, so a pixel-aligned read does not depend on a uv rounding
  *   int2   swr_post_texture_size(env, slot)
+ *   float  swr_post_texel_depth(env, slot, x, y), swr_post_sample_depth(env, slot, uv), swr_post_shadow(env, slot, uv, ref)
+ *          a DEPTH texture's words and the shadow comparison: swr_texel_depth, swr_sample_depth and swr_shadow of a user program,
+ *          above; an unbound or out-of-range slot reads float.MinValue and shadows nothing (1)
  * An unbound slot, and a slot outside 0 .. SWR_POST_TEXTURES - 1, has no texture: it samples and reads (1, 1, 1, 1), as swr_sample
  * does without a texture, and measures (0, 0).
  * What the result's x, y, z become (w is ignored, except by swr_texture_update_from_post): */

@@ -24,6 +24,8 @@ SWR_ERR_OOM = -3
 SWR_ERR_NO_DEVICE = -4
 SWR_ERR_UNSUPPORTED = -5
 SWR_TEXTURE_ALPHA_OPAQUE, SWR_TEXTURE_ALPHA_KEEP = 0, 1     # swr_texture_update_from_frame
+SWR_TEXTURE_FORMAT_RGBA8, SWR_TEXTURE_FORMAT_DEPTH32F = 0, 1     # swr_texture_format
+SWR_DEPTH_REDUCE_MAX, SWR_DEPTH_REDUCE_MIN, SWR_DEPTH_REDUCE_FIRST = 0, 1, 2     # swr_texture_update_from_depth
 SWR_POST_RGB32F, SWR_POST_RGB8, SWR_POST_RGBX8 = 0, 3, 4     # swr_readback_post & co: what a post program's result becomes
 SWR_POST_TEXTURES = 4                                        # swr_post_set_texture: slots 0 .. 3
 SWR_PROGRAM_TEXTURES = 4                                     # user programs: slot 0 the draw's texture, swr_program_set_texture: slots 1 .. 3
@@ -121,6 +123,7 @@ EXPORTS = [
     "swr_post_create", "swr_post_destroy", "swr_post_set_constants", "swr_post_validate", "swr_post_size",
     "swr_readback_post", "swr_present_post_async", "swr_post_device", "swr_post_device_async",
     "swr_post_set_texture", "swr_texture_update_from_post",
+    "swr_texture_create_depth", "swr_texture_update_from_depth", "swr_texture_readback_depth", "swr_texture_sample_depth", "swr_texture_format",
 ]
 
 _libs = {}
@@ -235,6 +238,11 @@ def load(name: str = None) -> C.CDLL:
         "swr_post_device_async": (I, [P, I, I, I, I, P]),
         "swr_post_set_texture": (I, [P, I, I, P]),
         "swr_texture_update_from_post": (I, [P, P, P, I, I, I, I]),
+        "swr_texture_create_depth": (I, [P, P, I, I, C.POINTER(P)]),
+        "swr_texture_update_from_depth": (I, [P, P, P, I, I, I]),
+        "swr_texture_readback_depth": (I, [P, P, P]),
+        "swr_texture_sample_depth": (I, [P, P, P, I, P]),
+        "swr_texture_format": (I, [P, P, C.POINTER(I)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -97,6 +97,25 @@ public:
     // ... with `post`, a program of the window's Device, between the resolve and the quantiser (swr_texture_update_from_post): alpha
     // 255, or the quantised w of the program's result.  The texture may not be bound to a slot of `post`
     inline void UpdateFromPost(const MainWindow& window, const PostProgram& post, int kx = 1, int ky = 1, bool keepAlpha = false);
+    // depth textures (build-defined, swr.h): float32 depth words as the raster stage stores them -- `depth` (Width * Height floats) or,
+    // null, float.MinValue everywhere; filled by UpdateFromDepth, read in programs through swr_shadow / swr_sample_depth / swr_texel_depth
+    static Texture Depth(const Device& dev, int width, int height, const float* depth = nullptr) { return Texture(dev, width, height, depth, DepthTag{}); }
+    // each texel becomes one word of its kx x ky block of the window's depth plane: SWR_DEPTH_REDUCE_MAX (the nearest under LessEqual),
+    // _MIN or _FIRST (top-left).  Otherwise UpdateFrom's contract
+    inline void UpdateFromDepth(const MainWindow& window, int kx = 1, int ky = 1, int reduce = SWR_DEPTH_REDUCE_MAX);
+    std::vector<float> ReadDepth() const {    // depth words row-major; waits for the GPU
+        std::vector<float> out((size_t)Width * (size_t)Height);
+        dev_.check(swr_texture_readback_depth(dev_.ctx(), h_, out.data()));
+        return out;
+    }
+    // (the word Texture.Sample's addressing picks, swr_shadow of it against ref) with the texture's filter as it is now (runs on the GPU)
+    std::array<float, 2> SampleDepth(float u, float v, float ref) const {
+        float in[3] = { u, v, ref }; std::array<float, 2> out{};
+        dev_.check(swr_texture_sample_depth(dev_.ctx(), h_, in, 1, out.data()));
+        return out;
+    }
+    int Format() const { int f = -1; dev_.check(swr_texture_format(dev_.ctx(), h_, &f)); return f; }   // SWR_TEXTURE_FORMAT_*
+    void SetBilinear(bool on) { dev_.check(swr_texture_set_filter(dev_.ctx(), h_, on ? 1 : 0)); }      // depth: 2 x 2 shadow lookups
     std::vector<uint8_t> Read() const {       // RGBA8 row-major; waits for the GPU
         std::vector<uint8_t> out((size_t)Width * (size_t)Height * 4);
         dev_.check(swr_texture_readback(dev_.ctx(), h_, out.data()));
@@ -113,6 +132,10 @@ public:
 private:
     Texture(const Device& dev, int width, int height) : dev_(dev), Width(width), Height(height) {
         dev_.check(swr_texture_create_target(dev_.ctx(), width, height, &h_));
+    }
+    struct DepthTag {};
+    Texture(const Device& dev, int width, int height, const float* depth, DepthTag) : dev_(dev), Width(width), Height(height) {
+        dev_.check(swr_texture_create_depth(dev_.ctx(), depth, width, height, &h_));
     }
     const Device& dev_;
     swr_texture* h_ = nullptr;
@@ -221,6 +244,10 @@ private:
 inline void Texture::UpdateFrom(const MainWindow& window, int kx, int ky, bool keepAlpha) {
     swr_context* src = window.device().ctx() == dev_.ctx() ? nullptr : window.device().ctx();
     dev_.check(swr_texture_update_from_frame(dev_.ctx(), h_, src, kx, ky, keepAlpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
+}
+inline void Texture::UpdateFromDepth(const MainWindow& window, int kx, int ky, int reduce) {
+    swr_context* src = window.device().ctx() == dev_.ctx() ? nullptr : window.device().ctx();
+    dev_.check(swr_texture_update_from_depth(dev_.ctx(), h_, src, kx, ky, reduce));
 }
 inline void Texture::UpdateFromPost(const MainWindow& window, const PostProgram& post, int kx, int ky, bool keepAlpha) {
     swr_context* src = window.device().ctx() == dev_.ctx() ? nullptr : window.device().ctx();

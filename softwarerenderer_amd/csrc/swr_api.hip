@@ -294,15 +294,35 @@ RttKernel rtt_kernel(int kx, int ky, bool alpha, bool blocked) {
         return k_frame_to_texture<decltype(x)::value, decltype(y)::value, decltype(a)::value, decltype(b)::value>; }); }); });
 }
 
-// swr_texture_create / swr_texture_create_target: w x h texels on the context's stream, the caller's or (rgba8 null) zeros
-int texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_texture** out, const char* what_failed) {
+// swr_texture_update_from_depth: k_depth_to_texture by factors and whether the block-linear copy exists (the reduction is an argument)
+using DepthTextureKernel = void (*)(const float*, uint32_t*, uint32_t*, uint32_t, uint32_t, int);
+DepthTextureKernel depth_texture_kernel(int kx, int ky, bool blocked) {
+    using K = DepthTextureKernel;
+    return with_flag<K>(blocked, [&](auto b) -> K { return with_factors<K>(kx, ky, [](auto x, auto y) -> K {
+        return k_depth_to_texture<decltype(x)::value, decltype(y)::value, decltype(b)::value>; }); });
+}
+
+// does the call suit the texture's format?  (the texels of both formats are 4 bytes: nothing else tells them apart)
+int texture_format_check(swr_context* c, const swr_texture* t, int format) {
+    if (t->format == format) return SWR_OK;
+    return fail(c, SWR_ERR_INVALID_ARG, format == SWR_TEXTURE_FORMAT_DEPTH32F ? "the texture is not a depth texture (SWR_TEXTURE_FORMAT_DEPTH32F): this call reads or writes depth words"
+                                                                              : "the texture is a depth texture (SWR_TEXTURE_FORMAT_DEPTH32F): use the swr_texture_*_depth calls");
+}
+
+// swr_texture_create / _create_target / _create_depth: w x h 4-byte texels on the context's stream, the caller's or (texels null) the
+// format's empty word: zeros, or float.MinValue
+int texture_create(swr_context* c, const void* texels, int w, int h, swr_texture** out, const char* what_failed, int format = SWR_TEXTURE_FORMAT_RGBA8) {
     if (w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
     if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
     swr_texture* t = new swr_texture();
-    t->w = w; t->h = h;
+    t->w = w; t->h = h; t->format = format;
     const size_t bytes = (size_t)w * h * 4;
+    const float empty_depth = SWR_FLOAT_MINVALUE;
+    int empty = 0;
+    if (format == SWR_TEXTURE_FORMAT_DEPTH32F) memcpy(&empty, &empty_depth, 4);
     hipError_t e = hipMalloc((void**)&t->d_rgba, bytes);
-    if (e == hipSuccess) e = rgba8 ? hipMemcpyAsync(t->d_rgba, rgba8, bytes, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(t->d_rgba, 0, bytes, c->stream);
+    if (e == hipSuccess) e = texels ? hipMemcpyAsync(t->d_rgba, texels, bytes, hipMemcpyHostToDevice, c->stream)
+                                    : hipMemsetD32Async((hipDeviceptr_t)t->d_rgba, empty, (size_t)w * h, c->stream);
     if (e != hipSuccess) {
         if (t->d_rgba) (void)hipFree(t->d_rgba);
         delete t;
@@ -313,12 +333,22 @@ int texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_textu
     return SWR_OK;
 }
 
+// What a texture is updated from: src's colour plane (swr_texture_update_from_frame), program post_id of src between the resolve and
+// the quantiser (_from_post), or src's depth plane (_from_depth).  mode: the alpha mode, or the depth reduction.
+enum UpdateFrom { FROM_FRAME, FROM_POST, FROM_DEPTH };
+struct TextureUpdate { UpdateFrom from; int kx, ky, mode, post_id; };
+
 // Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream (but a first use or growth of src's resolved
-// plane, launch_post_over).  posted: swr_texture_update_from_post -- program post_id of src runs between the resolve and the quantiser.
-int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode, bool posted = false, int post_id = 0) {
+// plane, launch_post_over).
+int texture_update(swr_context* c, swr_texture* t, swr_context* src, const TextureUpdate& u) {
+    const int kx = u.kx, ky = u.ky;
+    const bool posted = u.from == FROM_POST, from_depth = u.from == FROM_DEPTH;
     if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
-    if (alpha_mode != SWR_TEXTURE_ALPHA_OPAQUE && alpha_mode != SWR_TEXTURE_ALPHA_KEEP)
+    if (!from_depth && u.mode != SWR_TEXTURE_ALPHA_OPAQUE && u.mode != SWR_TEXTURE_ALPHA_KEEP)
         return fail(c, SWR_ERR_INVALID_ARG, "alpha_mode must be SWR_TEXTURE_ALPHA_OPAQUE (0) or SWR_TEXTURE_ALPHA_KEEP (1)");
+    if (from_depth && u.mode != SWR_DEPTH_REDUCE_MAX && u.mode != SWR_DEPTH_REDUCE_MIN && u.mode != SWR_DEPTH_REDUCE_FIRST)
+        return fail(c, SWR_ERR_INVALID_ARG, "reduce must be SWR_DEPTH_REDUCE_MAX (0), SWR_DEPTH_REDUCE_MIN (1) or SWR_DEPTH_REDUCE_FIRST (2)");
+    if (int rc = texture_format_check(c, t, from_depth ? SWR_TEXTURE_FORMAT_DEPTH32F : SWR_TEXTURE_FORMAT_RGBA8)) return rc;
     if (!resolve_factor_ok(kx) || !resolve_factor_ok(ky)) return fail(c, SWR_ERR_INVALID_ARG, "resolve factors must be 1, 2, 4 or 8");
     if (src->device != c->device) return fail(c, SWR_ERR_UNSUPPORTED, "the source frame lives on another device");
     if (src->W > 0 && src->H > 0 && (src->band_ty0 != 0 || band_rows(src) != src->H))
@@ -327,12 +357,14 @@ int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, 
         return fail(c, SWR_ERR_INVALID_ARG, "the source frame must measure texture width * kx by texture height * ky");
     const PostProg* post = nullptr;
     if (posted) {
-        const auto it = src->posts.find(post_id);
+        const auto it = src->posts.find(u.post_id);
         if (it == src->posts.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
         post = it->second.get();
         for (const swr_texture* bound : post->tex)
             if (bound == t) return fail(c, SWR_ERR_INVALID_ARG, "the texture is bound to a slot of the program: a pass may not sample the texture it writes");
     }
+    // (k_depth_to_texture loads kx words at once; the context's own plane is an allocation's start)
+    if (from_depth && ((uintptr_t)src->depth & 15u)) return fail(c, SWR_ERR_INVALID_ARG, "the source's bound depth buffer must be 16-byte aligned");
     int rc;
     // the frame is complete behind this point of src's stream, and c's recorded draws are in front of the kernel on c's stream: they
     // sample the old texels (raster kernels and k_texture_sample, the only readers of a texture, run on `stream`, never on the front stream)
@@ -347,11 +379,15 @@ int texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, 
     if (post) {
         // (the resolve writes src's plane and the program may sample src's textures: both behind rtt_frame_ev, and src's later work --
         // a present, an update of such a texture -- behind rtt_done_ev)
-        if ((rc = launch_post_over(c, src, post, alpha_mode == SWR_TEXTURE_ALPHA_KEEP ? POST_TEXELS_KEEP : POST_TEXELS_OPAQUE, kx, ky, t->d_rgba, (uint32_t*)t->d_blocked))) return rc;
+        if ((rc = launch_post_over(c, src, post, u.mode == SWR_TEXTURE_ALPHA_KEEP ? POST_TEXELS_KEEP : POST_TEXELS_OPAQUE, kx, ky, t->d_rgba, (uint32_t*)t->d_blocked))) return rc;
     } else {
         const auto [grid, block] = deliver_shape((uint32_t)t->w, (uint32_t)t->h);
-        hipLaunchKernelGGL(rtt_kernel(kx, ky, alpha_mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
-                           (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
+        if (from_depth)
+            hipLaunchKernelGGL(depth_texture_kernel(kx, ky, blocked), grid, block, 0, c->stream, (const float*)src->depth,
+                               (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h, u.mode);
+        else
+            hipLaunchKernelGGL(rtt_kernel(kx, ky, u.mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
+                               (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
         SWR_HIP(c, hipGetLastError());
     }
     if (src != c && src->stream != c->stream) {
@@ -717,35 +753,53 @@ int swr_texture_create(swr_context* c, const uint8_t* rgba8, int w, int h, swr_t
     return rgba8 ? texture_create(c, rgba8, w, h, out, "texture upload failed: ") : fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
 }
 int swr_texture_create_target(swr_context* c, int w, int h, swr_texture** out) { SWR_ENTER(c); return texture_create(c, nullptr, w, h, out, "texture allocation failed: "); }
+int swr_texture_create_depth(swr_context* c, const float* depth, int w, int h, swr_texture** out) {
+    SWR_ENTER(c);
+    return texture_create(c, depth, w, h, out, depth ? "texture upload failed: " : "texture allocation failed: ", SWR_TEXTURE_FORMAT_DEPTH32F);
+}
 
 namespace {
-// swr_texture_update_from_frame / _from_post under the mutexes of both contexts
-int texture_update_locked(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode, bool posted, int post_id) {
+// swr_texture_update_from_frame / _from_post / _from_depth under the mutexes of both contexts
+int texture_update_locked(swr_context* c, swr_texture* t, swr_context* src, const TextureUpdate& u) {
     if (!c) return SWR_ERR_INVALID_ARG;
     if (!src || src == c) {
         std::lock_guard<std::mutex> lock_(c->mu);
         (void)hipSetDevice(c->device);
-        return texture_update_from_frame(c, t, c, kx, ky, alpha_mode, posted, post_id);
+        return texture_update(c, t, c, u);
     }
     std::lock(c->mu, src->mu);                            // (both, in an order that cannot deadlock against the opposite call)
     std::lock_guard<std::mutex> lock_c(c->mu, std::adopt_lock), lock_s(src->mu, std::adopt_lock);
     (void)hipSetDevice(c->device);
-    return texture_update_from_frame(c, t, src, kx, ky, alpha_mode, posted, post_id);
+    return texture_update(c, t, src, u);
+}
+
+// swr_texture_readback / _readback_depth: the row-major texels of a texture of `format`
+int texture_readback(swr_context* c, const swr_texture* t, void* out, int format) {
+    if (!t || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback arguments");
+    if (int rc = texture_format_check(c, t, format)) return rc;
+    SWR_HIP(c, hipMemcpyAsync(out, t->d_rgba, (size_t)t->w * t->h * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
 }
 }  // namespace
 
 int swr_texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
-    return texture_update_locked(c, t, src, kx, ky, alpha_mode, false, 0);
+    return texture_update_locked(c, t, src, TextureUpdate{ FROM_FRAME, kx, ky, alpha_mode, 0 });
 }
 int swr_texture_update_from_post(swr_context* c, swr_texture* t, swr_context* src, int post_id, int kx, int ky, int alpha_mode) {
-    return texture_update_locked(c, t, src, kx, ky, alpha_mode, true, post_id);
+    return texture_update_locked(c, t, src, TextureUpdate{ FROM_POST, kx, ky, alpha_mode, post_id });
+}
+int swr_texture_update_from_depth(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int reduce) {
+    return texture_update_locked(c, t, src, TextureUpdate{ FROM_DEPTH, kx, ky, reduce, 0 });
 }
 
-int swr_texture_readback(swr_context* c, const swr_texture* t, uint8_t* rgba8) {
+int swr_texture_readback(swr_context* c, const swr_texture* t, uint8_t* rgba8) { SWR_ENTER(c); return texture_readback(c, t, rgba8, SWR_TEXTURE_FORMAT_RGBA8); }
+int swr_texture_readback_depth(swr_context* c, const swr_texture* t, float* out) { SWR_ENTER(c); return texture_readback(c, t, out, SWR_TEXTURE_FORMAT_DEPTH32F); }
+
+int swr_texture_format(swr_context* c, const swr_texture* t, int* format) {
     SWR_ENTER(c);
-    if (!t || !rgba8) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback arguments");
-    SWR_HIP(c, hipMemcpyAsync(rgba8, t->d_rgba, (size_t)t->w * t->h * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
+    if (!t || !format) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_format arguments");
+    *format = t->format;
+    return SWR_OK;
 }
 
 int swr_texture_set_filter(swr_context* c, swr_texture* t, int bilinear) {
@@ -780,6 +834,7 @@ int swr_texture_destroy(swr_context* c, swr_texture* t) {
 int swr_texture_sample(swr_context* c, const swr_texture* t, const float* uv, int n, float* out) {
     SWR_ENTER(c);
     if (!t || !uv || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample arguments");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
     if (n == 0) return SWR_OK;
     const size_t off_out = ((size_t)n * 8 + 15) & ~(size_t)15;
     int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 16);
@@ -790,6 +845,23 @@ int swr_texture_sample(swr_context* c, const swr_texture* t, const float* uv, in
     hipLaunchKernelGGL(k_texture_sample, dim3((n + 255) / 256), dim3(256), 0, c->stream, t->d_rgba, t->w, t->h, d_uv, n, d_out);
     SWR_HIP(c, hipGetLastError());
     SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+int swr_texture_sample_depth(swr_context* c, const swr_texture* t, const float* uv_ref, int n, float* out) {
+    SWR_ENTER(c);
+    if (!t || !uv_ref || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_depth arguments");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_DEPTH32F)) return rc;
+    if (n == 0) return SWR_OK;
+    const size_t off_out = ((size_t)n * 12 + 15) & ~(size_t)15;
+    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 8);
+    if (rc) return rc;
+    float* d_in = c->d_scratch.as<float>();
+    float2* d_out = reinterpret_cast<float2*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
+    SWR_HIP(c, hipMemcpyAsync(d_in, uv_ref, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_texture_sample_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float*)d_in, n, d_out);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_locked(c);
 }
 

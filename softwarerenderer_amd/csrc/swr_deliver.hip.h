@@ -47,6 +47,8 @@
 //   k_resolve_rgba<KX, KY>       one float4 into a window-sized plane of the context, for k_post.  Not launched under (1, 1), where the
 //                                frame is that plane already.  The plane is deliberate: a program that fetches neighbours would
 //                                otherwise redo a tree of up to 64 samples per tap.
+//   k_depth_to_texture<KX, KY, BLOCKED>  the DEPTH plane's KX x KY words reduced to one by a select tree (at the end of this file, with
+//                                its definition) and stored as k_frame_to_texture stores its dword: a depth texture's texel
 // Two other thread mappings were measured and removed: one lane per SOURCE pixel with in-wave adds for the resolve, and four
 // consecutive pixels per thread with whole-dword stores for the 8-bit present.  DESIGN.md sections 17 and 18 have the figures.
 // No LDS, no scratch, no inline assembly; nothing here is shared with the render kernels.  KX, KY in {1, 2, 4, 8} divide the
@@ -185,6 +187,74 @@ void k_resolve_rgba(const float4* __restrict__ color, float4* __restrict__ plane
     uint32_t ox, oy;
     if (!deliver_pixel(out_w, out_rows, ox, oy)) return;
     store_plane(plane, deliver_index(out_w, ox, oy), resolve_pixel<KX, KY>(color, out_w, ox, oy));
+}
+
+// ---- depth to texture (tests/depth_texture_cases.py restates it in numpy).  Texel (x, y) of a w x h depth texture
+// updated from a depth plane of w * KX by h * KY words is ONE of the block's own words, bit for bit -- no scale, no quantiser --, chosen
+// by the resolve's tree shape with a select in the addition's place: a balanced pairwise tree over the KX adjacent words of each row,
+// left to right, then the same tree over the KY row results, top to bottom, of
+//   SWR_DEPTH_REDUCE_MAX    pick(a, b) = b > a ? b : a     the nearest sample under the default test (new >= old, Rasterizer.cs:545)
+//   SWR_DEPTH_REDUCE_MIN    pick(a, b) = b < a ? b : a
+//   SWR_DEPTH_REDUCE_FIRST  pick(a, b) = a                 the top-left sample, the word swr_post_depth reads
+// The selects are pure: a NaN on the left stays, a NaN on the right is never taken, of +0 and -0 the left one stays -- which is why
+// the tree order is part of the definition, and why these are compares and selects, never a max or min instruction.  Under (1, 1)
+// all three copy the plane.
+template <int REDUCE>
+__device__ __forceinline__ float depth_pick(float a, float b) {
+    static_assert(REDUCE == SWR_DEPTH_REDUCE_MAX || REDUCE == SWR_DEPTH_REDUCE_MIN || REDUCE == SWR_DEPTH_REDUCE_FIRST, "a reduction of include/swr.h");
+    if constexpr (REDUCE == SWR_DEPTH_REDUCE_MAX) return b > a ? b : a;
+    else if constexpr (REDUCE == SWR_DEPTH_REDUCE_MIN) return b < a ? b : a;
+    else return a;
+}
+// the tree over N values in registers
+template <int REDUCE, int N>
+__device__ __forceinline__ float depth_tree(const float* v) {
+    if constexpr (N == 1) return v[0];
+    else return depth_pick<REDUCE>(depth_tree<REDUCE, N / 2>(v), depth_tree<REDUCE, N / 2>(v + N / 2));
+}
+// KX adjacent words of one row in one load of KX * 4 bytes (two of 16 under KX = 8): p is KX * 4-byte aligned, because the plane is
+// (swr_texture_update_from_depth checks a bound one) and the row pitch w * KX and the offset x * KX are multiples of KX words
+template <int KX>
+__device__ __forceinline__ void depth_load_row(const float* __restrict__ p, float* v) {
+    if constexpr (KX == 1) v[0] = p[0];
+    else if constexpr (KX == 2) { const float2 a = *reinterpret_cast<const float2*>(p); v[0] = a.x; v[1] = a.y; }
+    else {
+#pragma unroll
+        for (int i = 0; i < KX / 4; ++i) {
+            const float4 a = reinterpret_cast<const float4*>(p)[i];
+            v[4 * i] = a.x; v[4 * i + 1] = a.y; v[4 * i + 2] = a.z; v[4 * i + 3] = a.w;
+        }
+    }
+}
+// the word of the KX x KY block at p, rows `pitch` words apart (under FIRST the compiler drops every load but the first word's)
+template <int REDUCE, int KX, int KY>
+__device__ __forceinline__ float depth_block(const float* __restrict__ p, size_t pitch) {
+    float rows[KY];
+#pragma unroll
+    for (int r = 0; r < KY; ++r) {
+        float v[KX];
+        depth_load_row<KX>(p + (size_t)r * pitch, v);
+        rows[r] = depth_tree<REDUCE, KX>(v);
+    }
+    return depth_tree<REDUCE, KY>(rows);
+}
+
+// depth: the source plane, w * KX words wide and h * KY rows high; words: h x w texels row-major; blocked (BLOCKED only): the same
+// texels block-linear.  One thread per texel on deliver_pixel's grid; a wave's loads of one row cover 64 * KX * 4 contiguous bytes and
+// its store 256.  `reduce` is a run-time argument -- one scalar branch per wave in front of the loads -- and not a template parameter:
+// 32 instantiations instead of 96 (k_frame_to_texture has 64 already), and the kernel's time is its loads either way.
+template <int KX, int KY, bool BLOCKED>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_depth_to_texture(const float* __restrict__ depth, uint32_t* __restrict__ words, uint32_t* __restrict__ blocked, uint32_t w, uint32_t h, int reduce) {
+    static_assert((KX == 1 || KX == 2 || KX == 4 || KX == 8) && (KY == 1 || KY == 2 || KY == 4 || KY == 8), "factors divide the tile");
+    uint32_t x, y;
+    if (!deliver_pixel(w, h, x, y)) return;
+    const size_t pitch = (size_t)w * KX;
+    const float* __restrict__ p = depth + (size_t)y * KY * pitch + (size_t)x * KX;
+    const float d = reduce == SWR_DEPTH_REDUCE_MAX ? depth_block<SWR_DEPTH_REDUCE_MAX, KX, KY>(p, pitch)
+                  : reduce == SWR_DEPTH_REDUCE_MIN ? depth_block<SWR_DEPTH_REDUCE_MIN, KX, KY>(p, pitch)
+                  : depth_block<SWR_DEPTH_REDUCE_FIRST, KX, KY>(p, pitch);
+    store_texel(words, blocked, BLOCKED, w, x, y, __float_as_uint(d));
 }
 
 }  // namespace swr

@@ -612,6 +612,54 @@ __device__ __forceinline__ float4 texture_slot_texel(const TextureSlot& t, int x
     return texture_unpack(t32[t.w < 0 ? bilinear_texel_offset<true>(w, x, y) : bilinear_texel_offset<false>(w, x, y)]);
 }
 
+// DEPTH TEXTURES (build-defined; include/swr.h; tests/depth_texture_cases.py restates these in numpy).  A slot
+// that holds a depth texture has the same record: its 4-byte texels are float32 depth words as the raster stage stores them.  The
+// program says what the words mean by which function it calls, as a GLSL program does with sampler2DShadow; the functions above read
+// the same words as RGBA8, which is defined and memory-safe.  None of these is called by a kernel of the product library.
+// The word of texel (x, y) in either layout:
+__device__ __forceinline__ float texture_slot_depth_word(const TextureSlot& t, int w, int x, int y) {
+    const float* __restrict__ f = reinterpret_cast<const float*>(t.texels);
+    return f[t.w < 0 ? bilinear_texel_offset<true>(w, x, y) : bilinear_texel_offset<false>(w, x, y)];
+}
+// texel (x, y), x clamped to [0, w - 1] and y to [0, h - 1]; float.MinValue -- the cleared depth: nothing was drawn -- from an unbound slot
+__device__ __forceinline__ float texture_slot_depth_texel(const TextureSlot& t, int x, int y) {
+    if (!texture_slot_bound(t)) return SWR_FLOAT_MINVALUE;
+    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
+    x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x); y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+    return texture_slot_depth_word(t, w, x, y);
+}
+// the texel Texture.Sample's addressing picks (Texture.cs:43-54: texture_nearest_index), ALWAYS nearest whatever the filter: depth
+// words are not blended.  (Its x and y are taken back out of the index only where the slot holds the block-linear copy.)
+__device__ __forceinline__ float texture_slot_depth_sample(const TextureSlot& t, float tu, float tv) {
+    if (!texture_slot_bound(t)) return SWR_FLOAT_MINVALUE;
+    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
+    const uint32_t i = texture_nearest_index(w, h, tu, tv);
+    if (t.w >= 0) return reinterpret_cast<const float*>(t.texels)[i];
+    const uint32_t y = i / (uint32_t)w;
+    return texture_slot_depth_word(t, w, (int)(i - y * (uint32_t)w), (int)y);
+}
+// 1 where a fragment of depth `ref` would pass the default test (LessEqual: new >= old, Rasterizer.cs:545; false for NaN) against the
+// stored depth, else 0; the bias is the caller's, added into ref.  Nearest filter (h >= 0): the one texel texture_slot_depth_sample
+// reads.  Bilinear filter (h < 0): the footprint and the fractions of texture_sample_bilinear, the four RESULTS in {0, 1} blended
+// (percentage-closer filtering) -- as lerps, so that where all four agree every difference is exactly 0 and the result exactly 0 or 1
+// (the colour filter's c (1 - fx) + c fx does not promise that, and programs branch on == 1.0f).  An unbound slot: 1, lit.
+__device__ __forceinline__ float texture_slot_shadow(const TextureSlot& t, float tu, float tv, float ref) {
+    if (!texture_slot_bound(t)) return 1.0f;
+    if (t.h >= 0) return ref >= texture_slot_depth_sample(t, tu, tv) ? 1.0f : 0.0f;
+    const int w = t.w < 0 ? -t.w : t.w, h = -t.h;
+    const float x = tu * (float)w - 0.5f, y = tv * (float)h - 0.5f;
+    const float x0 = floorf(x), y0 = floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    int ix0 = f2i(x0) % w; if (ix0 < 0) ix0 += w;
+    int iy0 = f2i(y0) % h; if (iy0 < 0) iy0 += h;
+    const int ix1 = ix0 + 1 == w ? 0 : ix0 + 1, iy1 = iy0 + 1 == h ? 0 : iy0 + 1;
+    const float c00 = ref >= texture_slot_depth_word(t, w, ix0, iy0) ? 1.0f : 0.0f, c10 = ref >= texture_slot_depth_word(t, w, ix1, iy0) ? 1.0f : 0.0f;
+    const float c01 = ref >= texture_slot_depth_word(t, w, ix0, iy1) ? 1.0f : 0.0f, c11 = ref >= texture_slot_depth_word(t, w, ix1, iy1) ? 1.0f : 0.0f;
+    const float top = c00 + (c10 - c00) * fx;
+    const float bot = c01 + (c11 - c01) * fx;
+    return top + (bot - top) * fy;
+}
+
 // The per-draw block of a user-program batch (RasterArgs::user_consts, k_vertex_user's last argument): the draw's 64 captured constants,
 // then its captured texture slots 1 .. SWR_PROGRAM_TEXTURES - 1 as TextureSlot records (slot 0 is the draw's texture, in DrawParams).
 // Only run-time compiled kernels read it.  76 words, 304 bytes: every block and every record in it is 16-byte aligned.

@@ -22,6 +22,8 @@ struct swr_texture {
                                               // and written beside d_rgba by swr_texture_update_from_frame from then on
     int w = 0, h = 0;
     bool bilinear = false;                    // build-defined extension; the reference's Texture.Sample is nearest
+    int format = SWR_TEXTURE_FORMAT_RGBA8;    // or SWR_TEXTURE_FORMAT_DEPTH32F: the same 4-byte texels, float32 depth words (d_rgba names the
+                                              // row-major copy of either).  Host-side only: a slot's record does not carry it
 };
 
 namespace {

@@ -98,6 +98,14 @@ __device__ __forceinline__ float4 swr_post_texel(const swr_post_env& env, int sl
     if (!swr_post_has_texture(env, slot)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     return swr::texture_slot_texel(env.textures_[slot], x, y);
 }
+// A slot that holds a DEPTH texture: swr_texel_depth, swr_sample_depth and swr_shadow of a user program
+// (swr_program.hip.h; definitions in swr_device.h).  An unbound slot reads float.MinValue and shadows nothing (1).
+__device__ __forceinline__ swr::TextureSlot swr_post_slot_(const swr_post_env& env, int slot) {
+    return (unsigned)slot < (unsigned)SWR_POST_TEXTURES ? env.textures_[slot] : swr::TextureSlot{ nullptr, 0, 0 };
+}
+__device__ __forceinline__ float swr_post_texel_depth(const swr_post_env& env, int slot, int x, int y) { return swr::texture_slot_depth_texel(swr_post_slot_(env, slot), x, y); }
+__device__ __forceinline__ float swr_post_sample_depth(const swr_post_env& env, int slot, float2 uv) { return swr::texture_slot_depth_sample(swr_post_slot_(env, slot), uv.x, uv.y); }
+__device__ __forceinline__ float swr_post_shadow(const swr_post_env& env, int slot, float2 uv, float ref) { return swr::texture_slot_shadow(swr_post_slot_(env, slot), uv.x, uv.y, ref); }
 
 // the user's program (always inlined into k_post)
 __device__ __attribute__((always_inline)) float4 swr_post(const swr_post_in& in, const swr_post_env& env);

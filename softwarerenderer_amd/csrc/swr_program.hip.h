@@ -78,6 +78,15 @@ __device__ __forceinline__ bool swr_has_texture(const swr_fs_env& env, int slot)
 __device__ __forceinline__ float4 swr_sample(const swr_fs_env& env, int slot, float2 uv) { return swr::texture_slot_sample(swr_slot_(env, slot), uv.x, uv.y); }
 __device__ __forceinline__ float4 swr_texel(const swr_fs_env& env, int slot, int x, int y) { return swr::texture_slot_texel(swr_slot_(env, slot), x, y); }
 __device__ __forceinline__ int2 swr_texture_size(const swr_fs_env& env, int slot) { return swr::texture_slot_size(swr_slot_(env, slot)); }
+// A slot that holds a DEPTH texture (swr_texture_create_depth, swr_texture_update_from_depth) is read through
+// these three (swr_device.h has the definitions); an unbound slot has nothing drawn in it: float.MinValue, and every fragment is lit.
+//   swr_texel_depth(env, slot, x, y)   the float32 depth word of texel (x, y), clamped as swr_texel clamps
+//   swr_sample_depth(env, slot, uv)    the word of the texel Texture.Sample's addressing picks: nearest whatever the filter
+//   swr_shadow(env, slot, uv, ref)     1 where ref >= the stored depth (a fragment of depth ref passes LessEqual), else 0: one texel
+//                                      under the nearest filter, the 2 x 2 footprint's four results blended under the bilinear one
+__device__ __forceinline__ float swr_texel_depth(const swr_fs_env& env, int slot, int x, int y) { return swr::texture_slot_depth_texel(swr_slot_(env, slot), x, y); }
+__device__ __forceinline__ float swr_sample_depth(const swr_fs_env& env, int slot, float2 uv) { return swr::texture_slot_depth_sample(swr_slot_(env, slot), uv.x, uv.y); }
+__device__ __forceinline__ float swr_shadow(const swr_fs_env& env, int slot, float2 uv, float ref) { return swr::texture_slot_shadow(swr_slot_(env, slot), uv.x, uv.y, ref); }
 // the build's System.Numerics model (SWR_DOT_PAIRWISE): Vector3.Dot.  (swr_lerp, swr_max and swr_clamp: swr_user_math.hip.h)
 __device__ __forceinline__ float swr_dot3(float3 a, float3 b) { return swr::dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 // a null result: nothing is written (and under BlendMode.None the row's early-out applies)
@@ -116,6 +125,9 @@ __device__ __forceinline__ bool swr_has_texture(const swr_vs_env& env, int slot)
 __device__ __forceinline__ float4 swr_sample(const swr_vs_env& env, int slot, float2 uv) { return swr::texture_slot_sample(swr_slot_(env, slot), uv.x, uv.y); }
 __device__ __forceinline__ float4 swr_texel(const swr_vs_env& env, int slot, int x, int y) { return swr::texture_slot_texel(swr_slot_(env, slot), x, y); }
 __device__ __forceinline__ int2 swr_texture_size(const swr_vs_env& env, int slot) { return swr::texture_slot_size(swr_slot_(env, slot)); }
+__device__ __forceinline__ float swr_texel_depth(const swr_vs_env& env, int slot, int x, int y) { return swr::texture_slot_depth_texel(swr_slot_(env, slot), x, y); }
+__device__ __forceinline__ float swr_sample_depth(const swr_vs_env& env, int slot, float2 uv) { return swr::texture_slot_depth_sample(swr_slot_(env, slot), uv.x, uv.y); }
+__device__ __forceinline__ float swr_shadow(const swr_vs_env& env, int slot, float2 uv, float ref) { return swr::texture_slot_shadow(swr_slot_(env, slot), uv.x, uv.y, ref); }
 // new Shaders.VertexOutput() (Shaders.cs:26-47): zero-initialised before swr_vertex is called, Interpolate = true
 struct swr_vs_out {
     float4 clip_position;        // ClipPosition

@@ -452,6 +452,15 @@ __global__ __launch_bounds__(256) void k_texture_sample(const uint8_t* __restric
     if (i < n) out[i] = texture_sample(tex, w, h, uv[i].x, uv[i].y);
 }
 
+// swr_texture_sample_depth: the two device lookups of a depth texture as a slot holds it (filter and layout included);
+// uv_ref: n x (u, v, ref), out: n x (depth word, shadow)
+__global__ __launch_bounds__(256) void k_texture_sample_depth(TextureSlot t, const float* __restrict__ uv_ref, int n, float2* __restrict__ out) {
+    int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float u = uv_ref[3 * i], v = uv_ref[3 * i + 1], ref = uv_ref[3 * i + 2];
+    out[i] = make_float2(texture_slot_depth_sample(t, u, v), texture_slot_shadow(t, u, v, ref));
+}
+
 // row-major RGBA8 -> block-linear (4 x 4-texel blocks of 64 B, see bilinear_texel_offset); w and h are multiples of 4
 __global__ __launch_bounds__(256) void k_block_texture(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int w, int h) {
     const size_t n = (size_t)w * (size_t)h;

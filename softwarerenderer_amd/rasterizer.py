@@ -56,6 +56,12 @@ class CullMode(enum.IntEnum):       # Rasterizer.cs:45-50
     Front = 2
 
 
+class DepthReduce(enum.IntEnum):    # build-defined: SWR_DEPTH_REDUCE_* of include/swr.h (Texture.UpdateFromDepth)
+    Max = 0                         # the block's nearest sample under the default LessEqual test
+    Min = 1
+    First = 2                       # the block's top-left sample
+
+
 class Program(enum.IntEnum):        # built-in programs (include/swr.h)
     FlatColor = 0
     Gouraud = 1
@@ -319,6 +325,56 @@ class Texture:
         src = window._dev._ctx if window._dev is not self._dev else None
         self._dev._ck(self._dev._lib.swr_texture_update_from_post(
             self._dev._ctx, self._h, src, post._id, int(kx), int(ky), N.SWR_TEXTURE_ALPHA_KEEP if keep_alpha else N.SWR_TEXTURE_ALPHA_OPAQUE))
+
+    @classmethod
+    def Depth(cls, device: Device, width: int, height: int, depth: Optional[np.ndarray] = None) -> "Texture":
+        """A depth texture (swr_texture_create_depth; build-defined): float32 depth words as the raster stage stores them, `depth`
+        of shape (height, width) or, without it, float.MinValue everywhere -- nothing drawn.  Filled by UpdateFromDepth, read in
+        programs through swr_shadow / swr_sample_depth / swr_texel_depth; SetBilinear switches swr_shadow to its 2 x 2 form."""
+        t = cls.__new__(cls)
+        t._dev = device
+        t.Height, t.Width = int(height), int(width)
+        t._h = C.c_void_p()
+        words = None
+        if depth is not None:
+            words = np.ascontiguousarray(depth, dtype=np.float32)
+            if words.shape != (t.Height, t.Width):
+                raise ValueError("depth must be (height, width) float32")
+        device._ck(device._lib.swr_texture_create_depth(device._ctx, words.ctypes.data if words is not None else None, t.Width, t.Height, C.byref(t._h)))
+        return t
+
+    @property
+    def Format(self) -> int:
+        """SWR_TEXTURE_FORMAT_RGBA8 (0) or SWR_TEXTURE_FORMAT_DEPTH32F (1) (swr_texture_format)."""
+        f = C.c_int(-1)
+        self._dev._ck(self._dev._lib.swr_texture_format(self._dev._ctx, self._h, C.byref(f)))
+        return f.value
+
+    def UpdateFromDepth(self, window: "MainWindow", kx: int = 1, ky: int = 1, reduce: int = DepthReduce.Max):
+        """A frame's depth into this depth texture (swr_texture_update_from_depth): each texel becomes one word of its kx x ky block
+        of the window's depth plane -- the nearest (Max, under the default LessEqual test), the farthest (Min) or the top-left one
+        (First).  The window measures Width * kx by Height * ky; otherwise UpdateFrom's contract: immediate-mode order, no wait for
+        the GPU, the window of this Device or of another on the same GPU."""
+        window._activate()
+        src = window._dev._ctx if window._dev is not self._dev else None
+        self._dev._ck(self._dev._lib.swr_texture_update_from_depth(self._dev._ctx, self._h, src, int(kx), int(ky), int(reduce)))
+
+    def ReadDepth(self) -> np.ndarray:
+        """The depth words as (Height, Width) float32 (swr_texture_readback_depth); waits for the GPU."""
+        out = np.empty((self.Height, self.Width), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_texture_readback_depth(self._dev._ctx, self._h, out.ctypes.data))
+        return out
+
+    def SampleDepth(self, uv, ref) -> tuple:
+        """The device lookups of a depth texture with its filter as it is now (swr_texture_sample_depth), batched: uv of shape
+        (..., 2) and ref of shape (...) -> (depth, shadow), each of shape (...).  depth: the word of the texel Texture.Sample's
+        addressing picks.  shadow: 1 where ref >= the stored depth, one texel (nearest) or the 2 x 2 footprint blended (bilinear)."""
+        a = np.ascontiguousarray(np.asarray(uv, dtype=np.float32))
+        r = np.broadcast_to(np.asarray(ref, dtype=np.float32), a.shape[:-1])
+        flat = np.ascontiguousarray(np.concatenate([a.reshape(-1, 2), r.reshape(-1, 1)], axis=1))
+        out = np.empty((flat.shape[0], 2), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_texture_sample_depth(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
+        return out[:, 0].reshape(a.shape[:-1]), out[:, 1].reshape(a.shape[:-1])
 
     def Read(self) -> np.ndarray:
         """The texels as (Height, Width, 4) uint8 (swr_texture_readback); waits for the GPU."""
