@@ -64,12 +64,18 @@ struct BinArgs {
 __device__ __forceinline__ void bin_overflow(const BinArgs& a) {
     a.counters->overflow = 1u;
     if (a.ctrl->host_flag) __hip_atomic_store(a.ctrl->host_flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (a.replayable) {
-        atomicMin(&a.ctrl->first_bad, a.seq);
-        atomicMax(&a.ctrl->need, 2ull * (unsigned long long)a.list_capacity + 4096ull);
-        __hip_atomic_store(&a.ctrl->poison, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (a.ctrl->host_flag) __hip_atomic_store(a.ctrl->host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (a.replayable) poison_batch(a.ctrl, a.seq, 2ull * (unsigned long long)a.list_capacity + 4096ull);
+}
+// One pair into its tile's list.  store_pair: FILL, at a position already known (a position beyond the capacity: bin_overflow);
+// place_pair: FILL takes the position from the tile's cursor, COUNT only counts the pair.
+__device__ __forceinline__ void store_pair(const BinArgs& a, uint32_t at, uint32_t slot) {
+    if (at < a.list_capacity) a.tile_list[at] = slot;
+    else bin_overflow(a);
+}
+template <bool FILL>
+__device__ __forceinline__ void place_pair(const BinArgs& a, uint32_t tile, uint32_t slot) {
+    if (FILL) store_pair(a, a.tile_start[tile] + atomicAdd(&a.tile_count[tile], 1u), slot);
+    else atomicAdd(&a.tile_count[tile], 1u);
 }
 
 // ---- heaviest-first tile order for the raster kernel ---------------------------------------------
@@ -204,11 +210,7 @@ __device__ __forceinline__ void bin_big(const BinArgs& a, const SlotData& sd, ui
         if (FILL) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (want[j]) {
-                    const uint32_t at = a.tile_start[tile[j]] + base[j];
-                    if (at < a.list_capacity) a.tile_list[at] = sslot[j];
-                    else bin_overflow(a);
-                }
+                if (want[j]) store_pair(a, a.tile_start[tile[j]] + base[j], sslot[j]);
             }
         }
     }
@@ -234,13 +236,7 @@ __device__ __forceinline__ void bin_big(const BinArgs& a, const SlotData& sd, ui
             }
             if (want) {
                 const uint32_t tile = (uint32_t)(band_local_row(a.band, ty) * a.tiles_x + tx);
-                if (FILL) {
-                    const uint32_t at = a.tile_start[tile] + atomicAdd(&a.tile_count[tile], 1u);
-                    if (at < a.list_capacity) a.tile_list[at] = s_slot;
-                    else bin_overflow(a);
-                } else {
-                    atomicAdd(&a.tile_count[tile], 1u);
-                }
+                place_pair<FILL>(a, tile, s_slot);
             }
         }
     }
@@ -286,12 +282,8 @@ __device__ __forceinline__ void bin_block_slots(const BinArgs& a, uint32_t slot,
                 if (placed) {
                     const uint32_t rank = atomicAdd(&s_val[e], 1u);       // < 2048
                     packed[i] = e | (rank << 12) | 0x80000000u;
-                } else if (FILL) {                                      // crowded table (many distinct tiles): go direct
-                    const uint32_t at = a.tile_start[tile] + atomicAdd(&a.tile_count[tile], 1u);
-                    if (at < a.list_capacity) a.tile_list[at] = slot;
-                    else bin_overflow(a);
-                } else {
-                    atomicAdd(&a.tile_count[tile], 1u);
+                } else {                                                // crowded table (many distinct tiles): go direct
+                    place_pair<FILL>(a, tile, slot);
                 }
             }
             w.next();
@@ -312,11 +304,7 @@ __device__ __forceinline__ void bin_block_slots(const BinArgs& a, uint32_t slot,
         // phase 3: list position = the tile's base for this block + the pair's rank in the block
 #pragma unroll
         for (int i = 0; i < SWR_SMALL_TILES; ++i) {
-            if (packed[i] & 0x80000000u) {
-                const uint32_t at = s_val[packed[i] & 0xfffu] + ((packed[i] >> 12) & 0x7ffffu);
-                if (at < a.list_capacity) a.tile_list[at] = slot;
-                else bin_overflow(a);
-            }
+            if (packed[i] & 0x80000000u) store_pair(a, s_val[packed[i] & 0xfffu] + ((packed[i] >> 12) & 0x7ffffu), slot);
         }
     }
     bin_big<FILL>(a, sd, slot, big);
@@ -428,10 +416,7 @@ __global__ __launch_bounds__(SWR_SCAN_BLOCK) void k_scan_apply(uint32_t* __restr
         *total_out = total;
         if (total > capacity) {                     // does not fit: poison this and every later batch
             if (!poison_on_overflow) return;
-            atomicMin(&ctrl->first_bad, seq);
-            atomicMax(&ctrl->need, total);
-            __hip_atomic_store(&ctrl->poison, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (ctrl->host_flag) __hip_atomic_store(ctrl->host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            poison_batch(ctrl, seq, total);
         } else if (poison_on_overflow && !batch_poisoned(ctrl, seq)) {
             atomicAdd(&counters->tile_pairs, total);        // MODE_SYNC rounds are counted by the host
         }

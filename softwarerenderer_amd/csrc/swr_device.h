@@ -140,6 +140,14 @@ struct Ctrl {
 // raster kernel of flush N) a LATER batch may poison itself while this one's raster kernel is half way through its tiles, and
 // that must not stop the tiles that have not started yet -- the host replays from `first_bad` only.
 __device__ __forceinline__ bool batch_poisoned(const Ctrl* __restrict__ c, uint32_t seq) { return c->first_bad <= seq; }
+// Batch `seq` does not fit its pair lists (`need`: a capacity that would hold it): it and every later batch are poisoned, and the host's
+// polled word goes up with the device's
+__device__ __forceinline__ void poison_batch(Ctrl* __restrict__ c, uint32_t seq, unsigned long long need) {
+    atomicMin(&c->first_bad, seq);
+    atomicMax(&c->need, need);
+    __hip_atomic_store(&c->poison, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c->host_flag) __hip_atomic_store(c->host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 struct FrameParams {
     int width, height;          // full frame

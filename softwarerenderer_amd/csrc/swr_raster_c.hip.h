@@ -365,33 +365,37 @@ __global__ __launch_bounds__(SWR_COVER_BLOCK) void k_cover(CoverArgs a) {
 #define SWR_WINDOW 32                          // candidate pairs examined per batch (<= 64)
 // (every size here was swept: 8 / 12 / 13 / 20 / 24 / 28-pair batches, windows of 24-64, 1536 fragments -- profiles/r02_final_ablations.txt,
 //  profiles/r03_raster_experiments.md; the switches are gone, the numbers stay)
-// Where the three outputs' varyings of a pair come from when a fragment is shaded (VG in the code):
-//   staged in LDS (round 2's layout): nine rows per pair (twelve with the 4-light program's world position), 292 B per pair;
-//   from the vertex-stage output in HBM: buffer loads with staged byte offsets -- the lanes of one pair read the same 16-byte rows,
-//     a chunk touches the vertices of 3-4 pairs -- and only what the chain replay, the depth test and Interpolate's divisions need
-//     stays staged: 176 B per pair, 8,336 B per wave with 16 pairs = 18 waves per CU instead of 16 (LDS is allocated in units of
-//     1,280 B, tools/ubench/lds_occupancy.hip).
-// Measured on cfg3 (profiles/r03_raster_experiments.md): the loads cost 7 % at equal occupancy and the two extra waves return 4-5 %,
-// so the kernels WITHOUT the 4-light program keep the staged layout (VG = false); the kernels that carry it (PHONG = true: staged, they
-// had to shrink their batch to 12 pairs to stay at 16 waves) take the loads (VG = true): 16 pairs per batch again and 18 waves, cfg4 -5 %.
+// VG -- "varyings from global memory" -- is the one layout switch of this file: the template parameter of WaveLdsC and the second of
+// k_raster_c.  It says where a pair's three outputs' varyings come from when a fragment is shaded, and with that what a kernel can reach:
+//   VG = false, STAGED: the staging lane copies nine rows per pair (clip, colour, uv + normal of each output) into LDS, 292 B per pair,
+//     10,208 B per wave = 16 waves per CU.  A fragment reads nothing but LDS.  World position and the side arrays (Normal, the user
+//     block) are NOT reachable: the kernels of the reference's own programs (DUST2, Gouraud, flat, the generic one over them).
+//   VG = true, LOADED: buffer loads from the vertex-stage output in HBM with staged byte offsets -- the lanes of one pair read the same
+//     16-byte rows, a chunk touches the vertices of 3-4 pairs -- and only what the chain replay, the depth test and Interpolate's
+//     divisions need stays staged: 176 B per pair, 8,352 B per wave = 18 waves per CU (LDS is allocated in units of 1,280 B,
+//     tools/ubench/lds_occupancy.hip).  Every row of VOut, the Normal side array and the TriRec are reachable: the 4-light program
+//     (world position), wireframe, DEBUG_VARYINGS, user programs, the generic kernel over them.
+// Measured on cfg3 (profiles/r03_raster_experiments.md): the loads cost 7 % at equal occupancy and the two extra waves return 4-5 %, so
+// the reference's programs stay staged; a staged layout WITH world position (12-pair batches) lost by 5 % on cfg4 and is gone.
 // When the rows are requested (VG): the uv rows by the fragments that survive the chunk's cut, ahead of the chain replay (the texel
 // address hangs on them), the rest by the fragments that passed the depth test (cfg3, all kernels VG: 0.4290 ms against 0.4333 for
 // everything after the depth test, 0.4303 for everything ahead of the election, 0.4241 but spilling for everything after the cut).
-// The DUST2 kernel shades with the straight-line speculate-then-verify shader (shade_dust2_fast, swr_raster.hip.h).
-// staged float4 rows per pair (everything per-pair is computed once here instead of once per fragment):
+// float4 rows of `stage` per pair (everything per-pair is computed once at staging instead of once per fragment), both layouts:
 //   0: edge values at the pair's first pixel (w0,w1,w2 of Rasterizer.cs:481-483), invArea   [lines: t0x,t1x,t0y,t1y]
 //   1: depths[0..2], draw/flags word          2: column steps a12,a20,a01, first pixel (x,y inside the tile, 8 bits each)
 //   3: row steps b12,b20,b01, stream position of the pair's first fragment (int bits)
-//   VG:              4: byte offsets of outputs[0..2] in the VOut array, clip.w of outputs[0]
-//                    5: refined reciprocals of the three clip.w (Interpolate's divisions, see div_core), clip.w of outputs[1]
-//                    (clip.w of outputs[2] rides in the row-start entry)
-//                    6: byte offset of the pair's TriRec (DEBUG_VARYINGS reads the three screen positions from it)
-//   else 4-6 / 7-9 / 10-12: outputs[0] / [1] / [2] as {clip (x replaced by the output's wn.z, y by the refined reciprocal of clip.w),
-//   color, uv + wn.xy};  PHONG adds 13-15 = {wn.z, wpos} of each
-#define SWR_VROW(r, idx) L.stage[r][idx]
-template <bool PHONG>
+// VG (7 rows):
+//   ROW_VG_OFF: byte offsets of outputs[0..2] in the VOut array, clip.w of outputs[0]
+//   ROW_VG_RCP: refined reciprocals of the three clip.w (Interpolate's divisions, see div_core), clip.w of outputs[1]
+//               (clip.w of outputs[2] rides in the row-start entry, rt_w)
+//   ROW_VG_REC: byte offset of the pair's TriRec (DEBUG_VARYINGS and user programs read the three screen positions from it)
+// staged (13 rows):
+//   ROW_ST_OUT + 3 k + {0, 1, 2}: outputs[k] as {clip (x replaced by the output's wn.z, y by the refined reciprocal of clip.w), color,
+//               uv + wn.xy}
+constexpr int ROW_VG_OFF = 4, ROW_VG_RCP = 5, ROW_VG_REC = 6;
+constexpr int ROW_ST_OUT = 4;
+template <bool VG>
 struct __attribute__((aligned(16))) WaveLdsC {
-    static constexpr bool VG = PHONG;
     static constexpr int NQ = VG ? 7 : 13;
     static constexpr int BATCH = SWR_BATCH;        // pairs staged per batch
     static constexpr int WINDOW = SWR_WINDOW;      // candidate pairs examined per batch
@@ -419,7 +423,10 @@ struct __attribute__((aligned(16))) WaveLdsC {
         if constexpr (VG) { const float4 e = rowtab4[q][t]; x = e.x; y = e.y; z = e.z; }
         else { x = rowtab3[q][0][t]; y = rowtab3[q][1][t]; z = rowtab3[q][2][t]; }
     }
-    __device__ __forceinline__ float rt_w(int t) const { return rowtab4[0][VG ? t : 0].w; }
+    __device__ __forceinline__ float rt_w(int t) const {
+        static_assert(VG, "clip.w of outputs[2] rides in the row-start entry of the loaded layout only");
+        return rowtab4[0][t].w;
+    }
 };
 
 // tools/phase_times.py (-DSWR_DEBUG_PHASES, never the product): shader-clock ticks a wave spends in each phase of k_raster_c, summed
@@ -492,16 +499,30 @@ __device__ __forceinline__ int kth_set_bit32(uint32_t w, int k) {
     return base;
 }
 
+// 16 bytes at a byte offset of a raw buffer: the offset in a VGPR, the resource in SGPRs
+__device__ __forceinline__ float4 buffer_row(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+}
+
+// LINES: the batch is DebugMode.Wireframe (DrawLine records).  VG: the varyings layout (see WaveLdsC).
 // PROG / BLEND / DT >= 0: every draw of the batch has that program / blend mode / depth test (compile-time state:
 // the switches fold away); -1 = read them from the draw at run time.
 // EARLYOUT: some draw of the batch uses BlendMode.None, whose row early-out (Rasterizer.cs:520-523) is applied per chunk.
 // LDS is allocated in units of 1,280 B (tools/ubench/lds_occupancy.hip: 16 one-wave workgroups per CU up to 10,240 B, 18 up to 8,960 B,
 // 21 up to 7,680 B, 25 up to 6,400 B, 32 up to 5,120 B)
 static_assert(sizeof(WaveLdsC<false>) <= 10240 && sizeof(WaveLdsC<true>) <= 8960, "16 (18) waves per CU need <= 10,240 (8,960) B of LDS per wave");
-template <bool LINES, bool PHONG, int PROG = -1, int BLEND = -1, int DT = -1, bool EARLYOUT = false>
-__global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 4) void k_raster_c(RasterArgs a, const uint4* __restrict__ masks,
+static_assert(__builtin_offsetof(WaveLdsC<false>, stage) == 5120 && __builtin_offsetof(WaveLdsC<true>, stage) == 5120,
+              "col[256] and z[256], then stage: tests/test_lds_handoff_asm.py finds the staging stores and the stream's reads of row 0 by this offset");
+template <bool LINES, bool VG, int PROG = -1, int BLEND = -1, int DT = -1, bool EARLYOUT = false>
+__global__ __launch_bounds__(64, (VG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 4) void k_raster_c(RasterArgs a, const uint4* __restrict__ masks,
                                                                   const uint2* __restrict__ info) {
-    __shared__ WaveLdsC<PHONG> s_w;
+#ifndef SWR_RTC_PROGRAM
+    static_assert(PROG != SWR_PROG_CUSTOM, "user programs exist in run-time compiled code objects only (swr_rtc.h)");
+#endif
+    static_assert(VG || (PROG != SWR_PROG_PHONG_4POINT && PROG != SWR_PROG_DEBUG_VARYINGS && PROG != SWR_PROG_CUSTOM),
+                  "these programs read what only the loaded layout reaches");
+    __shared__ WaveLdsC<VG> s_w;
     if (batch_poisoned(a.ctrl, a.seq)) return;
     SWR_PHASE_DECL
 
@@ -529,28 +550,21 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
         return;
     }
     const uint32_t start = desc.y;
-    WaveLdsC<PHONG>& L = s_w;
-    constexpr bool VG = WaveLdsC<PHONG>::VG;
-    constexpr int RT_ROWS = WaveLdsC<PHONG>::RT_ROWS;
-    // the VOut array as a raw buffer: one 32-bit byte offset per vertex in a VGPR, the 16-byte row as the instruction's immediate
-    const __amdgpu_buffer_rsrc_t vout_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.vout, 0, (int)a.vout_bytes, 0x00020000);
-    // SWR_PROG_DEBUG_VARYINGS (its own instantiations, PROG = 4: a batch holds either only such draws or none, swr_render_mesh flushes
-    // in between): Normal of the three outputs from the side array, screen positions from the TriRec
+    WaveLdsC<VG>& L = s_w;
+    constexpr int RT_ROWS = WaveLdsC<VG>::RT_ROWS;
+    const __amdgpu_buffer_rsrc_t vout_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.vout, 0, (int)a.vout_bytes, 0x00020000);    // the VOut array as a raw buffer: a 32-bit byte offset per vertex in a VGPR
+    // SWR_PROG_DEBUG_VARYINGS (its own instantiations: a batch holds either only such draws or none, swr_render_mesh flushes in between):
+    // Normal of the three outputs from the side array, screen positions from the TriRec
     auto shade_debug = [&L, &a](int t, float w0f, float w1f, float w2f) {
-        if (!(PHONG && VG && PROG == SWR_PROG_DEBUG_VARYINGS)) return make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!(VG && PROG == SWR_PROG_DEBUG_VARYINGS)) return make_float4(0.f, 0.f, 0.f, 0.f);
         const __amdgpu_buffer_rsrc_t nrm_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.vnorm, 0, (int)(a.vout_bytes >> 2), 0x00020000);
         const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.recs, 0, 0x7ffffff0, 0x00020000);
-        const float4 q4 = L.stage[VG ? 4 : 0][t], q5 = L.stage[VG ? 5 : 0][t], q6 = L.stage[VG ? 6 : 0][t];
-        auto ld4 = [](__amdgpu_buffer_rsrc_t r, uint32_t off) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-            return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-        };
-        const float4 na = ld4(nrm_rsrc, __float_as_uint(q4.x) >> 2), nb = ld4(nrm_rsrc, __float_as_uint(q4.y) >> 2), nc = ld4(nrm_rsrc, __float_as_uint(q4.z) >> 2);
+        const float4 q4 = L.stage[ROW_VG_OFF][t], q5 = L.stage[ROW_VG_RCP][t], q6 = L.stage[ROW_VG_REC][t];
+        const float4 na = buffer_row(nrm_rsrc, __float_as_uint(q4.x) >> 2), nb = buffer_row(nrm_rsrc, __float_as_uint(q4.y) >> 2), nc = buffer_row(nrm_rsrc, __float_as_uint(q4.z) >> 2);
         const uint32_t ro = __float_as_uint(q6.x);
-        const float4 r0 = ld4(rec_rsrc, ro), r1 = ld4(rec_rsrc, ro + 16u);
+        const float4 r0 = buffer_row(rec_rsrc, ro), r1 = buffer_row(rec_rsrc, ro + 16u);
         const float sx[3] = { r0.x, r0.y, r0.z }, sy[3] = { r0.w, r1.x, r1.y };
-        float wc_clip = 0.0f;
-        if constexpr (VG) wc_clip = L.rt_w(t);
+        float wc_clip = 0.0f; if constexpr (VG) wc_clip = L.rt_w(t);
         const float inv_w = 1.0f / (float)(a.fp.width - 1), inv_h = 1.0f / (float)(a.fp.height - 1);      // Rasterizer.cs:362-363
         return shade_debug_varyings(w0f, w1f, w2f, q4.w, q5.w, wc_clip, na, nb, nc, sx, sy, inv_w, inv_h);
     };
@@ -559,23 +573,19 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
     // (swr_program.hip.h) and handed to the user's swr_fragment, inlined here: what it does not read is neither loaded nor computed
     auto shade_user = [&L, &a, vout_rsrc](int t, float w0f, float w1f, float w2f, const DrawConsts& dc, uint32_t draw, int px, int py) {
 #ifdef SWR_RTC_PROGRAM
-        if constexpr (PHONG && VG && PROG == SWR_PROG_CUSTOM) {
+        if constexpr (VG && PROG == SWR_PROG_CUSTOM) {
             const __amdgpu_buffer_rsrc_t nrm_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.vnorm, 0, (int)(a.vout_bytes >> 2), 0x00020000);
             const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.recs, 0, 0x7ffffff0, 0x00020000);
-            auto ld4 = [](__amdgpu_buffer_rsrc_t r, uint32_t off) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-                return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-            };
-            const float4 q4 = L.stage[4][t], q6 = L.stage[6][t];
+            const float4 q4 = L.stage[ROW_VG_OFF][t], q6 = L.stage[ROW_VG_REC][t];
             const uint32_t off[3] = { __float_as_uint(q4.x), __float_as_uint(q4.y), __float_as_uint(q4.z) };
             float4 clip[3], col[3], uvn[3], nrm[3], d4[3];
             float wnz[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                clip[k] = ld4(vout_rsrc, off[k]); col[k] = ld4(vout_rsrc, off[k] + 16u); uvn[k] = ld4(vout_rsrc, off[k] + 32u);
-                const float4 r3 = ld4(vout_rsrc, off[k] + 48u);
+                clip[k] = buffer_row(vout_rsrc, off[k]); col[k] = buffer_row(vout_rsrc, off[k] + 16u); uvn[k] = buffer_row(vout_rsrc, off[k] + 32u);
+                const float4 r3 = buffer_row(vout_rsrc, off[k] + 48u);
                 wnz[k] = r3.x;
-                nrm[k] = ld4(nrm_rsrc, off[k] >> 2);
+                nrm[k] = buffer_row(nrm_rsrc, off[k] >> 2);
 #ifdef SWR_USER_VERTEX      // swr_vs_out::data4 rides in VOut::wpos and in .w of the Normal side array (k_vertex_user, swr_geometry.hip.h)
                 d4[k] = make_float4(r3.y, r3.z, r3.w, nrm[k].w);
 #else                       // (k_vertex keeps Data["WorldPos"] there: not a varying of user programs)
@@ -583,7 +593,7 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
 #endif
             }
             const uint32_t ro = __float_as_uint(q6.x);
-            const float4 r0 = ld4(rec_rsrc, ro), r1 = ld4(rec_rsrc, ro + 16u);
+            const float4 r0 = buffer_row(rec_rsrc, ro), r1 = buffer_row(rec_rsrc, ro + 16u);
             const float sx[3] = { r0.x, r0.y, r0.z }, sy[3] = { r0.w, r1.x, r1.y };
             const float inv_w = 1.0f / (float)(a.fp.width - 1), inv_h = 1.0f / (float)(a.fp.height - 1);      // Rasterizer.cs:362-363
             const swr_fs_in in = interpolate_fs_in(w0f, w1f, w2f, clip, col, uvn, wnz, nrm, d4, sx, sy, inv_w, inv_h);
@@ -597,11 +607,12 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
         (void)L; (void)a; (void)vout_rsrc; (void)t; (void)w0f; (void)w1f; (void)w2f; (void)dc; (void)draw; (void)px; (void)py;
         return make_float4(0.f, 0.f, 0.f, 0.f);
     };
-    // part: 0 = everything, 1 = only the three uv rows (requested ahead of the chain replay, the texel address hangs
+    // The varyings of pair t's three outputs for Interpolate: LDS rows (staged), or buffer loads from VOut (VG).
+    // part (VG only): 0 = everything, 1 = only the three uv rows (requested ahead of the chain replay, the texel address hangs
     // on them), 2 = everything but the uv rows, which `V` already holds
     auto load_varyings = [&L, vout_rsrc](int t, bool fastdiv, int part = 0, TriVaryings V = TriVaryings()) {
-        if (VG) {
-            const float4 q4 = L.stage[VG ? 4 : 0][t], q5 = L.stage[VG ? 5 : 0][t];
+        if constexpr (VG) {
+            const float4 q4 = L.stage[ROW_VG_OFF][t], q5 = L.stage[ROW_VG_RCP][t];
             const uint32_t oa = __float_as_uint(q4.x), ob = __float_as_uint(q4.y), oc = __float_as_uint(q4.z);
             auto row = [&](uint32_t off, int r) {
                 const auto v = __builtin_amdgcn_raw_buffer_load_b128(vout_rsrc, (int)off + 16 * r, 0, 0);
@@ -613,40 +624,29 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
             if (part == 1) return V;
             V.a_cz = word(oa, 8); V.b_cz = word(ob, 8); V.c_cz = word(oc, 8);
             V.a_col = row(oa, 1); V.b_col = row(ob, 1); V.c_col = row(oc, 1);
-            if (PHONG) {
-                const float4 a3 = row(oa, 3), b3 = row(ob, 3), c3 = row(oc, 3);
-                V.a_wnz = a3.x; V.b_wnz = b3.x; V.c_wnz = c3.x;
-                V.a_wpos[0] = a3.y; V.a_wpos[1] = a3.z; V.a_wpos[2] = a3.w;
-                V.b_wpos[0] = b3.y; V.b_wpos[1] = b3.z; V.b_wpos[2] = b3.w;
-                V.c_wpos[0] = c3.y; V.c_wpos[1] = c3.z; V.c_wpos[2] = c3.w;
-            } else {
-                V.a_wnz = word(oa, 48); V.b_wnz = word(ob, 48); V.c_wnz = word(oc, 48);
-            }
-            // the divisions' operands come from LDS (staged once per pair): they do not wait for the rows above
-            V.a_r1 = q5.x; V.b_r1 = q5.y; V.c_r1 = q5.z;
-            V.a_w = q4.w; V.b_w = q5.w;
-            if constexpr (VG) V.c_w = L.rt_w(t);
-            V.fastdiv = fastdiv;
-            return V;
-        }
-        const float4 a_clip = SWR_VROW(VG ? 0 : 4, t), b_clip = SWR_VROW(VG ? 0 : 7, t), c_clip = SWR_VROW(VG ? 0 : 10, t);
-        V.a_col = SWR_VROW(VG ? 0 : 5, t); V.a_uvn = SWR_VROW(VG ? 0 : 6, t);
-        V.b_col = SWR_VROW(VG ? 0 : 8, t); V.b_uvn = SWR_VROW(VG ? 0 : 9, t);
-        V.c_col = SWR_VROW(VG ? 0 : 11, t); V.c_uvn = SWR_VROW(VG ? 0 : 12, t);
-        V.a_wnz = a_clip.x; V.b_wnz = b_clip.x; V.c_wnz = c_clip.x;
-        V.a_r1 = a_clip.y; V.b_r1 = b_clip.y; V.c_r1 = c_clip.y;
-        V.a_cz = a_clip.z; V.b_cz = b_clip.z; V.c_cz = c_clip.z;
-        V.a_w = a_clip.w; V.b_w = b_clip.w; V.c_w = c_clip.w;
-        V.fastdiv = fastdiv;
-        if (PHONG) {
-            const float4 a3 = SWR_VROW((PHONG && !VG) ? 13 : 0, t), b3 = SWR_VROW((PHONG && !VG) ? 14 : 0, t), c3 = SWR_VROW((PHONG && !VG) ? 15 : 0, t);
+            // row 3 = wn.z, then the world position, which only the 4-light program reads (what a shader does not read is not kept)
+            const float4 a3 = row(oa, 3), b3 = row(ob, 3), c3 = row(oc, 3);
+            V.a_wnz = a3.x; V.b_wnz = b3.x; V.c_wnz = c3.x;
             V.a_wpos[0] = a3.y; V.a_wpos[1] = a3.z; V.a_wpos[2] = a3.w;
             V.b_wpos[0] = b3.y; V.b_wpos[1] = b3.z; V.b_wpos[2] = b3.w;
             V.c_wpos[0] = c3.y; V.c_wpos[1] = c3.z; V.c_wpos[2] = c3.w;
+            // the divisions' operands come from LDS (staged once per pair): they do not wait for the rows above
+            V.a_r1 = q5.x; V.b_r1 = q5.y; V.c_r1 = q5.z;
+            V.a_w = q4.w; V.b_w = q5.w; V.c_w = L.rt_w(t);
+        } else {
+            (void)vout_rsrc; (void)part;
+            const float4 a_clip = L.stage[ROW_ST_OUT][t], b_clip = L.stage[ROW_ST_OUT + 3][t], c_clip = L.stage[ROW_ST_OUT + 6][t];
+            V.a_col = L.stage[ROW_ST_OUT + 1][t]; V.a_uvn = L.stage[ROW_ST_OUT + 2][t];
+            V.b_col = L.stage[ROW_ST_OUT + 4][t]; V.b_uvn = L.stage[ROW_ST_OUT + 5][t];
+            V.c_col = L.stage[ROW_ST_OUT + 7][t]; V.c_uvn = L.stage[ROW_ST_OUT + 8][t];
+            V.a_wnz = a_clip.x; V.b_wnz = b_clip.x; V.c_wnz = c_clip.x;
+            V.a_r1 = a_clip.y; V.b_r1 = b_clip.y; V.c_r1 = c_clip.y;
+            V.a_cz = a_clip.z; V.b_cz = b_clip.z; V.c_cz = c_clip.z;
+            V.a_w = a_clip.w; V.b_w = b_clip.w; V.c_w = c_clip.w;
         }
+        V.fastdiv = fastdiv;
         return V;
     };
-
     const int W = a.fp.width, H = a.fp.height;
     const int x0 = tx * SWR_TILE, y0 = ty * SWR_TILE;
 
@@ -657,7 +657,7 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
     uint4 ref_w = make_uint4(0u, 0u, 0u, 0u);
     int cnt_w = 0;
     float zb_w = 0.0f;                     // hi-Z bound of the entry (k_cover)
-    constexpr int BATCH = WaveLdsC<PHONG>::BATCH, WINDOW = WaveLdsC<PHONG>::WINDOW;
+    constexpr int BATCH = WaveLdsC<VG>::BATCH, WINDOW = WaveLdsC<VG>::WINDOW;
     if (lane < WINDOW && (uint32_t)lane < n) {
         ref_w = a.pair_refs[start + (uint32_t)lane];
         const uint2 pi = info[start + (uint32_t)lane];
@@ -738,10 +738,9 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
 #ifdef SWR_DEBUG_COUNTERS
         dbg_hidden += (unsigned)(cnt_seen - cnt);
 #endif
-        // slide the window: every lane fetches its entry of the NEXT window (24 B per candidate, consecutive lanes consecutive addresses,
-        // lines this wave touched a batch ago: L2 / L1 hits that return while this batch is rasterised).  Round 3 moved the unconsumed
-        // entries down with six ds_bpermute and fetched only the freed lanes: six LDS-crossbar round trips on the batch's critical path
-        // to save loads nobody waits for.
+        // slide the window: every lane fetches its entry of the NEXT window (lines this wave touched a batch ago: L2 / L1 hits that
+        // return while this batch is rasterised).  Round 3 moved the unconsumed entries down with six ds_bpermute and fetched only the
+        // freed lanes: six LDS-crossbar round trips on the batch's critical path to save loads nobody waits for.
         base += (uint32_t)consumed;
         {
             const uint32_t e = base + (uint32_t)lane;
@@ -766,13 +765,13 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
             const float4 f0 = fq[0], f1 = fq[1], f2 = fq[2], f3 = fq[3];
             bool fastdiv;
             float wc_stage = 0.0f;                                               // VG: clip.w of outputs[2] (rides in the row-start entry)
-            if (VG) {
+            if constexpr (VG) {
                 // only the three clip.w: the varyings themselves are fetched per fragment (load_varyings)
                 const float wa = a.vout[ref.y].clip[3], wb = a.vout[ref.z].clip[3], wc = a.vout[ref.w].clip[3];
                 fastdiv = div_operands_safe3(wa, wb, wc);
-                L.stage[VG ? 4 : 0][ci] = make_float4(__uint_as_float(ref.y << 6), __uint_as_float(ref.z << 6), __uint_as_float(ref.w << 6), wa);
-                L.stage[VG ? 5 : 0][ci] = make_float4(rcp_refined(wa), rcp_refined(wb), rcp_refined(wc), wb);
-                L.stage[VG ? 6 : 0][ci] = make_float4(__uint_as_float(ref.x << 6), 0.0f, 0.0f, 0.0f);
+                L.stage[ROW_VG_OFF][ci] = make_float4(__uint_as_float(ref.y << 6), __uint_as_float(ref.z << 6), __uint_as_float(ref.w << 6), wa);
+                L.stage[ROW_VG_RCP][ci] = make_float4(rcp_refined(wa), rcp_refined(wb), rcp_refined(wc), wb);
+                L.stage[ROW_VG_REC][ci] = make_float4(__uint_as_float(ref.x << 6), 0.0f, 0.0f, 0.0f);
                 wc_stage = wc;
             } else {
                 const float4* __restrict__ pa = reinterpret_cast<const float4*>(a.vout + ref.y);
@@ -784,10 +783,9 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
                 // ... nor is clip.y: the refined reciprocal of clip.w rides there (Interpolate's divisions, see div_core)
                 fastdiv = div_operands_safe3(a0.w, b0.w, c0.w);
                 a0.y = rcp_refined(a0.w); b0.y = rcp_refined(b0.w); c0.y = rcp_refined(c0.w);
-                SWR_VROW(VG ? 0 : 4, ci) = a0; SWR_VROW(VG ? 0 : 5, ci) = pa[1]; SWR_VROW(VG ? 0 : 6, ci) = pa[2];
-                SWR_VROW(VG ? 0 : 7, ci) = b0; SWR_VROW(VG ? 0 : 8, ci) = pb[1]; SWR_VROW(VG ? 0 : 9, ci) = pb[2];
-                SWR_VROW(VG ? 0 : 10, ci) = c0; SWR_VROW(VG ? 0 : 11, ci) = pc[1]; SWR_VROW(VG ? 0 : 12, ci) = pc[2];
-                if (PHONG) { SWR_VROW((PHONG && !VG) ? 13 : 0, ci) = a3; SWR_VROW((PHONG && !VG) ? 14 : 0, ci) = b3; SWR_VROW((PHONG && !VG) ? 15 : 0, ci) = c3; }
+                L.stage[ROW_ST_OUT][ci] = a0; L.stage[ROW_ST_OUT + 1][ci] = pa[1]; L.stage[ROW_ST_OUT + 2][ci] = pa[2];
+                L.stage[ROW_ST_OUT + 3][ci] = b0; L.stage[ROW_ST_OUT + 4][ci] = pb[1]; L.stage[ROW_ST_OUT + 5][ci] = pb[2];
+                L.stage[ROW_ST_OUT + 6][ci] = c0; L.stage[ROW_ST_OUT + 7][ci] = pc[1]; L.stage[ROW_ST_OUT + 8][ci] = pc[2];
             }
             {
                 const float t0x = f0.x, t1x = f0.y, t2x = f0.z, t0y = f0.w, t1y = f1.x, t2y = f1.y;
@@ -817,7 +815,7 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
                 // the reference's row chain from the pair's first row: the values at rows RT_ROWS, 2 RT_ROWS, ... are kept
                 float rw0 = r0.x, rw1 = r0.y, rw2 = r0.z;
 #pragma unroll
-                for (int q = 0; q < WaveLdsC<PHONG>::RT_N; ++q) {
+                for (int q = 0; q < WaveLdsC<VG>::RT_N; ++q) {
 #pragma unroll
                     for (int i = 0; i < RT_ROWS; ++i) { rw0 += b12; rw1 += b20; rw2 += b01; }            // :532-534
                     L.rt_store(q, ci, rw0, rw1, rw2, wc_stage);
@@ -944,7 +942,7 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
             }
             SWR_PHASE(4);
             const bool act = lane < cut;
-            if (VG) { if (act) Vg = load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 1); }
+            if constexpr (VG) { if (act) Vg = load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 1, Vg); }
             {   // (the head array has two spare words behind the last position: reading past the batch's end is in bounds)
                 const int hw_next = (pos + cut) >> 5;
                 hn0 = L.head[hw_next]; hn1 = L.head[hw_next + 1]; hn2 = L.head[hw_next + 2];
@@ -956,8 +954,8 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
             const DrawParams* __restrict__ cdp = a.draws + draw0;
             if (draw0 != dc_draw) {                                                       // wave-uniform: the constants live in SGPRs across chunks
                 dc_draw = draw0; dc = load_draw_consts(cdp);
-                if (!PHONG && !LINES && PROG == SWR_PROG_DUST2_LAMBERT_FOG) fast_draw = dust2_fast_applies(dc);
-                if (PHONG && !LINES && PROG == SWR_PROG_PHONG_4POINT) fast_draw = phong4_fast_applies(dc);
+                if (!VG && !LINES && PROG == SWR_PROG_DUST2_LAMBERT_FOG) fast_draw = dust2_fast_applies(dc);
+                if (VG && !LINES && PROG == SWR_PROG_PHONG_4POINT) fast_draw = phong4_fast_applies(dc);
             }
             const int f_program = PROG >= 0 ? PROG : dc.program, f_blend = BLEND >= 0 ? BLEND : dc.blend, f_dt = DT >= 0 ? DT : dc.depth_test;
             // outputs[0].Interpolate: every program but FLAT_COLOR sets it (k_setup), and the clipper's vertices always do
@@ -1011,20 +1009,20 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
                         const float4 src = make_float4(w0f, w1f, w2f, 1.0f);
 #else
                         float4 src = make_float4(0.f, 0.f, 0.f, 0.f);
-                        constexpr bool FAST = !LINES && ((!PHONG && PROG == SWR_PROG_DUST2_LAMBERT_FOG) || (PHONG && PROG == SWR_PROG_PHONG_4POINT));
-                        const TriVaryings Vs = VG ? load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 2, Vg) : load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u);
+                        constexpr bool FAST = !LINES && ((!VG && PROG == SWR_PROG_DUST2_LAMBERT_FOG) || (VG && PROG == SWR_PROG_PHONG_4POINT));
+                        const TriVaryings Vs = load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 2, Vg);
                         bool need_exact = !(FAST && fast_draw);           // wave-uniform
                         if (FAST && fast_draw) {
                             // speculate: the straight-line shader; verify: every shaded lane of the chunk took only legal shortcuts
                             bool safe;
-                            if constexpr (PHONG) src = shade_phong4_fast(cdp, dc, Vs, w0f, w1f, w2f, safe);
+                            if constexpr (VG) src = shade_phong4_fast(cdp, dc, Vs, w0f, w1f, w2f, safe);
                             else src = shade_dust2_fast(dc, Vs, w0f, w1f, w2f, safe);
                             need_exact = SWR_BALLOT(!safe) != 0ull;
                         }
                         if (need_exact)
-                            src = (PHONG && PROG == SWR_PROG_DEBUG_VARYINGS) ? shade_debug(t, w0f, w1f, w2f) :
-                                  (PHONG && PROG == SWR_PROG_CUSTOM) ? shade_user(t, w0f, w1f, w2f, dc, draw0, x0 + (pix & 15), y0 + (pix >> 4)) :
-                                  shade_fragment<PHONG>(cdp, dc, f_program, f_interp, Vs, w0f, w1f, w2f);                           // :507-509 / :321-323
+                            src = (VG && PROG == SWR_PROG_DEBUG_VARYINGS) ? shade_debug(t, w0f, w1f, w2f) :
+                                  (VG && PROG == SWR_PROG_CUSTOM) ? shade_user(t, w0f, w1f, w2f, dc, draw0, x0 + (pix & 15), y0 + (pix >> 4)) :
+                                  shade_fragment<VG>(cdp, dc, f_program, f_interp, Vs, w0f, w1f, w2f);                           // :507-509 / :321-323
 #endif
                         // triangles: W > 0 (:511); lines: W != 0 (:325)
                         if (is_line ? (src.w != 0.0f) : (src.w > 0.0f)) {
@@ -1037,11 +1035,9 @@ __global__ __launch_bounds__(64, (PHONG && PROG != SWR_PROG_PHONG_4POINT) ? 5 : 
                     e_d = d;
                     e_pass = depth_func(f_dt, d, L.z[pix]);
                     if (e_pass) {
-                        e_src = (PHONG && PROG == SWR_PROG_DEBUG_VARYINGS) ? shade_debug(t, w0f, w1f, w2f) :
-                                (PHONG && PROG == SWR_PROG_CUSTOM) ? shade_user(t, w0f, w1f, w2f, dc, draw0, x0 + (pix & 15), y0 + (pix >> 4)) :
-                                shade_fragment<PHONG>(cdp, dc, f_program, f_interp,
-                                                      VG ? load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 2, Vg) : load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u),
-                                                      w0f, w1f, w2f);
+                        e_src = (VG && PROG == SWR_PROG_DEBUG_VARYINGS) ? shade_debug(t, w0f, w1f, w2f) :
+                                (VG && PROG == SWR_PROG_CUSTOM) ? shade_user(t, w0f, w1f, w2f, dc, draw0, x0 + (pix & 15), y0 + (pix >> 4)) :
+                                shade_fragment<VG>(cdp, dc, f_program, f_interp, load_varyings(t, (dflags & SWR_FLAG_FASTDIV) != 0u, 2, Vg), w0f, w1f, w2f);
                         e_alpha = is_line ? (e_src.w != 0.0f) : (e_src.w > 0.0f);
                     }
                 }
