@@ -225,6 +225,14 @@ namespace SoftwareRenderer
         public static int TextureReadDepth(IntPtr ctx, IntPtr texture, float* depth) => swr_texture_readback_depth(ctx, texture, depth);
         [DllImport(Lib)] public static extern int swr_texture_sample_depth(IntPtr ctx, IntPtr texture, float* uvRef, int n, float* outDepthShadow);
         [DllImport(Lib)] public static extern int swr_texture_format(IntPtr ctx, IntPtr texture, out int format);
+        // mip chains (build-defined, swr.h): levels 1 .. L - 1 made on the GPU, sampled by user and post programs
+        [DllImport(Lib)] public static extern int swr_texture_generate_mipmaps(IntPtr ctx, IntPtr texture);
+        [DllImport(Lib)] public static extern int swr_texture_levels(IntPtr ctx, IntPtr texture, out int levels);
+        [DllImport(Lib)] public static extern int swr_texture_level_size(IntPtr ctx, IntPtr texture, int level, out int width, out int height);
+        [DllImport(Lib)] public static extern int swr_texture_readback_level(IntPtr ctx, IntPtr texture, int level, byte* rgba8);
+        public static int TextureReadLevel(IntPtr ctx, IntPtr texture, int level, byte* rgba8) => swr_texture_readback_level(ctx, texture, level, rgba8);
+        [DllImport(Lib)] public static extern int swr_texture_sample_lod(IntPtr ctx, IntPtr texture, float* uvLod, int n, float* outRgba);
+        [DllImport(Lib)] public static extern int swr_texture_lod(IntPtr ctx, IntPtr texture, float* grads, int n, float* outLod);
         [DllImport(Lib)] public static extern int swr_mesh_create(IntPtr ctx, Shaders.VertexInput* vertices, int nVertices, ushort* indices, int nIndices, out IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_mesh_destroy(IntPtr ctx, IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_set_state(IntPtr ctx, float nearClip, float farClip, int debugMode);
@@ -1074,6 +1082,31 @@ namespace SoftwareRenderer
         public int Format
         {
             get { SwrContext.Check(Native.swr_texture_format(SwrContext.Handle, Handle, out int f)); return f; }
+        }
+
+        /// Build-defined (the reference's Texture is one level): gives the texture its mip chain, or regenerates it -- 1 + floor(log2(max(
+        /// Width, Height))) levels, each a 2 x 2 box filter of the one before.  UpdateFrom's order, no wait for the GPU; from then on
+        /// UpdateFrom / UpdateFromPost regenerate the chain in the same call (swr_texture_generate_mipmaps).  User and post programs
+        /// read it through swr_sample_grad / swr_sample_lod / swr_sample_level; Sample and the built-in programs stay on level 0.
+        public void GenerateMipmaps()
+        {
+            SwrContext.Check(Native.swr_texture_generate_mipmaps(SwrContext.Handle, Handle));
+        }
+
+        /// 1, or the chain's length once GenerateMipmaps has run
+        public int Levels
+        {
+            get { SwrContext.Check(Native.swr_texture_levels(SwrContext.Handle, Handle, out int n)); return n; }
+        }
+
+        /// The RGBA8 texels of a level the texture has, row-major, max(1, Width >> level) * max(1, Height >> level) * 4 bytes; waits for the GPU.
+        public byte[] ReadLevel(int level)
+        {
+            SwrContext.Check(Native.swr_texture_level_size(SwrContext.Handle, Handle, level, out int w, out int h));
+            var pixels = new byte[w * h * 4];
+            fixed (byte* p = pixels)
+                SwrContext.Check(Native.TextureReadLevel(SwrContext.Handle, Handle, level, p));
+            return pixels;
         }
 
         /// The RGBA8 texels, row-major, Width * Height * 4 bytes; waits for the GPU (screenshots, tests).

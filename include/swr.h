@@ -325,6 +325,33 @@ int  swr_texture_readback_depth(swr_context* ctx, const swr_texture* tex, float*
 int  swr_texture_sample_depth(swr_context* ctx, const swr_texture* tex, const float* uv_ref, int n, float* out_depth_shadow);
 /* SWR_TEXTURE_FORMAT_* of any texture */
 int  swr_texture_format(swr_context* ctx, const swr_texture* tex, int* format);
+/* MIP CHAINS (build-defined: the reference's Texture is one level, Texture.cs:31-41; csrc/swr_deliver.hip.h, csrc/swr_device.h,
+ * DESIGN.md section 26): an RGBA8 texture -- uploaded, a render target, a pass's result -- gets the levels that let a user or post
+ * program sample it minified without aliasing.  A chain has L = 1 + floor(log2(max(w, h))) levels; level l measures max(1, w >> l) by
+ * max(1, h >> l).  Texel (x, y) of level l + 1 is, per byte channel, (p(2x, 2y) + p(x1, 2y) + p(2x, y1) + p(x1, y1) + 2) >> 2 over level
+ * l with x1 = min(2x + 1, w_l - 1), y1 = min(2y + 1, h_l - 1): a 2 x 2 box that rounds half up; an odd side >= 3 drops its last column
+ * or row.  The built-in programs and swr_sample never read a level other than 0.
+ * swr_texture_generate_mipmaps has swr_texture_update_from_frame's immediate-mode semantics: the context's recorded draws are flushed
+ * first and sample the texture as it was (one level, or the old levels); then the chain's record and the downsample kernels go onto
+ * ctx's stream; nothing waits for the GPU (swr_sync_count does not move).  The levels' memory is allocated by the first call and kept.
+ * From then on the chain is a property of the texture: swr_texture_update_from_frame / _from_post regenerate it in the same call,
+ * behind the update kernel, still without a host wait.  A texture never given a chain is updated exactly as before.  A 1 x 1 texture
+ * has a chain of one level: SWR_OK.  SWR_ERR_INVALID_ARG, nothing written, the context usable: tex NULL; a depth texture
+ * (hierarchical depth is out of scope -- the four calls below that read texels refuse one too, swr_texture_levels answers 1). */
+int  swr_texture_generate_mipmaps(swr_context* ctx, swr_texture* tex);
+/* host only: 1, or L once the chain exists */
+int  swr_texture_levels(swr_context* ctx, const swr_texture* tex, int* levels);
+/* host only: the size of any level 0 .. L - 1 of the FULL chain, generated or not; another level: SWR_ERR_INVALID_ARG */
+int  swr_texture_level_size(swr_context* ctx, const swr_texture* tex, int level, int* width, int* height);
+/* the row-major texels of a level the texture HAS (0 .. levels - 1; another: SWR_ERR_INVALID_ARG), as the kernels enqueued so far leave
+ * them; level 0 is swr_texture_readback; waits for the stream */
+int  swr_texture_readback_level(swr_context* ctx, const swr_texture* tex, int level, uint8_t* rgba8);
+/* The device lookups of a chain (csrc/swr_device.h; the program-side names are below), batched, through the texture as it is now --
+ * filter and block-linear copy included; they run on the GPU and wait for it.  n < 0 or a NULL pointer: SWR_ERR_INVALID_ARG.
+ *   swr_texture_sample_lod   n x (u, v, lod) -> n x RGBA: swr_sample_lod.  On a texture without a chain every lod gives level 0
+ *   swr_texture_lod          n x (dudx, dvdx, dudy, dvdy) -> n lods: swr_lod */
+int  swr_texture_sample_lod(swr_context* ctx, const swr_texture* tex, const float* uv_lod, int n, float* out_rgba);
+int  swr_texture_lod(swr_context* ctx, const swr_texture* tex, const float* grads, int n, float* out_lod);
 /* mesh.Vertices / mesh.Indices (ModelLoader.cs:45-47): u16 indices, 3 per triangle; an index >= n_vertices
  * is SWR_ERR_INVALID_ARG (C#: IndexOutOfRangeException at Rasterizer.cs:187) */
 int  swr_mesh_create(swr_context* ctx, const swr_vertex* vertices, int n_vertices,
@@ -439,7 +466,8 @@ int  swr_character_update(swr_context* ctx, const swr_character_params* params, 
  * porting guide): the text defines
  *     __device__ float4 swr_fragment(const swr_fs_in& in, const swr_fs_env& env);
  * `in` = Shaders.VertexOutput after Rasterizer.Interpolate (Rasterizer.cs:566-640): clip_position, color, tex_coord, normal,
- * screen_coords, barycentric, world_normal (Data["WorldNormal"]), data4 (see swr_program_create_vf); the vertex stage is Renderer.VertexShader (Renderer.cs:830-846,
+ * screen_coords, barycentric, world_normal (Data["WorldNormal"]), data4 (see swr_program_create_vf), tex_coord_grad (build-defined:
+ * (du/dx, dv/dx, du/dy, dv/dy) of tex_coord per pixel step, for swr_sample_grad below); the vertex stage is Renderer.VertexShader (Renderer.cs:830-846,
  * Interpolate = true).  `env` = the draw's uniforms, constants[64], the pixel x, y; helpers swr_sample (Texture.Sample), swr_has_texture,
  * swr_dot3, swr_lerp (this library's System.Numerics model), swr_max, swr_clamp (MathF.Max, Math.Clamp), swr_discard() (a null
  * result: W <= 0 or NaN writes nothing, Rasterizer.cs:511).  Compiled with this library's switches and its numerics model; the
@@ -468,6 +496,21 @@ int  swr_program_set_constants(swr_context* ctx, int program_id, const float* va
  *                                             texel.  Bilinear filter: the four results of the filter's 2 x 2 footprint blended as
  *                                             lerps by its fractions -- exactly 0 or 1 where all four agree (finite uv)
  *   An unbound or out-of-range slot reads float.MinValue (nothing drawn) and shadows nothing (1).
+ *   and, of any slot, its MIP CHAIN (swr_texture_generate_mipmaps) -- the levels are read when the kernel RUNS:
+ *     int    swr_texture_levels(env, slot)          1 without a chain, L with one; 0 for an unbound or out-of-range slot
+ *     float4 swr_sample_level(env, slot, uv, level) one level, clamped to [0, levels - 1]: level 0 is swr_sample; a level >= 1 applies
+ *                                             the slot's filter (nearest with wrap, or bilinear) inside that level, at that level's size
+ *     float4 swr_sample_lod(env, slot, uv, lod)     NaN or negative counts as 0, above levels - 1 as levels - 1; l0 = (int)lod,
+ *                                             f = lod - l0; f == 0 fetches level l0 alone, else c0 (1 - f) + c1 f per channel with c1
+ *                                             from level min(l0 + 1, levels - 1)
+ *     float  swr_lod(env, slot, grad)            float4 grad = (du/dx, dv/dx, du/dy, dv/dy) per pixel step: rho = the longer step in
+ *                                             level-0 texels, sqrt(max((dudx w)^2 + (dvdx h)^2, (dudy w)^2 + (dvdy h)^2)); 0 unless
+ *                                             rho > 1 (magnification, zero, NaN); else exponent(rho) + (significand(rho) - 1), a
+ *                                             piecewise-linear log2 from rho's bits -- exact at powers of two, at most 0.0861 below
+ *                                             log2(rho), never above --, clamped to levels - 1
+ *     float4 swr_sample_grad(env, slot, uv, grad)   swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad))
+ *   An unbound or out-of-range slot has 0 levels, lod 0, and samples (1, 1, 1, 1).  The fragment half gets its own gradient as
+ *   in.tex_coord_grad, the analytic derivative of in.tex_coord per pixel step (per fragment: there are no quads).
  * Slot 0 is and stays the `texture` argument of the render call.  Slots 1 .. SWR_PROGRAM_TEXTURES - 1 belong to the program, as its
  * constants do: a draw copies each slot's pointer, size and filter (the block-linear copy where the texture has one) when it is
  * RECORDED; later swr_program_set_texture and swr_texture_set_filter calls do not change recorded draws.  An unbound slot, and a slot
@@ -529,6 +572,10 @@ int  swr_program_validate_vf(const char* vertex_source, const char* fragment_sou
  *   float  swr_post_texel_depth(env, slot, x, y), swr_post_sample_depth(env, slot, uv), swr_post_shadow(env, slot, uv, ref)
  *          a DEPTH texture's words and the shadow comparison: swr_texel_depth, swr_sample_depth and swr_shadow of a user program,
  *          above; an unbound or out-of-range slot reads float.MinValue and shadows nothing (1)
+ *   int    swr_post_texture_levels(env, slot), float4 swr_post_sample_level(env, slot, uv, level), swr_post_sample_lod(env, slot, uv, lod),
+ *          float swr_post_lod(env, slot, grad)
+ *          a MIP CHAIN's lookups: swr_texture_levels, swr_sample_level, swr_sample_lod and swr_lod of a user
+ *          program, above.  A post pass has no gradient field: it knows its own scale (a half-size pass reads lod 1)
  * An unbound slot, and a slot outside 0 .. SWR_POST_TEXTURES - 1, has no texture: it samples and reads (1, 1, 1, 1), as swr_sample
  * does without a texture, and measures (0, 0).
  * What the result's x, y, z become (w is ignored, except by swr_texture_update_from_post): */

@@ -124,6 +124,7 @@ EXPORTS = [
     "swr_readback_post", "swr_present_post_async", "swr_post_device", "swr_post_device_async",
     "swr_post_set_texture", "swr_texture_update_from_post",
     "swr_texture_create_depth", "swr_texture_update_from_depth", "swr_texture_readback_depth", "swr_texture_sample_depth", "swr_texture_format",
+    "swr_texture_generate_mipmaps", "swr_texture_levels", "swr_texture_level_size", "swr_texture_readback_level", "swr_texture_sample_lod", "swr_texture_lod",
 ]
 
 _libs = {}
@@ -243,6 +244,12 @@ def load(name: str = None) -> C.CDLL:
         "swr_texture_readback_depth": (I, [P, P, P]),
         "swr_texture_sample_depth": (I, [P, P, P, I, P]),
         "swr_texture_format": (I, [P, P, C.POINTER(I)]),
+        "swr_texture_generate_mipmaps": (I, [P, P]),
+        "swr_texture_levels": (I, [P, P, C.POINTER(I)]),
+        "swr_texture_level_size": (I, [P, P, I, C.POINTER(I), C.POINTER(I)]),
+        "swr_texture_readback_level": (I, [P, P, I, P]),
+        "swr_texture_sample_lod": (I, [P, P, P, I, P]),
+        "swr_texture_lod": (I, [P, P, P, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

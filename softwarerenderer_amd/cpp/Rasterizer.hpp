@@ -116,6 +116,30 @@ public:
     }
     int Format() const { int f = -1; dev_.check(swr_texture_format(dev_.ctx(), h_, &f)); return f; }   // SWR_TEXTURE_FORMAT_*
     void SetBilinear(bool on) { dev_.check(swr_texture_set_filter(dev_.ctx(), h_, on ? 1 : 0)); }      // depth: 2 x 2 shadow lookups
+    // mip chains (build-defined, swr.h): 1 + floor(log2(max(Width, Height))) levels, each a 2 x 2 box filter of the one before, made on the
+    // GPU in UpdateFrom's order and without a wait; kept up to date by UpdateFrom / UpdateFromPost from then on.  Programs read them
+    // through swr_sample_grad / swr_sample_lod / swr_sample_level; Sample and the built-in programs stay on level 0
+    void GenerateMipmaps() { dev_.check(swr_texture_generate_mipmaps(dev_.ctx(), h_)); }
+    int Levels() const { int n = -1; dev_.check(swr_texture_levels(dev_.ctx(), h_, &n)); return n; }    // 1, or L once the chain exists
+    std::array<int, 2> LevelSize(int level) const {           // (w, h) of a level of the full chain, generated or not
+        std::array<int, 2> wh{}; dev_.check(swr_texture_level_size(dev_.ctx(), h_, level, &wh[0], &wh[1])); return wh;
+    }
+    std::vector<uint8_t> ReadLevel(int level) const {         // a level the texture has, RGBA8 row-major; waits for the GPU
+        const std::array<int, 2> wh = LevelSize(level);
+        std::vector<uint8_t> out((size_t)wh[0] * (size_t)wh[1] * 4);
+        dev_.check(swr_texture_readback_level(dev_.ctx(), h_, level, out.data()));
+        return out;
+    }
+    Vector4 SampleLod(float u, float v, float lod) const {    // swr_sample_lod as a program computes it (runs on the GPU)
+        float in[3] = { u, v, lod }; Vector4 out{};
+        dev_.check(swr_texture_sample_lod(dev_.ctx(), h_, in, 1, out.data()));
+        return out;
+    }
+    float Lod(float dudx, float dvdx, float dudy, float dvdy) const {    // swr_lod likewise
+        float in[4] = { dudx, dvdx, dudy, dvdy }; float out = 0.0f;
+        dev_.check(swr_texture_lod(dev_.ctx(), h_, in, 1, &out));
+        return out;
+    }
     std::vector<uint8_t> Read() const {       // RGBA8 row-major; waits for the GPU
         std::vector<uint8_t> out((size_t)Width * (size_t)Height * 4);
         dev_.check(swr_texture_readback(dev_.ctx(), h_, out.data()));

@@ -309,8 +309,54 @@ int texture_format_check(swr_context* c, const swr_texture* t, int format) {
                                                                               : "the texture is a depth texture (SWR_TEXTURE_FORMAT_DEPTH32F): use the swr_texture_*_depth calls");
 }
 
+// MIP CHAINS.  offset[l] of a w x h texture's chain of `levels` levels: level l's first texel in the tail
+void mip_offsets(const swr_texture* t, int levels, uint32_t* offset) {
+    uint32_t at = 0;
+    offset[0] = 0;
+    for (int l = 1; l < levels; ++l) { offset[l] = at; at += (uint32_t)mip_level_side(t->w, l) * (uint32_t)mip_level_side(t->h, l); }
+}
+// the record in front of one of t's texel arrays (d_rgba or d_blocked) as t's chain is now, on the context's stream: in front of the
+// texels' own upload at creation, behind the flushed draws (which read the old record) when a chain appears
+hipError_t texture_header_write(swr_context* c, const swr_texture* t, uint8_t* texels) {
+    TextureHeader h = {};
+    h.levels = (uint32_t)t->levels;
+    h.tail = t->levels > 1 ? t->d_tail : nullptr;
+    mip_offsets(t, t->levels, h.offset);
+    hipLaunchKernelGGL(k_texture_header, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<uint32_t*>(texels - SWR_TEXTURE_HEADER_BYTES), h);
+    return hipGetLastError();
+}
+// levels 1 .. L - 1 from the row-major level 0, on the context's stream: two levels per launch (k_mip_downsample<true>) wherever the
+// source level's sides are multiples of 4 and the alignments of its 16-byte loads and 8-byte stores hold, else one
+int mip_generate(swr_context* c, const swr_texture* t) {
+    uint32_t off[SWR_TEXTURE_MAX_LEVELS];
+    mip_offsets(t, t->levels, off);
+    uint32_t* tail = reinterpret_cast<uint32_t*>(t->d_tail);
+    for (int l = 0; l + 1 < t->levels;) {
+        const uint32_t sw = (uint32_t)mip_level_side(t->w, l), sh = (uint32_t)mip_level_side(t->h, l);
+        const uint32_t* src = l == 0 ? reinterpret_cast<const uint32_t*>(t->d_rgba) : tail + off[l];
+        const bool two = l + 2 < t->levels && (sw & 3u) == 0 && (sh & 3u) == 0 && (l == 0 || (off[l] & 3u) == 0) && (off[l + 1] & 1u) == 0;
+        if (two) {
+            const auto [grid, block] = deliver_shape(sw >> 2, sh >> 2);
+            hipLaunchKernelGGL(k_mip_downsample<true>, grid, block, 0, c->stream, src, sw, sh, tail + off[l + 1], tail + off[l + 2]);
+        } else {
+            const auto [grid, block] = deliver_shape((uint32_t)mip_level_side(t->w, l + 1), (uint32_t)mip_level_side(t->h, l + 1));
+            hipLaunchKernelGGL(k_mip_downsample<false>, grid, block, 0, c->stream, src, sw, sh, tail + off[l + 1], (uint32_t*)nullptr);
+        }
+        SWR_HIP(c, hipGetLastError());
+        l += two ? 2 : 1;
+    }
+    // Vertex programs sample textures too, and a pipelined batch runs its k_vertex_user on the front stream: the next such front end
+    // starts behind this point of the raster stream (the hand-over an unpipelined batch leaves, execute_batch).  Front ends flushed
+    // EARLIER need nothing: the raster stream already waits for each of them (front_done), so these writes are behind them
+    if (c->pipelining && c->front_stream && c->r_front_ev) {
+        SWR_HIP(c, hipEventRecord(c->r_front_ev, c->stream));
+        c->r_front_pending = true;
+    }
+    return SWR_OK;
+}
+
 // swr_texture_create / _create_target / _create_depth: w x h 4-byte texels on the context's stream, the caller's or (texels null) the
-// format's empty word: zeros, or float.MinValue
+// format's empty word: zeros, or float.MinValue.  The array's header (no chain: one level) goes in front of it on the same stream.
 int texture_create(swr_context* c, const void* texels, int w, int h, swr_texture** out, const char* what_failed, int format = SWR_TEXTURE_FORMAT_RGBA8) {
     if (w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
     if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
@@ -320,11 +366,12 @@ int texture_create(swr_context* c, const void* texels, int w, int h, swr_texture
     const float empty_depth = SWR_FLOAT_MINVALUE;
     int empty = 0;
     if (format == SWR_TEXTURE_FORMAT_DEPTH32F) memcpy(&empty, &empty_depth, 4);
-    hipError_t e = hipMalloc((void**)&t->d_rgba, bytes);
+    hipError_t e = texels_alloc(&t->d_rgba, bytes);
+    if (e == hipSuccess) e = texture_header_write(c, t, t->d_rgba);
     if (e == hipSuccess) e = texels ? hipMemcpyAsync(t->d_rgba, texels, bytes, hipMemcpyHostToDevice, c->stream)
                                     : hipMemsetD32Async((hipDeviceptr_t)t->d_rgba, empty, (size_t)w * h, c->stream);
     if (e != hipSuccess) {
-        if (t->d_rgba) (void)hipFree(t->d_rgba);
+        texels_free(t->d_rgba);
         delete t;
         c->err = std::string(what_failed) + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
@@ -390,6 +437,8 @@ int texture_update(swr_context* c, swr_texture* t, swr_context* src, const Textu
                                (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
         SWR_HIP(c, hipGetLastError());
     }
+    // a chain is a property of the texture: its levels follow the new level 0, on the same stream (a texture without one: nothing)
+    if (t->levels > 1 && (rc = mip_generate(c, t))) return rc;
     if (src != c && src->stream != c->stream) {
         // src's next raster, clear or upload may not overwrite the frame under the kernel
         if (!c->rtt_done_ev) SWR_HIP(c, hipEventCreateWithFlags(&c->rtt_done_ev, hipEventDisableTiming));
@@ -809,7 +858,8 @@ int swr_texture_set_filter(swr_context* c, swr_texture* t, int bilinear) {
     if (t->bilinear && !t->d_blocked && (t->w & 3) == 0 && (t->h & 3) == 0) {
         // the four taps of a bilinear fetch: one 64-byte line 9 times out of 16 from a block-linear copy, two lines always from the
         // row-major original (same stream as the upload and as the raster kernels that will read it)
-        SWR_HIP(c, hipMalloc((void**)&t->d_blocked, (size_t)t->w * t->h * 4));
+        SWR_HIP(c, texels_alloc(&t->d_blocked, (size_t)t->w * t->h * 4));
+        SWR_HIP(c, texture_header_write(c, t, t->d_blocked));          // (a copy of d_rgba's: the same levels, the same tail)
         const int blocks = (int)std::min<size_t>(((size_t)t->w * t->h + 255) / 256, 2048 * 8);
         hipLaunchKernelGGL(k_block_texture, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, t->w, t->h);
         SWR_HIP(c, hipGetLastError());
@@ -825,8 +875,9 @@ int swr_texture_destroy(swr_context* c, swr_texture* t) {
         for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
     for (auto& p : c->progs)                              // a later draw captures "no texture" there (recorded ones were flushed above)
         for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
-    if (t->d_rgba) (void)hipFree(t->d_rgba);
-    if (t->d_blocked) (void)hipFree(t->d_blocked);
+    texels_free(t->d_rgba);
+    texels_free(t->d_blocked);
+    if (t->d_tail) (void)hipFree(t->d_tail);
     delete t;
     return SWR_OK;
 }
@@ -862,6 +913,92 @@ int swr_texture_sample_depth(swr_context* c, const swr_texture* t, const float* 
     hipLaunchKernelGGL(k_texture_sample_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float*)d_in, n, d_out);
     SWR_HIP(c, hipGetLastError());
     SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+// ---- mip chains
+int swr_texture_generate_mipmaps(swr_context* c, swr_texture* t) {
+    SWR_ENTER(c);
+    if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
+    const int L = mip_full_levels(t->w, t->h);
+    if (L == 1) return SWR_OK;                               // 1 x 1: a chain of one level, which it has
+    // immediate-mode semantics without a host wait (swr_texture_update_from_frame's): the recorded draws go first and read the old
+    // record -- the device reads it when a kernel runs, so the order on the stream is what "earlier" and "later" mean
+    int rc = flush_locked(c); if (rc) return rc;
+    if (!t->d_tail) {
+        uint32_t off[SWR_TEXTURE_MAX_LEVELS];
+        mip_offsets(t, L, off);
+        const size_t texels = (size_t)off[L - 1] + (size_t)mip_level_side(t->w, L - 1) * (size_t)mip_level_side(t->h, L - 1);
+        SWR_HIP(c, hipMalloc((void**)&t->d_tail, texels * 4));
+    }
+    if (t->levels != L) {
+        t->levels = L;
+        SWR_HIP(c, texture_header_write(c, t, t->d_rgba));
+        if (t->d_blocked) SWR_HIP(c, texture_header_write(c, t, t->d_blocked));
+    }
+    return mip_generate(c, t);
+}
+
+int swr_texture_levels(swr_context* c, const swr_texture* t, int* levels) {
+    SWR_ENTER(c);
+    if (!t || !levels) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_levels arguments");
+    *levels = t->levels;
+    return SWR_OK;
+}
+
+int swr_texture_level_size(swr_context* c, const swr_texture* t, int level, int* w, int* h) {
+    SWR_ENTER(c);
+    if (!t || !w || !h) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_level_size arguments");
+    if (level < 0 || level >= mip_full_levels(t->w, t->h)) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the texture's full chain (0 .. floor(log2(max(w, h))))");
+    *w = mip_level_side(t->w, level); *h = mip_level_side(t->h, level);
+    return SWR_OK;
+}
+
+int swr_texture_readback_level(swr_context* c, const swr_texture* t, int level, uint8_t* rgba8) {
+    SWR_ENTER(c);
+    if (!t || !rgba8) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback_level arguments");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
+    if (level < 0 || level >= t->levels) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the levels the texture has (swr_texture_levels)");
+    if (level == 0) return texture_readback(c, t, rgba8, SWR_TEXTURE_FORMAT_RGBA8);
+    uint32_t off[SWR_TEXTURE_MAX_LEVELS];
+    mip_offsets(t, t->levels, off);
+    const size_t bytes = (size_t)mip_level_side(t->w, level) * (size_t)mip_level_side(t->h, level) * 4;
+    SWR_HIP(c, hipMemcpyAsync(rgba8, t->d_tail + (size_t)off[level] * 4, bytes, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+int swr_texture_sample_lod(swr_context* c, const swr_texture* t, const float* uv_lod, int n, float* out_rgba) {
+    SWR_ENTER(c);
+    if (!t || !uv_lod || !out_rgba || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_lod arguments");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
+    if (n == 0) return SWR_OK;
+    const size_t off_out = ((size_t)n * 12 + 15) & ~(size_t)15;
+    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 16);
+    if (rc) return rc;
+    float* d_in = c->d_scratch.as<float>();
+    float4* d_out = reinterpret_cast<float4*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
+    SWR_HIP(c, hipMemcpyAsync(d_in, uv_lod, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_texture_sample_lod, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float*)d_in, n, d_out);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+int swr_texture_lod(swr_context* c, const swr_texture* t, const float* grads, int n, float* out_lod) {
+    SWR_ENTER(c);
+    if (!t || !grads || !out_lod || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_lod arguments");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
+    if (n == 0) return SWR_OK;
+    const size_t off_out = (size_t)n * 16;
+    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 4);
+    if (rc) return rc;
+    float4* d_in = c->d_scratch.as<float4>();
+    float* d_out = reinterpret_cast<float*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
+    SWR_HIP(c, hipMemcpyAsync(d_in, grads, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_texture_lod, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipMemcpyAsync(out_lod, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     return sync_locked(c);
 }
 

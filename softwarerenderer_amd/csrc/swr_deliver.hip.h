@@ -49,6 +49,8 @@
 //                                otherwise redo a tree of up to 64 samples per tap.
 //   k_depth_to_texture<KX, KY, BLOCKED>  the DEPTH plane's KX x KY words reduced to one by a select tree (at the end of this file, with
 //                                its definition) and stored as k_frame_to_texture stores its dword: a depth texture's texel
+//   k_mip_downsample<TWO>        a texture's next mip level, or its next two, from the level before (at the end of this file, with its
+//                                definition): the one kernel here that reads texels instead of a frame
 // Two other thread mappings were measured and removed: one lane per SOURCE pixel with in-wave adds for the resolve, and four
 // consecutive pixels per thread with whole-dword stores for the 8-bit present.  DESIGN.md sections 17 and 18 have the figures.
 // No LDS, no scratch, no inline assembly; nothing here is shared with the render kernels.  KX, KY in {1, 2, 4, 8} divide the
@@ -256,5 +258,76 @@ void k_depth_to_texture(const float* __restrict__ depth, uint32_t* __restrict__ 
                   : depth_block<SWR_DEPTH_REDUCE_FIRST, KX, KY>(p, pitch);
     store_texel(words, blocked, BLOCKED, w, x, y, __float_as_uint(d));
 }
+
+// ---- mip chains (tests/mipmap_cases.py restates the downsample in numpy).  Texel (x, y) of level l + 1,
+// max(1, w_l >> 1) by max(1, h_l >> 1), is per byte channel, all four channels, in integers
+//   (p(x0, y0) + p(x1, y0) + p(x0, y1) + p(x1, y1) + 2) >> 2      taps from level l, x0 = 2x, x1 = min(2x + 1, w_l - 1), y likewise:
+// a box filter that rounds half up.  The clamp only bites where a side is already 1 (the tap is taken twice); an odd side >= 3 DROPS
+// its last column or row: no tap reaches it.  Levels are row-major words R | G << 8 | B << 16 | A << 24.
+// The four sums of a texel are taken two channels at a time: the even bytes and the odd bytes of a word each sit in 16-bit fields, where
+// four bytes and the 2 add up to at most 1022 and cannot carry into the neighbour.
+__device__ __forceinline__ uint32_t mip_average(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    const uint32_t m = 0x00ff00ffu, two = 0x00020002u;
+    const uint32_t even = (a & m) + (b & m) + (c & m) + (d & m) + two;
+    const uint32_t odd = ((a >> 8) & m) + ((b >> 8) & m) + ((c >> 8) & m) + ((d >> 8) & m) + two;
+    return ((even >> 2) & m) | (((odd >> 2) & m) << 8);
+}
+// src: level l, sw x sh texels row-major.  One thread per deliver_pixel cell, no LDS, no scratch, no stride loop.
+//   TWO = false  a cell is one texel of level l + 1 (dst1, max(1, sw >> 1) wide): four dword loads with the clamps above.  Any size.
+//   TWO = true   a cell is a 4 x 4 block of level l: four 16-byte loads, one per row -- a wave's load instruction reads 1024 contiguous
+//                bytes, eight whole 128-byte lines --, then the block's 2 x 2 texels of level l + 1 as two 8-byte stores (dst1, sw / 2
+//                wide: 512 contiguous bytes per wave and row) and, from those four ROUNDED words, its one texel of level l + 2 (dst2,
+//                sw / 4 wide): byte for byte what two TWO = false launches write, with half the launches and level l + 1 never read
+//                back.  The host launches it only where sw and sh are multiples of 4 -- no clamp bites, nothing is dropped -- and src
+//                is 16-byte, dst1 8-byte aligned (mip_generate, swr_api.hip).
+template <bool TWO>
+__global__ __launch_bounds__(SWR_RESOLVE_BLOCK_X * SWR_RESOLVE_BLOCK_Y)
+void k_mip_downsample(const uint32_t* __restrict__ src, uint32_t sw, uint32_t sh, uint32_t* __restrict__ dst1, uint32_t* __restrict__ dst2) {
+    uint32_t x, y;
+    if constexpr (TWO) {
+        const uint32_t bw = sw >> 2;
+        if (!deliver_pixel(bw, sh >> 2, x, y)) return;
+        uint4 r[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = *reinterpret_cast<const uint4*>(src + (size_t)(4u * y + (uint32_t)i) * sw + 4u * x);
+        const uint32_t t00 = mip_average(r[0].x, r[0].y, r[1].x, r[1].y), t10 = mip_average(r[0].z, r[0].w, r[1].z, r[1].w);
+        const uint32_t t01 = mip_average(r[2].x, r[2].y, r[3].x, r[3].y), t11 = mip_average(r[2].z, r[2].w, r[3].z, r[3].w);
+        uint32_t* o = dst1 + (size_t)(2u * y) * (sw >> 1) + 2u * x;
+        *reinterpret_cast<uint2*>(o) = make_uint2(t00, t10);
+        *reinterpret_cast<uint2*>(o + (sw >> 1)) = make_uint2(t01, t11);
+        dst2[(size_t)y * bw + x] = mip_average(t00, t10, t01, t11);
+    } else {
+        const uint32_t dw = (sw >> 1) > 1u ? (sw >> 1) : 1u, dh = (sh >> 1) > 1u ? (sh >> 1) : 1u;
+        if (!deliver_pixel(dw, dh, x, y)) return;
+        const uint32_t x0 = 2u * x, x1 = 2u * x + 1u < sw ? 2u * x + 1u : sw - 1u;
+        const uint32_t y0 = 2u * y, y1 = 2u * y + 1u < sh ? 2u * y + 1u : sh - 1u;
+        const uint32_t* __restrict__ r0 = src + (size_t)y0 * sw;
+        const uint32_t* __restrict__ r1 = src + (size_t)y1 * sw;
+        dst1[(size_t)y * dw + x] = mip_average(r0[x0], r0[x1], r1[x0], r1[x1]);
+    }
+}
+
+#if !defined(SWR_RTC_POST) && !defined(SWR_RTC_PROGRAM)        // (the library's own small launches: no run-time unit needs them)
+// the record in front of a texel array (TextureHeader, swr_device.h) and the zeros behind it: 64 words, one per thread.  The record
+// travels as a kernel argument, so no host buffer has to outlive the call
+__global__ __launch_bounds__(64) void k_texture_header(uint32_t* __restrict__ header_words, const TextureHeader h) {
+    const uint32_t* hw = reinterpret_cast<const uint32_t*>(&h);
+    const uint32_t i = threadIdx.x;
+    header_words[i] = i < sizeof(TextureHeader) / 4 ? hw[i] : 0u;
+}
+// swr_texture_sample_lod: uv_lod: n x (u, v, lod), out: n x RGBA, through the slot as the texture is now (filter and layout included)
+__global__ __launch_bounds__(256) void k_texture_sample_lod(TextureSlot t, const float* __restrict__ uv_lod, int n, float4* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = texture_slot_sample_lod(t, uv_lod[3 * i], uv_lod[3 * i + 1], uv_lod[3 * i + 2]);
+}
+// swr_texture_lod: grads: n x (dudx, dvdx, dudy, dvdy), out: n lods
+__global__ __launch_bounds__(256) void k_texture_lod(TextureSlot t, const float4* __restrict__ grads, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 g = grads[i];
+    out[i] = texture_slot_lod(t, g.x, g.y, g.z, g.w);
+}
+#endif
 
 }  // namespace swr

@@ -668,6 +668,81 @@ __device__ __forceinline__ float texture_slot_shadow(const TextureSlot& t, float
     return top + (bot - top) * fy;
 }
 
+// MIP CHAINS (build-defined; include/swr.h; tests/mipmap_cases.py restates these in numpy).  A slot is 16 bytes
+// and stays so, so "how many levels, and where" travels in the texture's memory: every texel array the library allocates -- row-major
+// or block-linear, either format, created from the host or as a target -- has this record in the 256 bytes in front of texel 0
+// (the rest of them zero), written on the context's stream with the texels.  Without a chain: levels 1, tail null.  With one
+// (swr_texture_generate_mipmaps): L = 1 + floor(log2(max(w, h))) levels, level l measuring max(1, w >> l) by max(1, h >> l); level 0
+// stays where the slot points, in the slot's layout, and levels 1 .. L - 1 lie row-major, one behind the other, in `tail`.
+// None of the functions below is called by a kernel of the product library; the device reads the record when a kernel runs.
+#define SWR_TEXTURE_HEADER_BYTES 256
+#define SWR_TEXTURE_MAX_LEVELS 32
+struct TextureHeader {
+    uint32_t levels;                            // 1: no chain
+    uint32_t reserved;                          // 0
+    const uint8_t* tail;                        // texel 0 of level 1; null without a chain
+    uint32_t offset[SWR_TEXTURE_MAX_LEVELS];    // offset[l], l >= 1: level l's first texel, in texels from `tail`; offset[0] = 0
+};
+static_assert(sizeof(TextureHeader) == 144 && sizeof(TextureHeader) <= SWR_TEXTURE_HEADER_BYTES && __builtin_offsetof(TextureHeader, levels) == 0 &&
+              __builtin_offsetof(TextureHeader, reserved) == 4 && __builtin_offsetof(TextureHeader, tail) == 8 && __builtin_offsetof(TextureHeader, offset) == 16,
+              "the record in front of every texel array");
+// the record of a BOUND slot
+__device__ __forceinline__ const TextureHeader* texture_slot_header(const TextureSlot& t) {
+    return reinterpret_cast<const TextureHeader*>(t.texels - SWR_TEXTURE_HEADER_BYTES);
+}
+// 0 for an unbound slot (answered before any load), else 1 or L
+__device__ __forceinline__ int texture_slot_levels(const TextureSlot& t) {
+    if (!texture_slot_bound(t)) return 0;
+    return (int)texture_slot_header(t)->levels;
+}
+// One level, `level` clamped to [0, levels - 1].  Level 0 is texture_slot_sample itself; a level >= 1 applies the slot's filter inside
+// that level, with that level's size, over its row-major texels.  (1, 1, 1, 1) from an unbound slot.
+__device__ __forceinline__ float4 texture_slot_sample_level(const TextureSlot& t, int level, float tu, float tv) {
+    if (!texture_slot_bound(t)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const TextureHeader* __restrict__ hd = texture_slot_header(t);
+    const int top = (int)hd->levels - 1;
+    level = level < 0 ? 0 : (level > top ? top : level);
+    if (level == 0) return texture_slot_sample(t, tu, tv);
+    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
+    const int wl = (w >> level) > 1 ? (w >> level) : 1, hl = (h >> level) > 1 ? (h >> level) : 1;
+    const uint8_t* __restrict__ texels = hd->tail + 4u * (size_t)hd->offset[level];
+    return t.h >= 0 ? texture_sample(texels, wl, hl, tu, tv) : texture_sample_bilinear<false>(texels, wl, hl, tu, tv);
+}
+// The level of detail of a fragment whose uv moves by (dudx, dvdx) per pixel step in x and (dudy, dvdy) in y: the longer of the two
+// steps measured in level-0 texels, rho, through a piecewise-linear log2 taken from rho's bits -- exponent + (significand - 1): exact at
+// powers of two, never above log2(rho) and never more than 0.0861 below it (the maximum of log2 m - (m - 1), at m = 1 / ln 2).  Nothing
+// fuses and nothing transcendental is called, so numpy restates it bit for bit.  !(rho > 1) -- magnification, zero, any NaN -- is 0;
+// the result is clamped to levels - 1 (+Inf too); an unbound slot gives 0.
+__device__ __forceinline__ float texture_slot_lod(const TextureSlot& t, float dudx, float dvdx, float dudy, float dvdy) {
+    if (!texture_slot_bound(t)) return 0.0f;
+    const float wf = (float)(t.w < 0 ? -t.w : t.w), hf = (float)(t.h < 0 ? -t.h : t.h);
+    const float ax = dudx * wf, ay = dvdx * hf, bx = dudy * wf, by = dvdy * hf;
+    const float rx = ax * ax + ay * ay, ry = bx * bx + by * by;
+    const float r2 = (ry > rx || ry != ry) ? ry : rx;                          // the larger; a NaN from either side
+    const float rho = sqrtf(r2);
+    if (!(rho > 1.0f)) return 0.0f;
+    const uint32_t bits = __float_as_uint(rho);
+    const int e = (int)(bits >> 23) - 127;                                     // (rho > 1: the sign bit is clear)
+    const float m = __uint_as_float((bits & 0x007fffffu) | 0x3f800000u);
+    const float lod = (float)e + (m - 1.0f);
+    const float top = (float)((int)texture_slot_header(t)->levels - 1);
+    return lod > top ? top : lod;
+}
+// Between two levels: a NaN or negative lod counts as 0, one above levels - 1 as levels - 1; l0 = (int)lod, f = lod - l0.  f == 0 fetches
+// level l0 alone; otherwise each channel is c0 (1 - f) + c1 f in the bilinear filter's form, c1 from level min(l0 + 1, levels - 1).
+__device__ __forceinline__ float4 texture_slot_sample_lod(const TextureSlot& t, float tu, float tv, float lod) {
+    if (!texture_slot_bound(t)) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const int top = (int)texture_slot_header(t)->levels - 1;
+    if (!(lod > 0.0f)) lod = 0.0f;
+    if (lod > (float)top) lod = (float)top;
+    const int l0 = (int)lod;
+    const float f = lod - (float)l0;
+    const float4 c0 = texture_slot_sample_level(t, l0, tu, tv);
+    if (f == 0.0f) return c0;
+    const float4 c1 = texture_slot_sample_level(t, l0 + 1 > top ? top : l0 + 1, tu, tv);
+    return make_float4(c0.x * (1.0f - f) + c1.x * f, c0.y * (1.0f - f) + c1.y * f, c0.z * (1.0f - f) + c1.z * f, c0.w * (1.0f - f) + c1.w * f);
+}
+
 // The per-draw block of a user-program batch (RasterArgs::user_consts, k_vertex_user's last argument): the draw's 64 captured constants,
 // then its captured texture slots 1 .. SWR_PROGRAM_TEXTURES - 1 as TextureSlot records (slot 0 is the draw's texture, in DrawParams).
 // Only run-time compiled kernels read it.  76 words, 304 bytes: every block and every record in it is 16-byte aligned.

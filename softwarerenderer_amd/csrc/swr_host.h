@@ -24,7 +24,23 @@ struct swr_texture {
     bool bilinear = false;                    // build-defined extension; the reference's Texture.Sample is nearest
     int format = SWR_TEXTURE_FORMAT_RGBA8;    // or SWR_TEXTURE_FORMAT_DEPTH32F: the same 4-byte texels, float32 depth words (d_rgba names the
                                               // row-major copy of either).  Host-side only: a slot's record does not carry it
+    // MIP CHAIN.  d_rgba and d_blocked each point at texel 0 of an allocation that begins SWR_TEXTURE_HEADER_BYTES
+    // earlier with a TextureHeader (swr_device.h): texels_alloc / texels_free.  Both headers name the same tail.
+    uint8_t* d_tail = nullptr;                // levels 1 .. L - 1, row-major, one behind the other: allocated by the first swr_texture_generate_mipmaps
+    int levels = 1;                           // what the headers say: 1, or L once the chain exists
 };
+
+// the chain a w x h texture can have: L = 1 + floor(log2(max(w, h))) levels, level l measuring max(1, w >> l) by max(1, h >> l)
+inline int mip_full_levels(int w, int h) { int L = 1; for (int m = w > h ? w : h; m > 1; m >>= 1) ++L; return L; }
+inline int mip_level_side(int side, int level) { return (side >> level) > 1 ? (side >> level) : 1; }
+// a texel array of `bytes` behind its header: *texels is texel 0, 256-byte aligned as hipMalloc's block is
+inline hipError_t texels_alloc(uint8_t** texels, size_t bytes) {
+    void* base = nullptr;
+    const hipError_t e = hipMalloc(&base, bytes + SWR_TEXTURE_HEADER_BYTES);
+    *texels = e == hipSuccess ? static_cast<uint8_t*>(base) + SWR_TEXTURE_HEADER_BYTES : nullptr;
+    return e;
+}
+inline void texels_free(uint8_t* texels) { if (texels) (void)hipFree(texels - SWR_TEXTURE_HEADER_BYTES); }
 
 namespace {
 

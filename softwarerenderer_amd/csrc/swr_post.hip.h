@@ -106,6 +106,12 @@ __device__ __forceinline__ swr::TextureSlot swr_post_slot_(const swr_post_env& e
 __device__ __forceinline__ float swr_post_texel_depth(const swr_post_env& env, int slot, int x, int y) { return swr::texture_slot_depth_texel(swr_post_slot_(env, slot), x, y); }
 __device__ __forceinline__ float swr_post_sample_depth(const swr_post_env& env, int slot, float2 uv) { return swr::texture_slot_depth_sample(swr_post_slot_(env, slot), uv.x, uv.y); }
 __device__ __forceinline__ float swr_post_shadow(const swr_post_env& env, int slot, float2 uv, float ref) { return swr::texture_slot_shadow(swr_post_slot_(env, slot), uv.x, uv.y, ref); }
+// A slot's MIP CHAIN: swr_texture_levels, swr_sample_level, swr_sample_lod and swr_lod of a user program.  A post
+// pass has no gradient field: it knows its own scale.  An unbound or out-of-range slot: 0 levels, lod 0, samples (1, 1, 1, 1).
+__device__ __forceinline__ int swr_post_texture_levels(const swr_post_env& env, int slot) { return swr::texture_slot_levels(swr_post_slot_(env, slot)); }
+__device__ __forceinline__ float4 swr_post_sample_level(const swr_post_env& env, int slot, float2 uv, int level) { return swr::texture_slot_sample_level(swr_post_slot_(env, slot), level, uv.x, uv.y); }
+__device__ __forceinline__ float4 swr_post_sample_lod(const swr_post_env& env, int slot, float2 uv, float lod) { return swr::texture_slot_sample_lod(swr_post_slot_(env, slot), uv.x, uv.y, lod); }
+__device__ __forceinline__ float swr_post_lod(const swr_post_env& env, int slot, float4 grad) { return swr::texture_slot_lod(swr_post_slot_(env, slot), grad.x, grad.y, grad.z, grad.w); }
 
 // the user's program (always inlined into k_post)
 __device__ __attribute__((always_inline)) float4 swr_post(const swr_post_in& in, const swr_post_env& env);

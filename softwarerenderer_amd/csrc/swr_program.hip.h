@@ -37,6 +37,9 @@ struct swr_fs_in {
     float3 world_normal;         // Data["WorldNormal"]: weighted sum renormalised (Rasterizer.cs:680-688)
     float4 data4;                // the user's own Vector4 key of VertexOutput.Data (swr_vs_out::data4): weighted sum with the normalised
                                  // weights, nothing else (Rasterizer.cs:690-693); zeros when the program has no vertex half
+    float4 tex_coord_grad;       // build-defined (mip chains): (du/dx, dv/dx, du/dy, dv/dy), the analytic derivative of
+                                 // tex_coord per pixel step in x and in y at this fragment -- what swr_sample_grad takes.  Per fragment:
+                                 // there are no quads and no neighbours (a chunk's fragments are compacted), so no finite differences
 };
 
 // what a fragment program closes over: the draw's uniform block, its captured constants, the pixel
@@ -87,6 +90,18 @@ __device__ __forceinline__ int2 swr_texture_size(const swr_fs_env& env, int slot
 __device__ __forceinline__ float swr_texel_depth(const swr_fs_env& env, int slot, int x, int y) { return swr::texture_slot_depth_texel(swr_slot_(env, slot), x, y); }
 __device__ __forceinline__ float swr_sample_depth(const swr_fs_env& env, int slot, float2 uv) { return swr::texture_slot_depth_sample(swr_slot_(env, slot), uv.x, uv.y); }
 __device__ __forceinline__ float swr_shadow(const swr_fs_env& env, int slot, float2 uv, float ref) { return swr::texture_slot_shadow(swr_slot_(env, slot), uv.x, uv.y, ref); }
+// A slot's MIP CHAIN (swr_texture_generate_mipmaps; definitions in swr_device.h).  The record is read when the
+// kernel runs.  An unbound or out-of-range slot: 0 levels, lod 0, samples (1, 1, 1, 1).
+//   swr_texture_levels(env, slot)             1 without a chain, L with one
+//   swr_sample_level(env, slot, uv, level)    one level, clamped to [0, levels - 1], the slot's filter applied inside it; level 0 is swr_sample
+//   swr_sample_lod(env, slot, uv, lod)        between levels (int)lod and the next: c0 (1 - f) + c1 f; one fetch where f == 0
+//   swr_lod(env, slot, grad)                  grad = (dudx, dvdx, dudy, dvdy): the piecewise-linear log2 of the longer step in texels
+//   swr_sample_grad(env, slot, uv, grad)      swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad)); grad = in.tex_coord_grad for in.tex_coord
+__device__ __forceinline__ int swr_texture_levels(const swr_fs_env& env, int slot) { return swr::texture_slot_levels(swr_slot_(env, slot)); }
+__device__ __forceinline__ float4 swr_sample_level(const swr_fs_env& env, int slot, float2 uv, int level) { return swr::texture_slot_sample_level(swr_slot_(env, slot), level, uv.x, uv.y); }
+__device__ __forceinline__ float4 swr_sample_lod(const swr_fs_env& env, int slot, float2 uv, float lod) { return swr::texture_slot_sample_lod(swr_slot_(env, slot), uv.x, uv.y, lod); }
+__device__ __forceinline__ float swr_lod(const swr_fs_env& env, int slot, float4 grad) { return swr::texture_slot_lod(swr_slot_(env, slot), grad.x, grad.y, grad.z, grad.w); }
+__device__ __forceinline__ float4 swr_sample_grad(const swr_fs_env& env, int slot, float2 uv, float4 grad) { return swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad)); }
 // the build's System.Numerics model (SWR_DOT_PAIRWISE): Vector3.Dot.  (swr_lerp, swr_max and swr_clamp: swr_user_math.hip.h)
 __device__ __forceinline__ float swr_dot3(float3 a, float3 b) { return swr::dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 // a null result: nothing is written (and under BlendMode.None the row's early-out applies)
@@ -128,6 +143,11 @@ __device__ __forceinline__ int2 swr_texture_size(const swr_vs_env& env, int slot
 __device__ __forceinline__ float swr_texel_depth(const swr_vs_env& env, int slot, int x, int y) { return swr::texture_slot_depth_texel(swr_slot_(env, slot), x, y); }
 __device__ __forceinline__ float swr_sample_depth(const swr_vs_env& env, int slot, float2 uv) { return swr::texture_slot_depth_sample(swr_slot_(env, slot), uv.x, uv.y); }
 __device__ __forceinline__ float swr_shadow(const swr_vs_env& env, int slot, float2 uv, float ref) { return swr::texture_slot_shadow(swr_slot_(env, slot), uv.x, uv.y, ref); }
+__device__ __forceinline__ int swr_texture_levels(const swr_vs_env& env, int slot) { return swr::texture_slot_levels(swr_slot_(env, slot)); }
+__device__ __forceinline__ float4 swr_sample_level(const swr_vs_env& env, int slot, float2 uv, int level) { return swr::texture_slot_sample_level(swr_slot_(env, slot), level, uv.x, uv.y); }
+__device__ __forceinline__ float4 swr_sample_lod(const swr_vs_env& env, int slot, float2 uv, float lod) { return swr::texture_slot_sample_lod(swr_slot_(env, slot), uv.x, uv.y, lod); }
+__device__ __forceinline__ float swr_lod(const swr_vs_env& env, int slot, float4 grad) { return swr::texture_slot_lod(swr_slot_(env, slot), grad.x, grad.y, grad.z, grad.w); }
+__device__ __forceinline__ float4 swr_sample_grad(const swr_vs_env& env, int slot, float2 uv, float4 grad) { return swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad)); }
 // new Shaders.VertexOutput() (Shaders.cs:26-47): zero-initialised before swr_vertex is called, Interpolate = true
 struct swr_vs_out {
     float4 clip_position;        // ClipPosition
@@ -198,6 +218,21 @@ __device__ __forceinline__ swr_fs_in interpolate_fs_in(float w0f, float w1f, flo
     // InterpolateData, Vector4 key: (a * wa + b * wb) + c * wc, no division and no renormalisation (:690-693)
     in.data4 = make_float4((d4[0].x * wa + d4[1].x * wb) + d4[2].x * wc, (d4[0].y * wa + d4[1].y * wb) + d4[2].y * wc,
                            (d4[0].z * wa + d4[1].z * wb) + d4[2].z * wc, (d4[0].w * wa + d4[1].w * wb) + d4[2].w * wc);
+    // tex_coord_grad: tex_coord = N / D with N = sum u_i b_i / w_i and D = sum b_i / w_i, b_i the screen-space barycentrics, which are
+    // linear in the pixel: their steps are the edge coefficients over the area (Rasterizer.cs:445-447, 527-534), so d(N / D) = (dN - (N / D) dD) / D
+    // with 1 / D = w.  A program that never reads the field computes none of this (the program is inlined).
+    const float area = (sx[2] - sx[0]) * (sy[1] - sy[0]) - (sy[2] - sy[0]) * (sx[1] - sx[0]);        // EdgeFunction, :411
+    const float ia = 1.0f / area;                                                                    // :427
+    const float g0x = (sy[1] - sy[2]) * ia, g0y = (sx[2] - sx[1]) * ia;
+    const float g1x = (sy[2] - sy[0]) * ia, g1y = (sx[0] - sx[2]) * ia;
+    const float g2x = (sy[0] - sy[1]) * ia, g2y = (sx[1] - sx[0]) * ia;
+    const float q0x = g0x / clip[0].w, q1x = g1x / clip[1].w, q2x = g2x / clip[2].w;
+    const float q0y = g0y / clip[0].w, q1y = g1y / clip[1].w, q2y = g2y / clip[2].w;
+    const float dx = (q0x + q1x) + q2x, dy = (q0y + q1y) + q2y;
+    const float nux = (uvn[0].x * q0x + uvn[1].x * q1x) + uvn[2].x * q2x, nuy = (uvn[0].x * q0y + uvn[1].x * q1y) + uvn[2].x * q2y;
+    const float nvx = (uvn[0].y * q0x + uvn[1].y * q1x) + uvn[2].y * q2x, nvy = (uvn[0].y * q0y + uvn[1].y * q1y) + uvn[2].y * q2y;
+    in.tex_coord_grad = make_float4((nux - in.tex_coord.x * dx) * w, (nvx - in.tex_coord.y * dx) * w,
+                                    (nuy - in.tex_coord.x * dy) * w, (nvy - in.tex_coord.y * dy) * w);
     return in;
 }
 

@@ -390,6 +390,53 @@ class Texture:
         self._dev._ck(self._dev._lib.swr_texture_sample(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
         return out.reshape(a.shape[:-1] + (4,))
 
+    def GenerateMipmaps(self):
+        """Build-defined (the reference's Texture is one level): give the texture its mip chain, or regenerate it
+        (swr_texture_generate_mipmaps).  L = 1 + floor(log2(max(Width, Height))) levels, each a 2 x 2 box filter of the one before,
+        per byte, rounding half up.  UpdateFrom's order and no wait for the GPU: draws recorded earlier see the old levels, later ones
+        the new.  From then on UpdateFrom / UpdateFromPost regenerate the chain in the same call.  Programs read it through
+        swr_sample_lod / swr_sample_grad / swr_sample_level; Texture.Sample and the built-in programs stay on level 0."""
+        self._dev._ck(self._dev._lib.swr_texture_generate_mipmaps(self._dev._ctx, self._h))
+
+    @property
+    def Levels(self) -> int:
+        """1, or L once GenerateMipmaps has run (swr_texture_levels)."""
+        n = C.c_int(-1)
+        self._dev._ck(self._dev._lib.swr_texture_levels(self._dev._ctx, self._h, C.byref(n)))
+        return n.value
+
+    def LevelSize(self, level: int) -> tuple:
+        """(width, height) of a level of the full chain, generated or not (swr_texture_level_size)."""
+        w, h = C.c_int(-1), C.c_int(-1)
+        self._dev._ck(self._dev._lib.swr_texture_level_size(self._dev._ctx, self._h, int(level), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def ReadLevel(self, level: int) -> np.ndarray:
+        """The texels of a level the texture has as (h_l, w_l, 4) uint8 (swr_texture_readback_level); waits for the GPU."""
+        w, h = self.LevelSize(level)
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        self._dev._ck(self._dev._lib.swr_texture_readback_level(self._dev._ctx, self._h, int(level), out.ctypes.data))
+        return out
+
+    def SampleLod(self, uv, lod) -> np.ndarray:
+        """swr_sample_lod as a program computes it, with the texture's filter as it is now (swr_texture_sample_lod), batched: uv of
+        shape (..., 2) and lod of shape (...) -> (..., 4); runs on the GPU."""
+        a = np.ascontiguousarray(np.asarray(uv, dtype=np.float32))
+        l = np.broadcast_to(np.asarray(lod, dtype=np.float32), a.shape[:-1])
+        flat = np.ascontiguousarray(np.concatenate([a.reshape(-1, 2), l.reshape(-1, 1)], axis=1))
+        out = np.empty((flat.shape[0], 4), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_texture_sample_lod(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
+        return out.reshape(a.shape[:-1] + (4,))
+
+    def Lod(self, grads) -> np.ndarray:
+        """swr_lod as a program computes it (swr_texture_lod), batched: grads of shape (..., 4) = (dudx, dvdx, dudy, dvdy) -> (...);
+        runs on the GPU."""
+        a = np.ascontiguousarray(np.asarray(grads, dtype=np.float32))
+        flat = a.reshape(-1, 4)
+        out = np.empty((flat.shape[0],), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_texture_lod(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
+        return out.reshape(a.shape[:-1])
+
     def SetBilinear(self, on: bool):
         """Build-defined extension (the reference samples nearest): bilinear filter with wrap for later draws."""
         self._dev._ck(self._dev._lib.swr_texture_set_filter(self._dev._ctx, self._h, 1 if on else 0))
