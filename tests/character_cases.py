@@ -14,7 +14,10 @@ variant (fused in the "fma" builds).  ProjectOnPlane is scalar C#: left to right
 
 `mut` names the mutants of tests/test_character_host.py: "plane_target_major", "slide_ray_major" (the other fold order in each fold),
 "plane_lt" (`<` for `<=` at maxDistance), "chain1_new_step" (chain 1 reading the ActualStepSize of :103), "project_dot3v"
-(ProjectOnPlane through Vector3.Dot)."""
+(ProjectOnPlane through Vector3.Dot); and those of tests/test_character_edges_host.py: "plane_cast_dead" (CheckPlane casts the rays
+that :270 leaves out), "plane_dead_le" (`<=` for `<` at :270), "slide_le" (a hit AT moveDistance counts, :362; among hits still
+strict `<`).  `probe`, when set, is told the live rays of every CheckPlane call and the operands of every MathF.Max / MathF.Min; it
+changes nothing."""
 from __future__ import annotations
 
 import dataclasses
@@ -32,6 +35,7 @@ STATE_FLOATS = ("position", "velocity", "jump_cooldown", "actual_step_size")
 STATE_INTS = ("grounded", "ceiling", "noclip")
 TRACE_FLOATS = ("ground_point", "ground_normal")
 TRACE_INTS = ("ground_found", "ceiling_found", "chain_attempts", "chain_stop")
+probe = None                             # callable(kind, *values) or None: "plane" (direction, live), "max" / "min" (a, b)
 
 
 def v3(x, y, z):
@@ -161,6 +165,8 @@ class World:
 # ============================================================================ the restatement
 def cs_max(a, b):
     """MathF.Max"""
+    if probe is not None:
+        probe("max", a, b)
     if a != b:
         return (a if b < a else b) if not np.isnan(a) else a
     return a if np.signbit(b) else b
@@ -168,6 +174,8 @@ def cs_max(a, b):
 
 def cs_min(a, b):
     """MathF.Min"""
+    if probe is not None:
+        probe("min", a, b)
     if a != b:
         return (a if a < b else b) if not np.isnan(a) else a
     return a if np.signbit(a) else b
@@ -208,8 +216,13 @@ def check_plane(w, p, pos, direction, velocity, dt, mut=()):
         ray_start = frame_start + safe - height_offset                                         # :266
         ray_end = frame_end + safe + height_offset
         ray_dir = ray_end - ray_start
-        live.append(not (R.dot3v(ray_dir, ray_dir, w.order) < F32(0.0001)))                    # :270
+        sqr = R.dot3v(ray_dir, ray_dir, w.order)
+        live.append(not (sqr <= F32(0.0001) if "plane_dead_le" in mut else sqr < F32(0.0001)))  # :270
         origins.append(ray_start); dirs.append(R.normalize3v(ray_dir, w.order))                # :273
+    if probe is not None:
+        probe("plane", direction, list(live))
+    if "plane_cast_dead" in mut:
+        live = [True] * 9
     hits = w.cast(np.asarray(origins), np.asarray(dirs))
     best_point, best_normal, best_distance, any_hit = v3(NEG_INF, NEG_INF, NEG_INF), v3(0, 1, 0), R.FLT_MAX, False
     n_t = len(w.targets)
@@ -250,7 +263,7 @@ def move_with_slide(w, p, ring, current, desired, step_now, tr, chain, depth=0, 
     order = [(r, t) for r in range(n_r) for t in range(n_t)] if "slide_ray_major" in mut else [(r, t) for t in range(n_t) for r in range(n_r)]
     for r, t in order:
         found, dist, _, normal = hits[t]
-        if found[r] and dist[r] < nearest:                                                     # :362
+        if found[r] and (dist[r] < nearest or ("slide_le" in mut and not collision and dist[r] <= nearest)):     # :362
             nearest, hit_normal, collision = dist[r], R.normalize3v(normal[r], w.order), True  # :365
     if not collision:
         tr["chain_stop"][chain] = 1

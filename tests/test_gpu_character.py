@@ -18,10 +18,10 @@ after EVERY step every field of the state and of the trace is compared -- intege
     byte for byte, with and without the trace, on a context of its own whose key buffer grows under the call;
   - arguments: the INVALID_ARG / UNSUPPORTED cases and the empty calls; the Python class against the restatement.
 
-Device mutants (one change in a scratch copy of csrc/, the product library rebuilt, this file run once on it) have NOT been run for
-this file: the ones the restatement's host mutants correspond to are the serial position in fold_keys (TARGET_MAJOR swapped in
-either fold), `<` for `<=` under INCLUSIVE, and `w.step_now = w.step_in` dropped from k_char_planes; tests/test_character_host.py
-records which cases each turns red in the restatement, and every one of those cases runs here."""
+Device mutants (one change in a scratch copy of csrc/, built as a library of its own, this file and
+tests/test_gpu_character_edges.py run once on it): the table in profiles/r21_character_edges.md says which tests each turns red.  Of
+this file's, test_ties catches TARGET_MAJOR swapped in either fold and test_a_hit_at_exactly_max_distance `<` for `<=` under
+INCLUSIVE; `w.step_now = w.step_in` dropped from k_char_planes changes nothing (k_char_begin stores the same value)."""
 import ctypes as C
 import os
 
