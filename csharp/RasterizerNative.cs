@@ -233,6 +233,18 @@ namespace SoftwareRenderer
         public static int TextureReadLevel(IntPtr ctx, IntPtr texture, int level, byte* rgba8) => swr_texture_readback_level(ctx, texture, level, rgba8);
         [DllImport(Lib)] public static extern int swr_texture_sample_lod(IntPtr ctx, IntPtr texture, float* uvLod, int n, float* outRgba);
         [DllImport(Lib)] public static extern int swr_texture_lod(IntPtr ctx, IntPtr texture, float* grads, int n, float* outLod);
+        // cube maps (build-defined, swr.h): six faces in one n x 6 n texture, looked up by direction in user and post programs
+        [DllImport(Lib)] public static extern int swr_texture_create_cube(IntPtr ctx, byte* rgba8OrNull, int n, out IntPtr texture);
+        [DllImport(Lib)] public static extern int swr_texture_create_cube_depth(IntPtr ctx, float* depthOrNull, int n, out IntPtr texture);
+        [DllImport(Lib)] public static extern int swr_texture_is_cube(IntPtr ctx, IntPtr texture, out int nOr0);
+        [DllImport(Lib)] public static extern int swr_texture_update_face_from_frame(IntPtr ctx, IntPtr texture, int face, IntPtr sourceCtx, int kx, int ky, int alphaMode);
+        [DllImport(Lib)] public static extern int swr_texture_update_face_from_depth(IntPtr ctx, IntPtr texture, int face, IntPtr sourceCtx, int kx, int ky, int reduce);
+        [DllImport(Lib)] public static extern int swr_texture_update_face_from_post(IntPtr ctx, IntPtr texture, int face, IntPtr sourceCtx, int postId, int kx, int ky, int alphaMode);
+        [DllImport(Lib)] public static extern int swr_texture_readback_face(IntPtr ctx, IntPtr texture, int face, int level, void* texels);
+        [DllImport(Lib)] public static extern int swr_cube_face_view(int face, float* eye, float* view);
+        [DllImport(Lib)] public static extern int swr_texture_cube_face(IntPtr ctx, float* dirs, int n, int* outFace, float* outSt);
+        [DllImport(Lib)] public static extern int swr_texture_sample_cube(IntPtr ctx, IntPtr texture, float* dirLod, int n, float* outRgba);
+        [DllImport(Lib)] public static extern int swr_texture_sample_cube_depth(IntPtr ctx, IntPtr texture, float* dirRef, int n, float* outDepthShadow);
         [DllImport(Lib)] public static extern int swr_mesh_create(IntPtr ctx, Shaders.VertexInput* vertices, int nVertices, ushort* indices, int nIndices, out IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_mesh_destroy(IntPtr ctx, IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_set_state(IntPtr ctx, float nearClip, float farClip, int debugMode);
@@ -1050,6 +1062,51 @@ namespace SoftwareRenderer
         }
 
         public enum DepthReduce { Max = 0, Min = 1, First = 2 }               // SWR_DEPTH_REDUCE_*
+
+        /// Cube maps (build-defined: the reference addresses a texture by uv alone and clears to one colour, Renderer.cs:413).  A cube
+        /// of side n is a texture n wide and 6 n high, face f (0..5 = +X, -X, +Y, -Y, +Z, -Z) in rows [f n, (f + 1) n).  `rgba8`: six
+        /// faces of n x n, face-major, or null for zeros (a target for UpdateFaceFrom).  Programs read it through swr_sample_cube.
+        public static TextureNative CreateCube(int n, byte[] rgba8 = null)
+        {
+            if (rgba8 != null && rgba8.Length != 6 * n * n * 4) throw new ArgumentException("rgba8 must hold 6 * n * n * 4 bytes");
+            fixed (byte* p = rgba8)
+            {
+                SwrContext.Check(Native.swr_texture_create_cube(SwrContext.Handle, p, n, out IntPtr h));
+                return new TextureNative(n, 6 * n, h);
+            }
+        }
+
+        /// A depth cube: float.MinValue everywhere until UpdateFaceFromDepth fills it; swr_shadow_cube / swr_sample_cube_depth read it.
+        public static TextureNative CreateCubeDepth(int n, float[] depth = null)
+        {
+            if (depth != null && depth.Length != 6 * n * n) throw new ArgumentException("depth must hold 6 * n * n floats");
+            fixed (float* p = depth)
+            {
+                SwrContext.Check(Native.swr_texture_create_cube_depth(SwrContext.Handle, p, n, out IntPtr h));
+                return new TextureNative(n, 6 * n, h);
+            }
+        }
+
+        /// UpdateFrom into one face of a cube: the frame measures n * kx by n * ky (swr_texture_update_face_from_frame).
+        public void UpdateFaceFrom(int face, int kx = 1, int ky = 1, bool keepAlpha = false, IntPtr sourceContext = default)
+        {
+            SwrContext.Check(Native.swr_texture_update_face_from_frame(SwrContext.Handle, Handle, face, sourceContext, kx, ky, keepAlpha ? 1 : 0));
+        }
+
+        /// UpdateFromDepth into one face of a depth cube (swr_texture_update_face_from_depth).
+        public void UpdateFaceFromDepth(int face, int kx = 1, int ky = 1, DepthReduce reduce = DepthReduce.Max, IntPtr sourceContext = default)
+        {
+            SwrContext.Check(Native.swr_texture_update_face_from_depth(SwrContext.Handle, Handle, face, sourceContext, kx, ky, (int)reduce));
+        }
+
+        /// Matrix4x4.CreateLookAt of a face's camera at `eye` (swr_cube_face_view): with CreatePerspectiveFieldOfView(pi / 2, 1, near,
+        /// far) the pixel whose centre lies in direction d from eye is the texel swr_sample_cube reads for d.
+        public static Matrix4x4 CubeFaceView(int face, Vector3 eye)
+        {
+            Matrix4x4 view;
+            if (Native.swr_cube_face_view(face, (float*)&eye, (float*)&view) != 0) throw new ArgumentOutOfRangeException(nameof(face));
+            return view;
+        }
 
         /// Each texel becomes ONE word of its kx x ky block of the frame's depth plane (Width * kx by Height * ky pixels): the
         /// nearest under the default LessEqual test (Max), the farthest (Min) or the top-left one (First).  Otherwise UpdateFrom's

@@ -352,6 +352,50 @@ int  swr_texture_readback_level(swr_context* ctx, const swr_texture* tex, int le
  *   swr_texture_lod          n x (dudx, dvdx, dudy, dvdy) -> n lods: swr_lod */
 int  swr_texture_sample_lod(swr_context* ctx, const swr_texture* tex, const float* uv_lod, int n, float* out_rgba);
 int  swr_texture_lod(swr_context* ctx, const swr_texture* tex, const float* grads, int n, float* out_lod);
+/* CUBE MAPS (build-defined: the reference addresses a texture by uv and clears to one colour, Renderer.cs:413; csrc/swr_device.h,
+ * DESIGN.md section 27): six square faces looked up by a DIRECTION -- a skybox, a reflection, a point light's shadow.  A cube of side n
+ * IS a texture n wide and 6 n high: face f (0..5 = +X, -X, +Y, -Y, +Z, -Z) occupies rows [f n, (f + 1) n), in either format.  Every
+ * other call on it -- readback, set_filter, format, destroy, binding to a draw, a program or a post slot, swr_sample, swr_texel -- sees
+ * that n x 6 n texture.  The block-linear copy follows its rule (made when n % 4 == 0; face f starts f n^2 texels into it as well).
+ * The lookup (texture_cube_face, csrc/swr_device.h), ax = |x|, ay = |y|, az = |z|: any NaN or Inf, or all three zero: face 0,
+ * s = t = 0.5.  Else X major when ax >= ay && ax >= az (ma = ax, face = x < 0 ? 1 : 0, sc = x < 0 ? -z : z, tc = -y); else Y major when
+ * ay >= az (ma = ay, face = y < 0 ? 3 : 2, sc = x, tc = y < 0 ? z : -z); else Z major (ma = az, face = z < 0 ? 5 : 4,
+ * sc = z < 0 ? x : -x, tc = -y); -0 counts as positive.  s = (sc / ma + 1) / 2, t = (tc / ma + 1) / 2, exactly 0 or 1 on an edge.
+ * A right-handed world seen from inside: face f is the image of a camera along the face's axis with up +Y (+Y: up +Z, -Y: up -Z)
+ * under the screen mapping of Rasterizer.cs:383-386 -- swr_cube_face_view is that camera.
+ * Nearest filter: texel (min((int)(s n), n - 1), min((int)(t n), n - 1)) of the face.  Bilinear: X = s n - 0.5, x0 = floor(X),
+ * fx = X - x0, taps x0 and x0 + 1 each CLAMPED to [0, n - 1], y likewise, blended as swr_sample blends: the footprint stays inside the
+ * face.  Filtering across face edges is out of scope: a seam of up to one texel of clamped colour is the defined result.
+ * rgba8 / depth: six faces of n x n, face-major (NULL: zeros, or float.MinValue).  n < 1, or 6 n^2 >= 2^30: SWR_ERR_INVALID_ARG. */
+int  swr_texture_create_cube(swr_context* ctx, const uint8_t* rgba8_or_null, int n, swr_texture** out);
+int  swr_texture_create_cube_depth(swr_context* ctx, const float* depth_or_null, int n, swr_texture** out);
+/* host only: n of a texture created by the two calls above, 0 of any other */
+int  swr_texture_is_cube(swr_context* ctx, const swr_texture* tex, int* n_or_0);
+/* One face from a frame, a frame's depth or a post pass: swr_texture_update_from_frame / _from_depth / _from_post with the face's
+ * n x n texels as the destination -- the same kernels, the same arguments otherwise, the same contract: one kernel on ctx's stream, no
+ * host wait (swr_sync_count does not move), immediate-mode order against the draws around it, two events between two contexts; a
+ * cube with a mip chain has it regenerated in the same call.  The frame must measure n kx by n ky.  SWR_ERR_INVALID_ARG, nothing
+ * written, the context usable: tex NULL; not a cube; face outside 0 .. 5; the other format; factors outside {1, 2, 4, 8}; a frame of
+ * another size; and what the whole-texture calls refuse.  SWR_ERR_UNSUPPORTED: a source that holds a band, or on another device. */
+int  swr_texture_update_face_from_frame(swr_context* ctx, swr_texture* tex, int face, swr_context* src, int kx, int ky, int alpha_mode);
+int  swr_texture_update_face_from_depth(swr_context* ctx, swr_texture* tex, int face, swr_context* src, int kx, int ky, int reduce);
+int  swr_texture_update_face_from_post(swr_context* ctx, swr_texture* tex, int face, swr_context* src, int post_id, int kx, int ky, int alpha_mode);
+/* one face of a level the cube has (0 .. levels - 1), (n >> level)^2 RGBA8 texels or depth words, row-major; waits for the stream */
+int  swr_texture_readback_face(swr_context* ctx, const swr_texture* tex, int face, int level, void* out);
+/* host only, no context: Matrix4x4.CreateLookAt(eye, eye + axis, up) of face's camera, float32, row-major as the draw calls take it.
+ * With CreatePerspectiveFieldOfView(pi / 2, 1, near, far) the pixel whose centre lies in direction d from eye is the texel the lookup
+ * names for d.  face outside 0 .. 5 or a NULL pointer: SWR_ERR_INVALID_ARG */
+int  swr_cube_face_view(int face, const float eye[3], float view[16]);
+/* The device lookups, batched, through the texture as it is now; they run on the GPU and wait for it.
+ *   swr_texture_cube_face          n x (x, y, z) -> n faces, n x (s, t)
+ *   swr_texture_sample_cube        n x (x, y, z, lod) -> n x RGBA: swr_sample_cube_lod (lod 0: swr_sample_cube); an RGBA8 cube
+ *   swr_texture_sample_cube_depth  n x (x, y, z, ref) -> n x (word, shadow): swr_sample_cube_depth, swr_shadow_cube; a depth cube
+ * MIP CHAINS: swr_texture_generate_mipmaps accepts an RGBA8 cube whose n is a power of two: L = 1 + log2(n) levels, level l the
+ * (n >> l) x 6 (n >> l) atlas -- the first L levels of the n x 6 n texture's chain, since no 2 x 2 box straddles a face.
+ * swr_texture_levels, _level_size and _readback_level answer for it.  Another n: SWR_ERR_UNSUPPORTED, nothing written. */
+int  swr_texture_cube_face(swr_context* ctx, const float* dirs, int n, int* out_face, float* out_st);
+int  swr_texture_sample_cube(swr_context* ctx, const swr_texture* tex, const float* dir_lod, int n, float* out_rgba);
+int  swr_texture_sample_cube_depth(swr_context* ctx, const swr_texture* tex, const float* dir_ref, int n, float* out_depth_shadow);
 /* mesh.Vertices / mesh.Indices (ModelLoader.cs:45-47): u16 indices, 3 per triangle; an index >= n_vertices
  * is SWR_ERR_INVALID_ARG (C#: IndexOutOfRangeException at Rasterizer.cs:187) */
 int  swr_mesh_create(swr_context* ctx, const swr_vertex* vertices, int n_vertices,
@@ -511,6 +555,15 @@ int  swr_program_set_constants(swr_context* ctx, int program_id, const float* va
  *     float4 swr_sample_grad(env, slot, uv, grad)   swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad))
  *   An unbound or out-of-range slot has 0 levels, lod 0, and samples (1, 1, 1, 1).  The fragment half gets its own gradient as
  *   in.tex_coord_grad, the analytic derivative of in.tex_coord per pixel step (per fragment: there are no quads).
+ *   and, of a slot that holds a CUBE MAP (swr_texture_create_cube), by a float3 direction of any length:
+ *     void   swr_cube_face(dir, &face, &uv)         the face (int) and where in it (float2 in [0, 1]^2, v downwards)
+ *     float4 swr_sample_cube(env, slot, dir)        the slot's filter inside the face (bilinear: taps clamped to the face)
+ *     float4 swr_sample_cube_level(env, slot, dir, level), swr_sample_cube_lod(env, slot, dir, lod)   inside the cube's chain
+ *     float4 swr_cube_texel(env, slot, face, x, y)  one texel; face clamped to [0, 5], x and y to the face
+ *     int    swr_cube_size(env, slot)               n
+ *     float  swr_sample_cube_depth(env, slot, dir)  a depth cube's word, always nearest
+ *     float  swr_shadow_cube(env, slot, dir, ref)   swr_shadow by direction: a point light's shadow with dir = world - light
+ *   A slot that is unbound, out of range or not n by 6 n is not a cube: (1, 1, 1, 1), float.MinValue, shadow 1, size 0 -- no load.
  * Slot 0 is and stays the `texture` argument of the render call.  Slots 1 .. SWR_PROGRAM_TEXTURES - 1 belong to the program, as its
  * constants do: a draw copies each slot's pointer, size and filter (the block-linear copy where the texture has one) when it is
  * RECORDED; later swr_program_set_texture and swr_texture_set_filter calls do not change recorded draws.  An unbound slot, and a slot
@@ -576,6 +629,9 @@ int  swr_program_validate_vf(const char* vertex_source, const char* fragment_sou
  *          float swr_post_lod(env, slot, grad)
  *          a MIP CHAIN's lookups: swr_texture_levels, swr_sample_level, swr_sample_lod and swr_lod of a user
  *          program, above.  A post pass has no gradient field: it knows its own scale (a half-size pass reads lod 1)
+ *   swr_post_cube_face, swr_post_sample_cube, swr_post_sample_cube_level, swr_post_sample_cube_lod, swr_post_cube_texel,
+ *          swr_post_cube_size, swr_post_sample_cube_depth, swr_post_shadow_cube
+ *          a CUBE MAP's lookups: the functions of a user program without the prefix, above
  * An unbound slot, and a slot outside 0 .. SWR_POST_TEXTURES - 1, has no texture: it samples and reads (1, 1, 1, 1), as swr_sample
  * does without a texture, and measures (0, 0).
  * What the result's x, y, z become (w is ignored, except by swr_texture_update_from_post): */

@@ -125,6 +125,9 @@ EXPORTS = [
     "swr_post_set_texture", "swr_texture_update_from_post",
     "swr_texture_create_depth", "swr_texture_update_from_depth", "swr_texture_readback_depth", "swr_texture_sample_depth", "swr_texture_format",
     "swr_texture_generate_mipmaps", "swr_texture_levels", "swr_texture_level_size", "swr_texture_readback_level", "swr_texture_sample_lod", "swr_texture_lod",
+    "swr_texture_create_cube", "swr_texture_create_cube_depth", "swr_texture_is_cube", "swr_texture_update_face_from_frame",
+    "swr_texture_update_face_from_depth", "swr_texture_update_face_from_post", "swr_texture_readback_face", "swr_cube_face_view",
+    "swr_texture_cube_face", "swr_texture_sample_cube", "swr_texture_sample_cube_depth",
 ]
 
 _libs = {}
@@ -250,6 +253,17 @@ def load(name: str = None) -> C.CDLL:
         "swr_texture_readback_level": (I, [P, P, I, P]),
         "swr_texture_sample_lod": (I, [P, P, P, I, P]),
         "swr_texture_lod": (I, [P, P, P, I, P]),
+        "swr_texture_create_cube": (I, [P, P, I, C.POINTER(P)]),
+        "swr_texture_create_cube_depth": (I, [P, P, I, C.POINTER(P)]),
+        "swr_texture_is_cube": (I, [P, P, C.POINTER(I)]),
+        "swr_texture_update_face_from_frame": (I, [P, P, I, P, I, I, I]),
+        "swr_texture_update_face_from_depth": (I, [P, P, I, P, I, I, I]),
+        "swr_texture_update_face_from_post": (I, [P, P, I, P, I, I, I, I]),
+        "swr_texture_readback_face": (I, [P, P, I, I, P]),
+        "swr_cube_face_view": (I, [I, P, P]),
+        "swr_texture_cube_face": (I, [P, P, I, P, P]),
+        "swr_texture_sample_cube": (I, [P, P, P, I, P]),
+        "swr_texture_sample_cube_depth": (I, [P, P, P, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -140,6 +140,50 @@ public:
         dev_.check(swr_texture_lod(dev_.ctx(), h_, in, 1, &out));
         return out;
     }
+    // cube maps (build-defined, swr.h): a cube of side n is a texture n wide and 6 n high, face f (0..5 = +X, -X, +Y, -Y, +Z, -Z) in rows
+    // [f n, (f + 1) n); programs read it through swr_sample_cube / swr_shadow_cube.  The factories are below (Cube, CubeTarget, CubeDepth)
+    static Texture Cube(const Device& dev, const uint8_t* faces_rgba8, int n) { return Texture(dev, n, faces_rgba8, CubeTag{}); }   // six faces of n x n, face-major
+    static Texture CubeTarget(const Device& dev, int n) { return Texture(dev, n, (const uint8_t*)nullptr, CubeTag{}); }                // zeros, for UpdateFaceFrom
+    static Texture CubeDepth(const Device& dev, int n, const float* words = nullptr) { return Texture(dev, n, words, CubeTag{}); }      // float.MinValue without words
+    // Matrix4x4.CreateLookAt of a face's camera at `eye` (host only): with CreatePerspectiveFieldOfView(pi / 2, 1, near, far) the pixel
+    // whose centre lies in direction d from eye is the texel swr_sample_cube reads for d
+    static std::array<float, 16> CubeFaceView(int face, const float eye[3]) {
+        std::array<float, 16> view{};
+        if (swr_cube_face_view(face, eye, view.data()) != SWR_OK) throw std::invalid_argument("face must be 0 .. 5");
+        return view;
+    }
+    // swr_cube_face as a program computes it (runs on the GPU): the face of a direction and (s, t) in it
+    static int CubeFace(const Device& dev, float x, float y, float z, float st[2]) {
+        float in[3] = { x, y, z }; int face = -1;
+        dev.check(swr_texture_cube_face(dev.ctx(), in, 1, &face, st));
+        return face;
+    }
+    int IsCube() const { int n = -1; dev_.check(swr_texture_is_cube(dev_.ctx(), h_, &n)); return n; }   // n, or 0
+    void UpdateFaceFrom(int face, int kx = 1, int ky = 1, bool keep_alpha = false, swr_context* source = nullptr) {
+        dev_.check(swr_texture_update_face_from_frame(dev_.ctx(), h_, face, source, kx, ky, keep_alpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
+    }
+    void UpdateFaceFromDepth(int face, int kx = 1, int ky = 1, int reduce = SWR_DEPTH_REDUCE_MAX, swr_context* source = nullptr) {
+        dev_.check(swr_texture_update_face_from_depth(dev_.ctx(), h_, face, source, kx, ky, reduce));
+    }
+    void UpdateFaceFromPost(int face, int post_id, int kx = 1, int ky = 1, bool keep_alpha = false, swr_context* source = nullptr) {
+        dev_.check(swr_texture_update_face_from_post(dev_.ctx(), h_, face, source, post_id, kx, ky, keep_alpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
+    }
+    std::vector<uint8_t> ReadFace(int face, int level = 0) const {      // (n >> level)^2 texels of 4 bytes: RGBA8, or depth words; waits for the GPU
+        const size_t n = (size_t)(Width >> level);
+        std::vector<uint8_t> out(n * n * 4);
+        dev_.check(swr_texture_readback_face(dev_.ctx(), h_, face, level, out.data()));
+        return out;
+    }
+    Vector4 SampleCube(float x, float y, float z, float lod = 0.0f) const {   // swr_sample_cube_lod as a program computes it (runs on the GPU)
+        float in[4] = { x, y, z, lod }; Vector4 out{};
+        dev_.check(swr_texture_sample_cube(dev_.ctx(), h_, in, 1, out.data()));
+        return out;
+    }
+    std::array<float, 2> SampleCubeDepth(float x, float y, float z, float ref) const {   // (word, shadow): swr_sample_cube_depth, swr_shadow_cube
+        float in[4] = { x, y, z, ref }; std::array<float, 2> out{};
+        dev_.check(swr_texture_sample_cube_depth(dev_.ctx(), h_, in, 1, out.data()));
+        return out;
+    }
     std::vector<uint8_t> Read() const {       // RGBA8 row-major; waits for the GPU
         std::vector<uint8_t> out((size_t)Width * (size_t)Height * 4);
         dev_.check(swr_texture_readback(dev_.ctx(), h_, out.data()));
@@ -156,6 +200,13 @@ public:
 private:
     Texture(const Device& dev, int width, int height) : dev_(dev), Width(width), Height(height) {
         dev_.check(swr_texture_create_target(dev_.ctx(), width, height, &h_));
+    }
+    struct CubeTag {};
+    Texture(const Device& dev, int n, const uint8_t* faces, CubeTag) : dev_(dev), Width(n), Height(6 * n) {
+        dev_.check(swr_texture_create_cube(dev_.ctx(), faces, n, &h_));
+    }
+    Texture(const Device& dev, int n, const float* words, CubeTag) : dev_(dev), Width(n), Height(6 * n) {
+        dev_.check(swr_texture_create_cube_depth(dev_.ctx(), words, n, &h_));
     }
     struct DepthTag {};
     Texture(const Device& dev, int width, int height, const float* depth, DepthTag) : dev_(dev), Width(width), Height(height) {

@@ -383,7 +383,9 @@ int texture_create(swr_context* c, const void* texels, int w, int h, swr_texture
 // What a texture is updated from: src's colour plane (swr_texture_update_from_frame), program post_id of src between the resolve and
 // the quantiser (_from_post), or src's depth plane (_from_depth).  mode: the alpha mode, or the depth reduction.
 enum UpdateFrom { FROM_FRAME, FROM_POST, FROM_DEPTH };
-struct TextureUpdate { UpdateFrom from; int kx, ky, mode, post_id; };
+// by_face: one face of a cube (swr_texture_update_face_from_*), `face` as the caller gave it -- the same kernels
+// over the face's n x n texels, which start face * n * n texels into the row-major array and into the block-linear copy alike
+struct TextureUpdate { UpdateFrom from; int kx, ky, mode, post_id; int face = 0; bool by_face = false; };
 
 // Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream (but a first use or growth of src's resolved
 // plane, launch_post_over).
@@ -391,6 +393,10 @@ int texture_update(swr_context* c, swr_texture* t, swr_context* src, const Textu
     const int kx = u.kx, ky = u.ky;
     const bool posted = u.from == FROM_POST, from_depth = u.from == FROM_DEPTH;
     if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
+    if (u.by_face && !t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube, swr_texture_create_cube_depth)");
+    if (u.by_face && (u.face < 0 || u.face > 5)) return fail(c, SWR_ERR_INVALID_ARG, "face must be 0 .. 5 (+X, -X, +Y, -Y, +Z, -Z)");
+    const int tw = t->w, th = u.by_face ? t->w : t->h;                             // what the kernel writes: the texture, or one face of it
+    const size_t first = u.by_face ? (size_t)u.face * (size_t)t->w * (size_t)t->w : 0;   // its first texel, in texels
     if (!from_depth && u.mode != SWR_TEXTURE_ALPHA_OPAQUE && u.mode != SWR_TEXTURE_ALPHA_KEEP)
         return fail(c, SWR_ERR_INVALID_ARG, "alpha_mode must be SWR_TEXTURE_ALPHA_OPAQUE (0) or SWR_TEXTURE_ALPHA_KEEP (1)");
     if (from_depth && u.mode != SWR_DEPTH_REDUCE_MAX && u.mode != SWR_DEPTH_REDUCE_MIN && u.mode != SWR_DEPTH_REDUCE_FIRST)
@@ -400,8 +406,9 @@ int texture_update(swr_context* c, swr_texture* t, swr_context* src, const Textu
     if (src->device != c->device) return fail(c, SWR_ERR_UNSUPPORTED, "the source frame lives on another device");
     if (src->W > 0 && src->H > 0 && (src->band_ty0 != 0 || band_rows(src) != src->H))
         return fail(c, SWR_ERR_UNSUPPORTED, "the source context holds only a band of its frame (swr_set_band*)");
-    if ((long long)t->w * kx != (long long)src->W || (long long)t->h * ky != (long long)src->H)
-        return fail(c, SWR_ERR_INVALID_ARG, "the source frame must measure texture width * kx by texture height * ky");
+    if ((long long)tw * kx != (long long)src->W || (long long)th * ky != (long long)src->H)
+        return fail(c, SWR_ERR_INVALID_ARG, u.by_face ? "the source frame must measure n * kx by n * ky for a cube map of side n"
+                                                      : "the source frame must measure texture width * kx by texture height * ky");
     const PostProg* post = nullptr;
     if (posted) {
         const auto it = src->posts.find(u.post_id);
@@ -423,18 +430,20 @@ int texture_update(swr_context* c, swr_texture* t, swr_context* src, const Textu
         SWR_HIP(c, hipStreamWaitEvent(c->stream, src->rtt_frame_ev, 0));
     }
     const bool blocked = t->d_blocked != nullptr;         // (made by swr_texture_set_filter: both sides are multiples of 4)
+    uint32_t* const d_rgba = reinterpret_cast<uint32_t*>(t->d_rgba) + first;
+    uint32_t* const d_blocked = blocked ? reinterpret_cast<uint32_t*>(t->d_blocked) + first : nullptr;
     if (post) {
         // (the resolve writes src's plane and the program may sample src's textures: both behind rtt_frame_ev, and src's later work --
         // a present, an update of such a texture -- behind rtt_done_ev)
-        if ((rc = launch_post_over(c, src, post, u.mode == SWR_TEXTURE_ALPHA_KEEP ? POST_TEXELS_KEEP : POST_TEXELS_OPAQUE, kx, ky, t->d_rgba, (uint32_t*)t->d_blocked))) return rc;
+        if ((rc = launch_post_over(c, src, post, u.mode == SWR_TEXTURE_ALPHA_KEEP ? POST_TEXELS_KEEP : POST_TEXELS_OPAQUE, kx, ky, d_rgba, d_blocked))) return rc;
     } else {
-        const auto [grid, block] = deliver_shape((uint32_t)t->w, (uint32_t)t->h);
+        const auto [grid, block] = deliver_shape((uint32_t)tw, (uint32_t)th);
         if (from_depth)
             hipLaunchKernelGGL(depth_texture_kernel(kx, ky, blocked), grid, block, 0, c->stream, (const float*)src->depth,
-                               (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h, u.mode);
+                               d_rgba, d_blocked, (uint32_t)tw, (uint32_t)th, u.mode);
         else
             hipLaunchKernelGGL(rtt_kernel(kx, ky, u.mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
-                               (uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, (uint32_t)t->w, (uint32_t)t->h);
+                               d_rgba, d_blocked, (uint32_t)tw, (uint32_t)th);
         SWR_HIP(c, hipGetLastError());
     }
     // a chain is a property of the texture: its levels follow the new level 0, on the same stream (a texture without one: nothing)
@@ -921,7 +930,9 @@ int swr_texture_generate_mipmaps(swr_context* c, swr_texture* t) {
     SWR_ENTER(c);
     if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
     if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    const int L = mip_full_levels(t->w, t->h);
+    if (t->cube && (t->w & (t->w - 1)) != 0)
+        return fail(c, SWR_ERR_UNSUPPORTED, "a cube map's chain needs a power-of-two side (per-face level sizes are out of scope, DESIGN.md section 27)");
+    const int L = texture_full_levels(t);                    // (a cube's chain ends where a face is one texel)
     if (L == 1) return SWR_OK;                               // 1 x 1: a chain of one level, which it has
     // immediate-mode semantics without a host wait (swr_texture_update_from_frame's): the recorded draws go first and read the old
     // record -- the device reads it when a kernel runs, so the order on the stream is what "earlier" and "later" mean
@@ -950,7 +961,7 @@ int swr_texture_levels(swr_context* c, const swr_texture* t, int* levels) {
 int swr_texture_level_size(swr_context* c, const swr_texture* t, int level, int* w, int* h) {
     SWR_ENTER(c);
     if (!t || !w || !h) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_level_size arguments");
-    if (level < 0 || level >= mip_full_levels(t->w, t->h)) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the texture's full chain (0 .. floor(log2(max(w, h))))");
+    if (level < 0 || level >= texture_full_levels(t)) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the texture's full chain (0 .. floor(log2(max(w, h))))");
     *w = mip_level_side(t->w, level); *h = mip_level_side(t->h, level);
     return SWR_OK;
 }
@@ -999,6 +1010,124 @@ int swr_texture_lod(swr_context* c, const swr_texture* t, const float* grads, in
     hipLaunchKernelGGL(k_texture_lod, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
     SWR_HIP(c, hipGetLastError());
     SWR_HIP(c, hipMemcpyAsync(out_lod, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+// ---- cube maps: an n x 6 n texture, face f in rows [f n, (f + 1) n)
+namespace {
+int cube_create(swr_context* c, const void* texels, int n, swr_texture** out, int format) {
+    if (n < 1 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad cube map arguments");
+    if (6ull * (uint64_t)n * (uint64_t)n >= (1ull << 30)) return fail(c, SWR_ERR_INVALID_ARG, "cube maps of 2^30 texels or more are not supported (32-bit texel index)");
+    const int rc = texture_create(c, texels, n, 6 * n, out, texels ? "texture upload failed: " : "texture allocation failed: ", format);
+    if (rc == SWR_OK) (*out)->cube = true;
+    return rc;
+}
+}  // namespace
+
+int swr_texture_create_cube(swr_context* c, const uint8_t* rgba8, int n, swr_texture** out) { SWR_ENTER(c); return cube_create(c, rgba8, n, out, SWR_TEXTURE_FORMAT_RGBA8); }
+int swr_texture_create_cube_depth(swr_context* c, const float* depth, int n, swr_texture** out) { SWR_ENTER(c); return cube_create(c, depth, n, out, SWR_TEXTURE_FORMAT_DEPTH32F); }
+
+int swr_texture_is_cube(swr_context* c, const swr_texture* t, int* n) {
+    SWR_ENTER(c);
+    if (!t || !n) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_is_cube arguments");
+    *n = t->cube ? t->w : 0;
+    return SWR_OK;
+}
+
+int swr_texture_update_face_from_frame(swr_context* c, swr_texture* t, int face, swr_context* src, int kx, int ky, int alpha_mode) {
+    return texture_update_locked(c, t, src, TextureUpdate{ FROM_FRAME, kx, ky, alpha_mode, 0, face, true });
+}
+int swr_texture_update_face_from_depth(swr_context* c, swr_texture* t, int face, swr_context* src, int kx, int ky, int reduce) {
+    return texture_update_locked(c, t, src, TextureUpdate{ FROM_DEPTH, kx, ky, reduce, 0, face, true });
+}
+int swr_texture_update_face_from_post(swr_context* c, swr_texture* t, int face, swr_context* src, int post_id, int kx, int ky, int alpha_mode) {
+    return texture_update_locked(c, t, src, TextureUpdate{ FROM_POST, kx, ky, alpha_mode, post_id, face, true });
+}
+
+int swr_texture_readback_face(swr_context* c, const swr_texture* t, int face, int level, void* out) {
+    SWR_ENTER(c);
+    if (!t || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback_face arguments");
+    if (!t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube, swr_texture_create_cube_depth)");
+    if (face < 0 || face > 5) return fail(c, SWR_ERR_INVALID_ARG, "face must be 0 .. 5 (+X, -X, +Y, -Y, +Z, -Z)");
+    if (level < 0 || level >= t->levels) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the levels the texture has (swr_texture_levels)");
+    const size_t n = (size_t)(t->w >> level);
+    const uint8_t* from = t->d_rgba;
+    if (level > 0) {
+        uint32_t off[SWR_TEXTURE_MAX_LEVELS];
+        mip_offsets(t, t->levels, off);
+        from = t->d_tail + (size_t)off[level] * 4;
+    }
+    SWR_HIP(c, hipMemcpyAsync(out, from + (size_t)face * n * n * 4, n * n * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+int swr_cube_face_view(int face, const float* eye, float* view) {
+    if (face < 0 || face > 5 || !eye || !view) return SWR_ERR_INVALID_ARG;
+    // Matrix4x4.CreateLookAt(eye, eye + axis, up) with up = +Y (+Y: +Z, -Y: -Z): the camera's x, y and z axes in the world
+    static const float X[6][3] = { { 0, 0, 1 }, { 0, 0, -1 }, { 1, 0, 0 }, { 1, 0, 0 }, { -1, 0, 0 }, { 1, 0, 0 } };
+    static const float Y[6][3] = { { 0, 1, 0 }, { 0, 1, 0 }, { 0, 0, 1 }, { 0, 0, -1 }, { 0, 1, 0 }, { 0, 1, 0 } };
+    static const float Z[6][3] = { { -1, 0, 0 }, { 1, 0, 0 }, { 0, -1, 0 }, { 0, 1, 0 }, { 0, 0, -1 }, { 0, 0, 1 } };
+    const float (*axes[3])[3] = { X, Y, Z };
+    for (int k = 0; k < 3; ++k) {
+        const float* a = axes[k][face];
+        for (int r = 0; r < 3; ++r) view[4 * r + k] = a[r];
+        // (Vector3.Dot(axis, eye) in float32: two of the products are zeros, so the sum is +-eye's component whatever fuses)
+        view[12 + k] = -((a[0] * eye[0] + a[1] * eye[1]) + a[2] * eye[2]);
+    }
+    view[3] = view[7] = view[11] = 0.0f; view[15] = 1.0f;
+    return SWR_OK;
+}
+
+int swr_texture_cube_face(swr_context* c, const float* dirs, int n, int* out_face, float* out_st) {
+    SWR_ENTER(c);
+    if (!dirs || !out_face || !out_st || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_cube_face arguments");
+    if (n == 0) return SWR_OK;
+    // faces and (s, t) come back in one block: n x (face, s, t) would interleave types, so two blocks, the second 16-byte aligned
+    const size_t off_face = ((size_t)n * 12 + 15) & ~(size_t)15, off_st = off_face + (((size_t)n * 4 + 15) & ~(size_t)15);
+    int rc = ensure(c, c->d_scratch, off_st + (size_t)n * 8);
+    if (rc) return rc;
+    char* base = reinterpret_cast<char*>(c->d_scratch.p);
+    SWR_HIP(c, hipMemcpyAsync(base, dirs, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_texture_cube_face, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float*)base, n, (int*)(base + off_face), (float2*)(base + off_st));
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipMemcpyAsync(out_face, base + off_face, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    SWR_HIP(c, hipMemcpyAsync(out_st, base + off_st, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+int swr_texture_sample_cube(swr_context* c, const swr_texture* t, const float* dir_lod, int n, float* out_rgba) {
+    SWR_ENTER(c);
+    if (!t || !dir_lod || !out_rgba || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_cube arguments");
+    if (!t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube)");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
+    if (n == 0) return SWR_OK;
+    const size_t off_out = (size_t)n * 16;
+    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 16);
+    if (rc) return rc;
+    float4* d_in = c->d_scratch.as<float4>();
+    float4* d_out = d_in + n;
+    SWR_HIP(c, hipMemcpyAsync(d_in, dir_lod, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_texture_sample_cube, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    return sync_locked(c);
+}
+
+int swr_texture_sample_cube_depth(swr_context* c, const swr_texture* t, const float* dir_ref, int n, float* out) {
+    SWR_ENTER(c);
+    if (!t || !dir_ref || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_cube_depth arguments");
+    if (!t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube_depth)");
+    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_DEPTH32F)) return rc;
+    if (n == 0) return SWR_OK;
+    const size_t off_out = (size_t)n * 16;
+    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 8);
+    if (rc) return rc;
+    float4* d_in = c->d_scratch.as<float4>();
+    float2* d_out = reinterpret_cast<float2*>(d_in + n);
+    SWR_HIP(c, hipMemcpyAsync(d_in, dir_ref, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_texture_sample_cube_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_locked(c);
 }
 

@@ -328,6 +328,29 @@ __global__ __launch_bounds__(256) void k_texture_lod(TextureSlot t, const float4
     const float4 g = grads[i];
     out[i] = texture_slot_lod(t, g.x, g.y, g.z, g.w);
 }
+// cube maps.  swr_texture_cube_face: dirs: n x (x, y, z) -> n faces and n x (s, t)
+__global__ __launch_bounds__(256) void k_texture_cube_face(const float* __restrict__ dirs, int n, int* __restrict__ out_face, float2* __restrict__ out_st) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int face; float s, t;
+    texture_cube_face(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], face, s, t);
+    out_face[i] = face;
+    out_st[i] = make_float2(s, t);
+}
+// swr_texture_sample_cube: dir_lod: n x (x, y, z, lod), out: n x RGBA, through the slot as the texture is now
+__global__ __launch_bounds__(256) void k_texture_sample_cube(TextureSlot t, const float4* __restrict__ dir_lod, int n, float4* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 d = dir_lod[i];
+    out[i] = texture_slot_sample_cube_lod(t, d.x, d.y, d.z, d.w);
+}
+// swr_texture_sample_cube_depth: dir_ref: n x (x, y, z, ref), out: n x (word, shadow)
+__global__ __launch_bounds__(256) void k_texture_sample_cube_depth(TextureSlot t, const float4* __restrict__ dir_ref, int n, float2* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 d = dir_ref[i];
+    out[i] = make_float2(texture_slot_cube_depth_sample(t, d.x, d.y, d.z), texture_slot_shadow_cube(t, d.x, d.y, d.z, d.w));
+}
 #endif
 
 }  // namespace swr

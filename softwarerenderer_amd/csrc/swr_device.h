@@ -743,6 +743,159 @@ __device__ __forceinline__ float4 texture_slot_sample_lod(const TextureSlot& t, 
     return make_float4(c0.x * (1.0f - f) + c1.x * f, c0.y * (1.0f - f) + c1.y * f, c0.z * (1.0f - f) + c1.z * f, c0.w * (1.0f - f) + c1.w * f);
 }
 
+// CUBE MAPS (build-defined; include/swr.h; tests/cubemap_cases.py restates these in numpy).  A cube of side n is
+// an ordinary texture n wide and 6 n high: face f (0..5 = +X, -X, +Y, -Y, +Z, -Z) is rows [f n, (f + 1) n), in either format and either
+// layout (n % 4 == 0: face f starts f n^2 texels into the block-linear copy too).  The slot's record does not say "cube": the program
+// does, by the function it calls.  A slot that is unbound or whose |h| != 6 |w| is NOT A CUBE, which is answered before any load: the
+// colour functions give (1, 1, 1, 1), the depth word is float.MinValue, the shadow 1, the size 0.  None of these is called by a kernel of
+// the product library.
+// The face a direction points at and where in it, (s, t) in [0, 1]^2 with t growing downwards: a right-handed world seen from inside;
+// face f is the image of a camera along the face's axis with up +Y (+Y: up +Z, -Y: up -Z) under the reference's screen mapping
+// (Rasterizer.cs:383-386).  The larger magnitude wins, ties in the order X, Y, Z; -0 counts as positive.  A direction with a NaN or an
+// Inf, and the zero vector: face 0, s = t = 0.5.  s and t are exactly 0 or 1 on a face's edge (the divide is correctly rounded).
+__device__ __forceinline__ void texture_cube_face(float x, float y, float z, int& face, float& s, float& t) {
+    const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
+    const float flt_max = 3.402823466e+38f;
+    face = 0; s = 0.5f; t = 0.5f;
+    if (!(ax <= flt_max && ay <= flt_max && az <= flt_max)) return;
+    if (ax == 0.0f && ay == 0.0f && az == 0.0f) return;
+    float ma, sc, tc;
+    if (ax >= ay && ax >= az) { ma = ax; face = x < 0 ? 1 : 0; sc = x < 0 ? -z : z; tc = -y; }
+    else if (ay >= az)        { ma = ay; face = y < 0 ? 3 : 2; sc = x;              tc = y < 0 ? z : -z; }
+    else                      { ma = az; face = z < 0 ? 5 : 4; sc = z < 0 ? x : -x; tc = -y; }
+    const float qs = sc / ma, qt = tc / ma;
+    s = (qs + 1.0f) * 0.5f;
+    t = (qt + 1.0f) * 0.5f;
+}
+// n of a cube, 0 of anything else (no load)
+__device__ __forceinline__ int texture_slot_cube_size(const TextureSlot& t) {
+    if (!texture_slot_bound(t)) return 0;
+    const int w = t.w < 0 ? -t.w : t.w, h = t.h < 0 ? -t.h : t.h;
+    return (w >= 1 && h % 6 == 0 && h / 6 == w) ? w : 0;
+}
+// one level of a cube as the functions below address it: 6 faces of n x n four-byte texels, face-major
+struct CubeLevel { const uint32_t* texels; int n; bool blocked; };
+__device__ __forceinline__ CubeLevel cube_level0(const TextureSlot& t, int n) {
+    return CubeLevel{ reinterpret_cast<const uint32_t*>(t.texels), n, t.w < 0 };
+}
+__device__ __forceinline__ uint32_t cube_word(const CubeLevel& c, int face, int x, int y) {       // x, y inside the face
+    const int row = face * c.n + y;
+    return c.texels[c.blocked ? bilinear_texel_offset<true>(c.n, x, row) : bilinear_texel_offset<false>(c.n, x, row)];
+}
+// the nearest texel of (s, t): (min((int)(s n), n - 1), min((int)(t n), n - 1))
+__device__ __forceinline__ void cube_nearest(int n, float s, float t, int& x, int& y) {
+    x = (int)(s * (float)n); y = (int)(t * (float)n);
+    x = x > n - 1 ? n - 1 : x; y = y > n - 1 ? n - 1 : y;
+}
+// the bilinear footprint of (s, t): X = s n - 0.5, x0 = floor(X), fx = X - x0, taps x0 and x0 + 1 each clamped to [0, n - 1] -- the
+// footprint never leaves the face (filtering across face edges is out of scope: a seam of up to one texel of clamped colour)
+__device__ __forceinline__ void cube_footprint(int n, float s, float t, int& x0, int& x1, int& y0, int& y1, float& fx, float& fy) {
+    const float X = s * (float)n - 0.5f, Y = t * (float)n - 0.5f;
+    const float fx0 = floorf(X), fy0 = floorf(Y);
+    fx = X - fx0; fy = Y - fy0;
+    const int ix = (int)fx0, iy = (int)fy0;
+    x0 = ix < 0 ? 0 : (ix > n - 1 ? n - 1 : ix); x1 = ix + 1 < 0 ? 0 : (ix + 1 > n - 1 ? n - 1 : ix + 1);
+    y0 = iy < 0 ? 0 : (iy > n - 1 ? n - 1 : iy); y1 = iy + 1 < 0 ? 0 : (iy + 1 > n - 1 ? n - 1 : iy + 1);
+}
+// the slot's filter inside one level: nearest unpacked as Texture.Sample unpacks it, bilinear blended in texture_sample_bilinear's form
+__device__ __forceinline__ float4 cube_level_sample(const CubeLevel& c, bool bilinear, float x, float y, float z) {
+    int face; float s, t;
+    texture_cube_face(x, y, z, face, s, t);
+    if (!bilinear) {
+        int tx, ty;
+        cube_nearest(c.n, s, t, tx, ty);
+        return texture_unpack(cube_word(c, face, tx, ty));
+    }
+    int x0, x1, y0, y1; float fx, fy;
+    cube_footprint(c.n, s, t, x0, x1, y0, y1, fx, fy);
+    const uint32_t p00 = cube_word(c, face, x0, y0), p10 = cube_word(c, face, x1, y0);
+    const uint32_t p01 = cube_word(c, face, x0, y1), p11 = cube_word(c, face, x1, y1);
+    const float inv255 = 1.0f / 255.0f;
+    float o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float c00 = (float)((p00 >> (8 * k)) & 0xffu) * inv255, c10 = (float)((p10 >> (8 * k)) & 0xffu) * inv255;
+        const float c01 = (float)((p01 >> (8 * k)) & 0xffu) * inv255, c11 = (float)((p11 >> (8 * k)) & 0xffu) * inv255;
+        const float top = c00 * (1.0f - fx) + c10 * fx;
+        const float bot = c01 * (1.0f - fx) + c11 * fx;
+        o[k] = top * (1.0f - fy) + bot * fy;
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+// level 0 by direction, with the slot's filter
+__device__ __forceinline__ float4 texture_slot_sample_cube(const TextureSlot& t, float x, float y, float z) {
+    const int n = texture_slot_cube_size(t);
+    if (n == 0) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    return cube_level_sample(cube_level0(t, n), t.h < 0, x, y, z);
+}
+// texel (x, y) of a face: face clamped to [0, 5], x and y to [0, n - 1]; no filter, no direction
+__device__ __forceinline__ float4 texture_slot_cube_texel(const TextureSlot& t, int face, int x, int y) {
+    const int n = texture_slot_cube_size(t);
+    if (n == 0) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    face = face < 0 ? 0 : (face > 5 ? 5 : face);
+    x = x < 0 ? 0 : (x > n - 1 ? n - 1 : x); y = y < 0 ? 0 : (y > n - 1 ? n - 1 : y);
+    return texture_unpack(cube_word(cube_level0(t, n), face, x, y));
+}
+// the last level a cube lookup may name: what the record says (texture_slot_sample_level's clamp), and never past floor(log2 n) -- a
+// cube's chain ends there (swr_texture_generate_mipmaps), and in the longer chain of an n x 6 n texture that was not created as a cube
+// the levels beyond it hold fewer than six faces' rows
+__device__ __forceinline__ int cube_top_level(const TextureSlot& t, int n) {
+    const int top = (int)texture_slot_header(t)->levels - 1, cap = 31 - __builtin_clz((unsigned)n);
+    return top < cap ? (top < 0 ? 0 : top) : cap;
+}
+// One level of a cube's chain, `level` clamped to [0, top]: level l is the n_l x 6 n_l atlas with n_l = n >> l, row-major behind the
+// header's tail; the slot's filter is applied inside it.  Level 0 is texture_slot_sample_cube.
+__device__ __forceinline__ float4 texture_slot_sample_cube_level(const TextureSlot& t, int level, float x, float y, float z) {
+    const int n = texture_slot_cube_size(t);
+    if (n == 0) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const int top = cube_top_level(t, n);
+    level = level < 0 ? 0 : (level > top ? top : level);
+    if (level == 0) return cube_level_sample(cube_level0(t, n), t.h < 0, x, y, z);
+    const TextureHeader* __restrict__ hd = texture_slot_header(t);
+    const CubeLevel c{ reinterpret_cast<const uint32_t*>(hd->tail) + hd->offset[level], n >> level, false };
+    return cube_level_sample(c, t.h < 0, x, y, z);
+}
+// between two levels, blended as texture_slot_sample_lod blends them
+__device__ __forceinline__ float4 texture_slot_sample_cube_lod(const TextureSlot& t, float x, float y, float z, float lod) {
+    const int n = texture_slot_cube_size(t);
+    if (n == 0) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    const int top = cube_top_level(t, n);
+    if (!(lod > 0.0f)) lod = 0.0f;
+    if (lod > (float)top) lod = (float)top;
+    const int l0 = (int)lod;
+    const float f = lod - (float)l0;
+    const float4 c0 = texture_slot_sample_cube_level(t, l0, x, y, z);
+    if (f == 0.0f) return c0;
+    const float4 c1 = texture_slot_sample_cube_level(t, l0 + 1 > top ? top : l0 + 1, x, y, z);
+    return make_float4(c0.x * (1.0f - f) + c1.x * f, c0.y * (1.0f - f) + c1.y * f, c0.z * (1.0f - f) + c1.z * f, c0.w * (1.0f - f) + c1.w * f);
+}
+// A DEPTH cube (swr_texture_create_cube_depth): the word of the nearest texel, ALWAYS nearest whatever the filter
+__device__ __forceinline__ float texture_slot_cube_depth_sample(const TextureSlot& t, float x, float y, float z) {
+    const int n = texture_slot_cube_size(t);
+    if (n == 0) return SWR_FLOAT_MINVALUE;
+    int face, tx, ty; float s, tt;
+    texture_cube_face(x, y, z, face, s, tt);
+    cube_nearest(n, s, tt, tx, ty);
+    return __uint_as_float(cube_word(cube_level0(t, n), face, tx, ty));
+}
+// texture_slot_shadow by direction: nearest filter, ref >= word ? 1 : 0 of the one texel; bilinear filter, the four comparisons over
+// the clamped footprint blended as lerps -- exactly 0 or 1 where the four agree.  Not a cube: 1, lit.
+__device__ __forceinline__ float texture_slot_shadow_cube(const TextureSlot& t, float x, float y, float z, float ref) {
+    const int n = texture_slot_cube_size(t);
+    if (n == 0) return 1.0f;
+    if (t.h >= 0) return ref >= texture_slot_cube_depth_sample(t, x, y, z) ? 1.0f : 0.0f;
+    int face; float s, tt;
+    texture_cube_face(x, y, z, face, s, tt);
+    int x0, x1, y0, y1; float fx, fy;
+    cube_footprint(n, s, tt, x0, x1, y0, y1, fx, fy);
+    const CubeLevel c = cube_level0(t, n);
+    const float c00 = ref >= __uint_as_float(cube_word(c, face, x0, y0)) ? 1.0f : 0.0f, c10 = ref >= __uint_as_float(cube_word(c, face, x1, y0)) ? 1.0f : 0.0f;
+    const float c01 = ref >= __uint_as_float(cube_word(c, face, x0, y1)) ? 1.0f : 0.0f, c11 = ref >= __uint_as_float(cube_word(c, face, x1, y1)) ? 1.0f : 0.0f;
+    const float top = c00 + (c10 - c00) * fx;
+    const float bot = c01 + (c11 - c01) * fx;
+    return top + (bot - top) * fy;
+}
+
 // The per-draw block of a user-program batch (RasterArgs::user_consts, k_vertex_user's last argument): the draw's 64 captured constants,
 // then its captured texture slots 1 .. SWR_PROGRAM_TEXTURES - 1 as TextureSlot records (slot 0 is the draw's texture, in DrawParams).
 // Only run-time compiled kernels read it.  76 words, 304 bytes: every block and every record in it is 16-byte aligned.

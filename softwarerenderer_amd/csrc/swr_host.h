@@ -28,11 +28,16 @@ struct swr_texture {
     // earlier with a TextureHeader (swr_device.h): texels_alloc / texels_free.  Both headers name the same tail.
     uint8_t* d_tail = nullptr;                // levels 1 .. L - 1, row-major, one behind the other: allocated by the first swr_texture_generate_mipmaps
     int levels = 1;                           // what the headers say: 1, or L once the chain exists
+    // CUBE MAP: w = n, h = 6 n, face f in rows [f n, (f + 1) n).  Host-side only, like the format
+    bool cube = false;
 };
 
 // the chain a w x h texture can have: L = 1 + floor(log2(max(w, h))) levels, level l measuring max(1, w >> l) by max(1, h >> l)
 inline int mip_full_levels(int w, int h) { int L = 1; for (int m = w > h ? w : h; m > 1; m >>= 1) ++L; return L; }
 inline int mip_level_side(int side, int level) { return (side >> level) > 1 ? (side >> level) : 1; }
+// ... and a cube of power-of-two side n: L = 1 + log2(n), level l the (n >> l) x 6 (n >> l) atlas -- the first L levels of the n x 6 n
+// texture's chain, where no 2 x 2 box straddles two faces.  Another side has no chain (swr_texture_generate_mipmaps refuses it)
+inline int texture_full_levels(const swr_texture* t) { return t->cube ? ((t->w & (t->w - 1)) == 0 ? mip_full_levels(t->w, 1) : 1) : mip_full_levels(t->w, t->h); }
 // a texel array of `bytes` behind its header: *texels is texel 0, 256-byte aligned as hipMalloc's block is
 inline hipError_t texels_alloc(uint8_t** texels, size_t bytes) {
     void* base = nullptr;

@@ -112,6 +112,17 @@ __device__ __forceinline__ int swr_post_texture_levels(const swr_post_env& env, 
 __device__ __forceinline__ float4 swr_post_sample_level(const swr_post_env& env, int slot, float2 uv, int level) { return swr::texture_slot_sample_level(swr_post_slot_(env, slot), level, uv.x, uv.y); }
 __device__ __forceinline__ float4 swr_post_sample_lod(const swr_post_env& env, int slot, float2 uv, float lod) { return swr::texture_slot_sample_lod(swr_post_slot_(env, slot), uv.x, uv.y, lod); }
 __device__ __forceinline__ float swr_post_lod(const swr_post_env& env, int slot, float4 grad) { return swr::texture_slot_lod(swr_post_slot_(env, slot), grad.x, grad.y, grad.z, grad.w); }
+// A slot's CUBE MAP: swr_cube_face, swr_sample_cube, swr_sample_cube_level, swr_sample_cube_lod, swr_cube_texel,
+// swr_cube_size, swr_sample_cube_depth and swr_shadow_cube of a user program.  Not a cube (unbound, out of range, not n by 6 n):
+// (1, 1, 1, 1), float.MinValue, shadow 1, size 0.
+__device__ __forceinline__ void swr_post_cube_face(float3 dir, int* face, float2* uv) { swr::texture_cube_face(dir.x, dir.y, dir.z, *face, uv->x, uv->y); }
+__device__ __forceinline__ float4 swr_post_sample_cube(const swr_post_env& env, int slot, float3 dir) { return swr::texture_slot_sample_cube(swr_post_slot_(env, slot), dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float4 swr_post_sample_cube_level(const swr_post_env& env, int slot, float3 dir, int level) { return swr::texture_slot_sample_cube_level(swr_post_slot_(env, slot), level, dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float4 swr_post_sample_cube_lod(const swr_post_env& env, int slot, float3 dir, float lod) { return swr::texture_slot_sample_cube_lod(swr_post_slot_(env, slot), dir.x, dir.y, dir.z, lod); }
+__device__ __forceinline__ float4 swr_post_cube_texel(const swr_post_env& env, int slot, int face, int x, int y) { return swr::texture_slot_cube_texel(swr_post_slot_(env, slot), face, x, y); }
+__device__ __forceinline__ int swr_post_cube_size(const swr_post_env& env, int slot) { return swr::texture_slot_cube_size(swr_post_slot_(env, slot)); }
+__device__ __forceinline__ float swr_post_sample_cube_depth(const swr_post_env& env, int slot, float3 dir) { return swr::texture_slot_cube_depth_sample(swr_post_slot_(env, slot), dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float swr_post_shadow_cube(const swr_post_env& env, int slot, float3 dir, float ref) { return swr::texture_slot_shadow_cube(swr_post_slot_(env, slot), dir.x, dir.y, dir.z, ref); }
 
 // the user's program (always inlined into k_post)
 __device__ __attribute__((always_inline)) float4 swr_post(const swr_post_in& in, const swr_post_env& env);

@@ -102,6 +102,24 @@ __device__ __forceinline__ float4 swr_sample_level(const swr_fs_env& env, int sl
 __device__ __forceinline__ float4 swr_sample_lod(const swr_fs_env& env, int slot, float2 uv, float lod) { return swr::texture_slot_sample_lod(swr_slot_(env, slot), uv.x, uv.y, lod); }
 __device__ __forceinline__ float swr_lod(const swr_fs_env& env, int slot, float4 grad) { return swr::texture_slot_lod(swr_slot_(env, slot), grad.x, grad.y, grad.z, grad.w); }
 __device__ __forceinline__ float4 swr_sample_grad(const swr_fs_env& env, int slot, float2 uv, float4 grad) { return swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad)); }
+// A slot that holds a CUBE MAP (swr_texture_create_cube, swr_texture_update_face_from_frame; definitions in
+// swr_device.h): six faces +X, -X, +Y, -Y, +Z, -Z looked up by a direction from the cube's centre, of any length.  A slot that is unbound,
+// out of range or not n by 6 n is not a cube: it samples (1, 1, 1, 1), reads float.MinValue, shadows nothing (1) and measures 0.
+//   swr_cube_face(dir, &face, &uv)              the face the direction points at and where in it, uv in [0, 1]^2, v downwards
+//   swr_sample_cube(env, slot, dir)             the slot's filter inside that face: nearest, or bilinear with its 2 x 2 taps clamped to the face
+//   swr_sample_cube_level / _lod(env, slot, dir, level | lod)   the same inside the levels of the cube's chain (swr_sample_level / _lod)
+//   swr_cube_texel(env, slot, face, x, y)       one texel, face clamped to [0, 5] and x, y to the face
+//   swr_cube_size(env, slot)                    n
+//   swr_sample_cube_depth(env, slot, dir)       a DEPTH cube's word, always nearest
+//   swr_shadow_cube(env, slot, dir, ref)        swr_shadow by direction (a point light: dir = world - light)
+__device__ __forceinline__ void swr_cube_face(float3 dir, int* face, float2* uv) { swr::texture_cube_face(dir.x, dir.y, dir.z, *face, uv->x, uv->y); }
+__device__ __forceinline__ float4 swr_sample_cube(const swr_fs_env& env, int slot, float3 dir) { return swr::texture_slot_sample_cube(swr_slot_(env, slot), dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float4 swr_sample_cube_level(const swr_fs_env& env, int slot, float3 dir, int level) { return swr::texture_slot_sample_cube_level(swr_slot_(env, slot), level, dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float4 swr_sample_cube_lod(const swr_fs_env& env, int slot, float3 dir, float lod) { return swr::texture_slot_sample_cube_lod(swr_slot_(env, slot), dir.x, dir.y, dir.z, lod); }
+__device__ __forceinline__ float4 swr_cube_texel(const swr_fs_env& env, int slot, int face, int x, int y) { return swr::texture_slot_cube_texel(swr_slot_(env, slot), face, x, y); }
+__device__ __forceinline__ int swr_cube_size(const swr_fs_env& env, int slot) { return swr::texture_slot_cube_size(swr_slot_(env, slot)); }
+__device__ __forceinline__ float swr_sample_cube_depth(const swr_fs_env& env, int slot, float3 dir) { return swr::texture_slot_cube_depth_sample(swr_slot_(env, slot), dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float swr_shadow_cube(const swr_fs_env& env, int slot, float3 dir, float ref) { return swr::texture_slot_shadow_cube(swr_slot_(env, slot), dir.x, dir.y, dir.z, ref); }
 // the build's System.Numerics model (SWR_DOT_PAIRWISE): Vector3.Dot.  (swr_lerp, swr_max and swr_clamp: swr_user_math.hip.h)
 __device__ __forceinline__ float swr_dot3(float3 a, float3 b) { return swr::dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 // a null result: nothing is written (and under BlendMode.None the row's early-out applies)
@@ -148,6 +166,13 @@ __device__ __forceinline__ float4 swr_sample_level(const swr_vs_env& env, int sl
 __device__ __forceinline__ float4 swr_sample_lod(const swr_vs_env& env, int slot, float2 uv, float lod) { return swr::texture_slot_sample_lod(swr_slot_(env, slot), uv.x, uv.y, lod); }
 __device__ __forceinline__ float swr_lod(const swr_vs_env& env, int slot, float4 grad) { return swr::texture_slot_lod(swr_slot_(env, slot), grad.x, grad.y, grad.z, grad.w); }
 __device__ __forceinline__ float4 swr_sample_grad(const swr_vs_env& env, int slot, float2 uv, float4 grad) { return swr_sample_lod(env, slot, uv, swr_lod(env, slot, grad)); }
+__device__ __forceinline__ float4 swr_sample_cube(const swr_vs_env& env, int slot, float3 dir) { return swr::texture_slot_sample_cube(swr_slot_(env, slot), dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float4 swr_sample_cube_level(const swr_vs_env& env, int slot, float3 dir, int level) { return swr::texture_slot_sample_cube_level(swr_slot_(env, slot), level, dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float4 swr_sample_cube_lod(const swr_vs_env& env, int slot, float3 dir, float lod) { return swr::texture_slot_sample_cube_lod(swr_slot_(env, slot), dir.x, dir.y, dir.z, lod); }
+__device__ __forceinline__ float4 swr_cube_texel(const swr_vs_env& env, int slot, int face, int x, int y) { return swr::texture_slot_cube_texel(swr_slot_(env, slot), face, x, y); }
+__device__ __forceinline__ int swr_cube_size(const swr_vs_env& env, int slot) { return swr::texture_slot_cube_size(swr_slot_(env, slot)); }
+__device__ __forceinline__ float swr_sample_cube_depth(const swr_vs_env& env, int slot, float3 dir) { return swr::texture_slot_cube_depth_sample(swr_slot_(env, slot), dir.x, dir.y, dir.z); }
+__device__ __forceinline__ float swr_shadow_cube(const swr_vs_env& env, int slot, float3 dir, float ref) { return swr::texture_slot_shadow_cube(swr_slot_(env, slot), dir.x, dir.y, dir.z, ref); }
 // new Shaders.VertexOutput() (Shaders.cs:26-47): zero-initialised before swr_vertex is called, Interpolate = true
 struct swr_vs_out {
     float4 clip_position;        // ClipPosition

@@ -68,6 +68,29 @@ def create_look_at(eye, target, up) -> np.ndarray:
     return m
 
 
+# the cameras of a cube map's six faces (+X, -X, +Y, -Y, +Z, -Z): where each looks and what it holds up (swr_cube_face_view)
+CUBE_FACE_AXIS = ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))
+CUBE_FACE_UP = ((0, 1, 0), (0, 1, 0), (0, 0, 1), (0, 0, -1), (0, 1, 0), (0, 1, 0))
+_CUBE_X = ((0, 0, 1), (0, 0, -1), (1, 0, 0), (1, 0, 0), (-1, 0, 0), (1, 0, 0))
+_CUBE_Y = ((0, 1, 0), (0, 1, 0), (0, 0, 1), (0, 0, -1), (0, 1, 0), (0, 1, 0))
+_CUBE_Z = ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1))
+
+
+def cube_face_view(face: int, eye) -> np.ndarray:
+    """create_look_at(eye, eye + CUBE_FACE_AXIS[face], CUBE_FACE_UP[face]) with the camera's axes taken as the exact unit vectors
+    they are (eye + axis - eye is not the axis for every float eye).  Under create_perspective_fov(pi / 2, 1, near, far) the pixel
+    whose centre lies in direction d from eye is the texel texture_cube_face(d) names."""
+    if not 0 <= int(face) <= 5:
+        raise ValueError("face must be 0 .. 5 (+X, -X, +Y, -Y, +Z, -Z)")
+    eye = np.asarray(eye, dtype=F)
+    m = np.eye(4, dtype=F)
+    for k, table in enumerate((_CUBE_X, _CUBE_Y, _CUBE_Z)):
+        a = np.asarray(table[int(face)], dtype=F)
+        m[0, k], m[1, k], m[2, k] = a
+        m[3, k] = -F(F(F(a[0] * eye[0]) + F(a[1] * eye[1])) + F(a[2] * eye[2]))
+    return m
+
+
 def multiply(a, b) -> np.ndarray:
     return (np.asarray(a, dtype=F) @ np.asarray(b, dtype=F)).astype(F)
 

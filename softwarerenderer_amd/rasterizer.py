@@ -437,6 +437,129 @@ class Texture:
         self._dev._ck(self._dev._lib.swr_texture_lod(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
         return out.reshape(a.shape[:-1])
 
+    # ---- cube maps (build-defined; include/swr.h): a cube of side n is a texture n wide and 6 n high, face f
+    # (0..5 = +X, -X, +Y, -Y, +Z, -Z) in rows [f n, (f + 1) n); every other method sees that atlas
+    @classmethod
+    def _cube(cls, device: Device, n: int, data, depth: bool) -> "Texture":
+        t = cls.__new__(cls)
+        t._dev = device
+        t.Width, t.Height = int(n), 6 * int(n)
+        t._h = C.c_void_p()
+        fn = device._lib.swr_texture_create_cube_depth if depth else device._lib.swr_texture_create_cube
+        device._ck(fn(device._ctx, data.ctypes.data if data is not None else None, int(n), C.byref(t._h)))
+        return t
+
+    @classmethod
+    def Cube(cls, device: Device, faces) -> "Texture":
+        """A cube map from six faces (swr_texture_create_cube): `faces` of shape (6, n, n, 4) uint8, in the order +X, -X, +Y, -Y,
+        +Z, -Z, each as a camera along that axis sees it (hostmath.cube_face_view).  Read in programs through swr_sample_cube."""
+        px = np.ascontiguousarray(faces, dtype=np.uint8)
+        if px.ndim != 4 or px.shape[0] != 6 or px.shape[1] != px.shape[2] or px.shape[3] != 4 or px.shape[1] < 1:
+            raise ValueError("faces must be (6, n, n, 4) uint8")
+        return cls._cube(device, px.shape[1], px, False)
+
+    @classmethod
+    def CubeTarget(cls, device: Device, n: int) -> "Texture":
+        """A cube map of zeros without host data, to be filled face by face by UpdateFaceFrom / UpdateFaceFromPost."""
+        return cls._cube(device, n, None, False)
+
+    @classmethod
+    def CubeDepth(cls, device: Device, n: int, words=None) -> "Texture":
+        """A depth cube map (swr_texture_create_cube_depth): `words` of shape (6, n, n) float32 or, without it, float.MinValue
+        everywhere.  Filled by UpdateFaceFromDepth, read in programs through swr_shadow_cube / swr_sample_cube_depth."""
+        w = None
+        if words is not None:
+            w = np.ascontiguousarray(words, dtype=np.float32)
+            if w.shape != (6, int(n), int(n)):
+                raise ValueError("words must be (6, n, n) float32")
+        return cls._cube(device, n, w, True)
+
+    @property
+    def IsCube(self) -> int:
+        """n of a cube map, 0 of any other texture (swr_texture_is_cube)."""
+        n = C.c_int(-1)
+        self._dev._ck(self._dev._lib.swr_texture_is_cube(self._dev._ctx, self._h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def _face(face) -> int:
+        f = int(face)
+        if not 0 <= f <= 5:
+            raise ValueError("face must be 0 .. 5 (+X, -X, +Y, -Y, +Z, -Z)")
+        return f
+
+    def UpdateFaceFrom(self, face: int, window: "MainWindow", kx: int = 1, ky: int = 1, keep_alpha: bool = False):
+        """UpdateFrom into one face of a cube map (swr_texture_update_face_from_frame): the window measures n * kx by n * ky.  The
+        same kernel, order and contract; a cube with a mip chain has it regenerated in the same call."""
+        face = self._face(face)
+        window._activate()
+        src = window._dev._ctx if window._dev is not self._dev else None
+        self._dev._ck(self._dev._lib.swr_texture_update_face_from_frame(
+            self._dev._ctx, self._h, face, src, int(kx), int(ky), N.SWR_TEXTURE_ALPHA_KEEP if keep_alpha else N.SWR_TEXTURE_ALPHA_OPAQUE))
+
+    def UpdateFaceFromDepth(self, face: int, window: "MainWindow", kx: int = 1, ky: int = 1, reduce: int = DepthReduce.Max):
+        """UpdateFromDepth into one face of a depth cube map (swr_texture_update_face_from_depth)."""
+        face = self._face(face)
+        window._activate()
+        src = window._dev._ctx if window._dev is not self._dev else None
+        self._dev._ck(self._dev._lib.swr_texture_update_face_from_depth(self._dev._ctx, self._h, face, src, int(kx), int(ky), int(reduce)))
+
+    def UpdateFaceFromPost(self, face: int, window: "MainWindow", post: PostProgram, kx: int = 1, ky: int = 1, keep_alpha: bool = False):
+        """UpdateFromPost into one face of a cube map (swr_texture_update_face_from_post)."""
+        face = self._face(face)
+        window._activate()
+        src = window._dev._ctx if window._dev is not self._dev else None
+        self._dev._ck(self._dev._lib.swr_texture_update_face_from_post(
+            self._dev._ctx, self._h, face, src, post._id, int(kx), int(ky), N.SWR_TEXTURE_ALPHA_KEEP if keep_alpha else N.SWR_TEXTURE_ALPHA_OPAQUE))
+
+    def ReadFace(self, face: int, level: int = 0) -> np.ndarray:
+        """One face of a level the cube has (swr_texture_readback_face): (n_l, n_l, 4) uint8, or (n, n) float32 depth words;
+        waits for the GPU."""
+        face = self._face(face)
+        if not 0 <= int(level) < 32 or (self.Width >> int(level)) < 1:
+            raise ValueError("the level is outside the cube's chain")
+        n = self.Width >> int(level)
+        out = np.empty((n, n), dtype=np.float32) if self.Format == N.SWR_TEXTURE_FORMAT_DEPTH32F else np.empty((n, n, 4), dtype=np.uint8)
+        self._dev._ck(self._dev._lib.swr_texture_readback_face(self._dev._ctx, self._h, face, int(level), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _dirs4(dirs, last) -> tuple:
+        a = np.asarray(dirs, dtype=np.float32)
+        if a.ndim < 1 or a.shape[-1] != 3:
+            raise ValueError("directions must have shape (..., 3)")
+        l = np.broadcast_to(np.asarray(last, dtype=np.float32), a.shape[:-1])
+        return a.shape[:-1], np.ascontiguousarray(np.concatenate([a.reshape(-1, 3), l.reshape(-1, 1)], axis=1))
+
+    def SampleCube(self, dirs, lod=0.0) -> np.ndarray:
+        """swr_sample_cube_lod as a program computes it, with the texture's filter as it is now (swr_texture_sample_cube), batched:
+        dirs of shape (..., 3) and lod of shape (...) -> (..., 4); lod 0 is swr_sample_cube; runs on the GPU."""
+        shape, flat = self._dirs4(dirs, lod)
+        out = np.empty((flat.shape[0], 4), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_texture_sample_cube(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
+        return out.reshape(shape + (4,))
+
+    def SampleCubeDepth(self, dirs, ref) -> tuple:
+        """swr_sample_cube_depth and swr_shadow_cube of a depth cube (swr_texture_sample_cube_depth), batched: dirs of shape
+        (..., 3) and ref of shape (...) -> (depth, shadow), each of shape (...)."""
+        shape, flat = self._dirs4(dirs, ref)
+        out = np.empty((flat.shape[0], 2), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_texture_sample_cube_depth(self._dev._ctx, self._h, flat.ctypes.data, flat.shape[0], out.ctypes.data))
+        return out[:, 0].reshape(shape), out[:, 1].reshape(shape)
+
+    @staticmethod
+    def CubeFace(device: Device, dirs) -> tuple:
+        """swr_cube_face as a program computes it (swr_texture_cube_face), batched: dirs of shape (..., 3) -> (face of shape (...)
+        int32, st of shape (..., 2)); runs on the GPU."""
+        a = np.asarray(dirs, dtype=np.float32)
+        if a.ndim < 1 or a.shape[-1] != 3:
+            raise ValueError("directions must have shape (..., 3)")
+        flat = np.ascontiguousarray(a.reshape(-1, 3))
+        face = np.empty((flat.shape[0],), dtype=np.int32)
+        st = np.empty((flat.shape[0], 2), dtype=np.float32)
+        device._ck(device._lib.swr_texture_cube_face(device._ctx, flat.ctypes.data, flat.shape[0], face.ctypes.data, st.ctypes.data))
+        return face.reshape(a.shape[:-1]), st.reshape(a.shape[:-1] + (2,))
+
     def SetBilinear(self, on: bool):
         """Build-defined extension (the reference samples nearest): bilinear filter with wrap for later draws."""
         self._dev._ck(self._dev._lib.swr_texture_set_filter(self._dev._ctx, self._h, 1 if on else 0))
