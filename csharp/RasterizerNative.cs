@@ -247,6 +247,12 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_texture_sample_cube_depth(IntPtr ctx, IntPtr texture, float* dirRef, int n, float* outDepthShadow);
         [DllImport(Lib)] public static extern int swr_mesh_create(IntPtr ctx, Shaders.VertexInput* vertices, int nVertices, ushort* indices, int nIndices, out IntPtr mesh);
         [DllImport(Lib)] public static extern int swr_mesh_destroy(IntPtr ctx, IntPtr mesh);
+        // deforming meshes (include/swr.h "DEFORMING MESHES"): a retained mesh rewritten on the GPU
+        [DllImport(Lib)] public static extern int swr_mesh_create_like(IntPtr ctx, IntPtr src, out IntPtr mesh);
+        [DllImport(Lib)] public static extern int swr_mesh_readback(IntPtr ctx, IntPtr mesh, Shaders.VertexInput* outVertices);
+        [DllImport(Lib)] public static extern int swr_mesh_blend(IntPtr ctx, IntPtr dst, IntPtr a, IntPtr b, float t);
+        [DllImport(Lib)] public static extern int swr_mesh_set_skin(IntPtr ctx, IntPtr src, ushort* joints4, float* weights4);
+        [DllImport(Lib)] public static extern int swr_mesh_skin(IntPtr ctx, IntPtr dst, IntPtr src, Matrix4x4* palette, int nJoints);
         [DllImport(Lib)] public static extern int swr_set_state(IntPtr ctx, float nearClip, float farClip, int debugMode);
         [DllImport(Lib)] public static extern int swr_initialize_tile_locks(IntPtr ctx, int width, int height);
         [DllImport(Lib)] public static extern int swr_render_mesh(IntPtr ctx, IntPtr mesh, Matrix4x4* model, Matrix4x4* view, Matrix4x4* projection, int program, SwrUniforms* uniforms, IntPtr texture, int cullMode, int depthTest, int blendMode);
@@ -439,6 +445,13 @@ namespace SoftwareRenderer
             ~MeshHandle() { if (Ptr != IntPtr.Zero) Native.swr_mesh_destroy(SwrContext.Handle, Ptr); }
         }
 
+        /// Makes `handle` (a retained mesh made by swr_mesh_create_like) the device copy of `mesh`: freed with the Mesh object.
+        internal static void Adopt(Mesh mesh, IntPtr handle)
+        {
+            retained.Remove(mesh);
+            retained.Add(mesh, new MeshHandle { Ptr = handle });
+        }
+
         /// The device copy of a ModelLoader mesh, uploaded on first use (draws and PhysicsNative's ray queries share it).
         internal static unsafe IntPtr Retain(Mesh mesh)
         {
@@ -516,6 +529,55 @@ namespace SoftwareRenderer
                 ? Native.swr_render_mesh_culled(ctx, h, &model, &view, &projection, (int)program, &uniforms, texture, (int)cullMode, (int)depthTest, (int)blendMode)
                 : Native.swr_render_mesh(ctx, h, &model, &view, &projection, (int)program, &uniforms, texture, (int)cullMode, (int)depthTest, (int)blendMode);
             SwrContext.Check(rc);
+        }
+    }
+
+    // ---------------------------------------------------------------- deforming meshes ----
+    // A pose of a ModelLoader mesh on the GPU (build-defined, DESIGN.md section 28).  The reference animates by swapping whole key
+    // frames (Model.PlayAnimation, ModelLoader.cs:331-348) and shoots at the meshes it draws (Renderer.cs:172-216,503-541): a
+    // DeformedMesh is a retained copy of a mesh whose vertices are rewritten in place -- the blend of two key frames, or a skinned
+    // bind pose -- so that Rasterizer.RenderMesh(window, pose.Target, ...) and PhysicsNative.Raycast(..., pose.Target, ...) see the
+    // same vertices.  Target is an ordinary Mesh object whose device copy this class owns; its managed Vertices are the bind pose.
+    public sealed unsafe class DeformedMesh
+    {
+        public readonly Mesh Source;          // the mesh whose device copy was duplicated (and that carries the skin attributes)
+        public readonly Mesh Target;          // draw and shoot at this one
+        readonly IntPtr dst;
+
+        public DeformedMesh(Mesh source, Mesh target)
+        {
+            Source = source; Target = target;
+            SwrContext.Check(Native.swr_mesh_create_like(SwrContext.Handle, Rasterizer.Retain(source), out dst));
+            Rasterizer.Adopt(target, dst);
+        }
+
+        /// Target = a * (1 - t) + b * t, every scalar of position, uv, normal and colour (Vector*.Lerp's form; t is not clamped).
+        /// a and b are key frames with Source's vertex count: frames i and j of Model.AnimationFrames.
+        public void Blend(Mesh a, Mesh b, float t) =>
+            SwrContext.Check(Native.swr_mesh_blend(SwrContext.Handle, dst, Rasterizer.Retain(a), Rasterizer.Retain(b), t));
+
+        /// Four joint indices and four weights per vertex of Source, uploaded once.
+        public void SetSkin(ushort[] joints4, float[] weights4)
+        {
+            fixed (ushort* j = joints4)
+            fixed (float* w = weights4)
+                SwrContext.Check(Native.swr_mesh_set_skin(SwrContext.Handle, Rasterizer.Retain(Source), j, w));
+        }
+
+        /// Target = Source skinned by `palette` (one Matrix4x4 per joint: inverse bind * joint world * inverse mesh world, the caller's).
+        public void Skin(Matrix4x4[] palette)
+        {
+            fixed (Matrix4x4* p = palette)
+                SwrContext.Check(Native.swr_mesh_skin(SwrContext.Handle, dst, Rasterizer.Retain(Source), p, palette.Length));
+        }
+
+        /// The pose as the device holds it.
+        public Shaders.VertexInput[] Read()
+        {
+            var outv = new Shaders.VertexInput[Source.Vertices.Length];
+            fixed (Shaders.VertexInput* v = outv)
+                SwrContext.Check(Native.swr_mesh_readback(SwrContext.Handle, dst, v));
+            return outv;
         }
     }
 

@@ -402,6 +402,40 @@ int  swr_mesh_create(swr_context* ctx, const swr_vertex* vertices, int n_vertice
                      const uint16_t* indices, int n_indices, swr_mesh** out);
 int  swr_mesh_destroy(swr_context* ctx, swr_mesh* mesh);
 
+/* DEFORMING MESHES (build-defined) ----------------------------------------------------------------------------
+ * A retained mesh's vertices rewritten on the GPU: a blend of two key frames (Model.AnimationFrames, ModelLoader.cs:79-115; the
+ * reference swaps whole frames, PlayAnimation :331-348) or linear-blend skinning by a joint palette.  The result is the mesh's own
+ * swr_vertex array, so every reader follows the pose: swr_render_mesh*, swr_raycast*, swr_character_update, swr_mesh_bounds.
+ * ORDER: immediate mode, as swr_texture_update_from_frame -- draws recorded before a deform see the old vertices, draws recorded after
+ * it the new ones; no host wait in a loop that presents every frame.  Recorded draws are flushed first only if one of them references
+ * `dst`; a batch still in flight that references `dst` (it may have to be replayed against the vertices it saw) is waited for and
+ * validated before the first write.  After a deform the bounding sphere is computed again on first use.
+ * SWR_ERR_INVALID_ARG, nothing written, the context usable: a NULL pointer, unequal vertex counts, `dst` being a source, a mesh of
+ * another context, swr_mesh_skin on a source without skin attributes, n_joints <= the largest joint index the attributes use.
+ * (A transient mesh -- the one swr_render_mesh_arrays makes per call -- is refused likewise; no call hands its handle out.)
+ * SWR_ERR_UNSUPPORTED: n_joints > 65535.  A mesh without vertices: SWR_OK, nothing launched. */
+/* a retained mesh with src's vertex count, its vertices and indices copied device to device: a deform target */
+int  swr_mesh_create_like(swr_context* ctx, const swr_mesh* src, swr_mesh** out);
+/* the n_vertices 48-byte records as the device holds them.  Flushes nothing and waits only for work that writes the mesh */
+int  swr_mesh_readback(swr_context* ctx, const swr_mesh* mesh, swr_vertex* out);
+/* dst = a * (1 - t) + b * t for every scalar of position, uv, normal and color: the library's Lerp model (Shaders.Lerp, fused or not as
+ * the build's numerics say, swr_numerics_mode).  The normal is NOT renormalised (Renderer.VertexShader normalises the world normal): t = 0
+ * and t = 1 are the identity on finite inputs, up to the sign of a zero.  Any float t, used as it is: no clamp, NaN gives NaN.  dst
+ * keeps its own indices. */
+int  swr_mesh_blend(swr_context* ctx, swr_mesh* dst, const swr_mesh* a, const swr_mesh* b, float t);
+/* static skin attributes of a retained mesh: four joint indices and four weights per vertex, uploaded once and freed with the mesh.
+ * NULL, NULL removes them (and waits for the device). */
+int  swr_mesh_set_skin(swr_context* ctx, swr_mesh* src, const uint16_t* joints4, const float* weights4);
+/* dst = skin(src): palette = n_joints matrices of 16 floats, row-major for row vectors (glTF's jointMatrix -- inverse bind matrix x joint
+ * world x inverse mesh world -- as the caller computes it).  Per vertex, in the System.Numerics model (swr_set_transform_fma):
+ *   p_k = Vector3.Transform(position, palette[j_k]), n_k = Vector3.TransformNormal(normal, palette[j_k])  for k = 0 .. 3
+ *   r = w_0 * x_0, then r = w_k * x_k + r for k = 1, 2, 3 (each fused or not as the Transform / TransformNormal flag says)
+ *   normal = Vector3.Normalize(r_n); uv and color are copied.
+ * All four influences are evaluated (a zero weight on a matrix holding Inf gives NaN); weights are used as given, not renormalised.
+ * The normal goes through the joint matrix's upper 3 x 3: right for rigid joints and uniform scale, not for a sheared or unevenly
+ * scaled joint (that needs the inverse transpose, which the caller would have to supply as a second palette: not built). */
+int  swr_mesh_skin(swr_context* ctx, swr_mesh* dst, const swr_mesh* src, const float* palette, int n_joints);
+
 /* state ≙ public statics Rasterizer.NearClip / FarClip / RenderDebugMode, Rasterizer.cs:20-22 */
 int  swr_set_state(swr_context* ctx, float near_clip, float far_clip, int debug_mode);
 /* Rasterizer.InitializeTileLocks, Rasterizer.cs:69-93: width/height <= 0 -> SWR_ERR_INVALID_ARG */

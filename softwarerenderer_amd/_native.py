@@ -128,6 +128,7 @@ EXPORTS = [
     "swr_texture_create_cube", "swr_texture_create_cube_depth", "swr_texture_is_cube", "swr_texture_update_face_from_frame",
     "swr_texture_update_face_from_depth", "swr_texture_update_face_from_post", "swr_texture_readback_face", "swr_cube_face_view",
     "swr_texture_cube_face", "swr_texture_sample_cube", "swr_texture_sample_cube_depth",
+    "swr_mesh_create_like", "swr_mesh_readback", "swr_mesh_blend", "swr_mesh_set_skin", "swr_mesh_skin",
 ]
 
 _libs = {}
@@ -264,6 +265,11 @@ def load(name: str = None) -> C.CDLL:
         "swr_texture_cube_face": (I, [P, P, I, P, P]),
         "swr_texture_sample_cube": (I, [P, P, P, I, P]),
         "swr_texture_sample_cube_depth": (I, [P, P, P, I, P]),
+        "swr_mesh_create_like": (I, [P, P, C.POINTER(P)]),
+        "swr_mesh_readback": (I, [P, P, P]),
+        "swr_mesh_blend": (I, [P, P, P, P, F]),
+        "swr_mesh_set_skin": (I, [P, P, P, P]),
+        "swr_mesh_skin": (I, [P, P, P, fp, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -329,6 +329,51 @@ inline void Texture::UpdateFromPost(const MainWindow& window, const PostProgram&
     dev_.check(swr_texture_update_from_post(dev_.ctx(), h_, src, post.id(), kx, ky, keepAlpha ? SWR_TEXTURE_ALPHA_KEEP : SWR_TEXTURE_ALPHA_OPAQUE));
 }
 
+// A retained mesh (Mesh.Vertices / Mesh.Indices, ModelLoader.cs:45-47, uploaded once) and its deforms on the GPU (build-defined,
+// include/swr.h "DEFORMING MESHES"): a blend of two key frames, linear-blend skinning by a joint palette.  Draws, ray queries and
+// the bounding sphere follow the pose.
+class Mesh {
+public:
+    Mesh(const Device& dev, const std::vector<Shaders::VertexInput>& vertices, const std::vector<uint16_t>& indices)
+        : dev_(dev), n_vertices_((int)vertices.size()) {
+        dev_.check(swr_mesh_create(dev_.ctx(), vertices.data(), (int)vertices.size(), indices.data(), (int)indices.size(), &h_));
+    }
+    ~Mesh() { if (h_) swr_mesh_destroy(dev_.ctx(), h_); }
+    Mesh(const Mesh&) = delete;
+    Mesh& operator=(const Mesh&) = delete;
+    Mesh(Mesh&& o) noexcept : dev_(o.dev_), h_(o.h_), n_vertices_(o.n_vertices_) { o.h_ = nullptr; }
+    swr_mesh* handle() const { return h_; }
+    int VertexCount() const { return n_vertices_; }
+    Vector4 SphereBounds() const { Vector4 o{}; dev_.check(swr_mesh_bounds(dev_.ctx(), h_, o.data())); return o; }   // ModelLoader.cs:291
+    // a deform target: this mesh's vertices and indices copied on the GPU
+    Mesh Like() const { Mesh m(dev_, n_vertices_); dev_.check(swr_mesh_create_like(dev_.ctx(), h_, &m.h_)); return m; }
+    // the vertices as the device holds them (flushes nothing)
+    std::vector<Shaders::VertexInput> Read() const {
+        std::vector<Shaders::VertexInput> out((size_t)n_vertices_);
+        dev_.check(swr_mesh_readback(dev_.ctx(), h_, out.data()));
+        return out;
+    }
+    // vertices = a * (1 - t) + b * t, every scalar, in the build's Lerp model; t is not clamped
+    void BlendFrom(const Mesh& a, const Mesh& b, float t) { dev_.check(swr_mesh_blend(dev_.ctx(), h_, a.h_, b.h_, t)); }
+    // four joint indices and four weights per vertex, retained; two empty vectors remove them
+    void SetSkin(const std::vector<uint16_t>& joints4, const std::vector<float>& weights4) {
+        if (joints4.empty() && weights4.empty() && n_vertices_ > 0) { dev_.check(swr_mesh_set_skin(dev_.ctx(), h_, nullptr, nullptr)); return; }
+        if (joints4.size() != 4 * (size_t)n_vertices_ || weights4.size() != 4 * (size_t)n_vertices_)
+            throw std::invalid_argument("joints4 and weights4 must hold four entries per vertex");
+        static const uint16_t no_joint = 0; static const float no_weight = 0.0f;              // (a mesh without vertices: valid pointers)
+        dev_.check(swr_mesh_set_skin(dev_.ctx(), h_, joints4.empty() ? &no_joint : joints4.data(), weights4.empty() ? &no_weight : weights4.data()));
+    }
+    // vertices = src's, skinned by `palette` (glTF's jointMatrix per joint, row-major for row vectors) with src's skin attributes
+    void SkinFrom(const Mesh& src, const std::vector<Matrix4x4>& palette) {
+        dev_.check(swr_mesh_skin(dev_.ctx(), h_, src.h_, palette.empty() ? nullptr : palette[0].data(), (int)palette.size()));
+    }
+private:
+    Mesh(const Device& dev, int n_vertices) : dev_(dev), n_vertices_(n_vertices) {}
+    const Device& dev_;
+    swr_mesh* h_ = nullptr;
+    int n_vertices_ = 0;
+};
+
 class Rasterizer {                            // public static class Rasterizer, Rasterizer.cs:12
 public:
     enum class DebugMode { None = 0, Wireframe = 1 };                                              // :14-18
@@ -358,6 +403,20 @@ public:
                                        model.data(), view.data(), projection.data(), (int)shader.program, &shader.uniforms,
                                        shader.texture ? shader.texture->handle() : nullptr,
                                        (int)cullMode, (int)depthTest, (int)blendMode));
+    }
+    // ... from a retained mesh (no per-draw upload; a deformed mesh is drawn in its pose)
+    static void RenderMesh(MainWindow& window, const Mesh& mesh, const Matrix4x4& model, const Matrix4x4& view,
+                           const Matrix4x4& projection, const ShaderProgram& shader,
+                           CullMode cullMode = CullMode::Back, DepthTest depthTest = DepthTest::LessEqual,
+                           BlendMode blendMode = BlendMode::Alpha) {
+        const Device& d = window.device();
+        d.check(swr_set_state(d.ctx(), NearClip, FarClip, (int)RenderDebugMode));
+        if ((int)shader.program >= SWR_PROG_USER_BASE) {
+            d.SetProgramConstants((int)shader.program, shader.constants);
+            for (int k = 1; k < SWR_PROGRAM_TEXTURES; ++k) d.SetProgramTexture((int)shader.program, k, shader.textures[k - 1]);
+        }
+        d.check(swr_render_mesh(d.ctx(), mesh.handle(), model.data(), view.data(), projection.data(), (int)shader.program, &shader.uniforms,
+                                shader.texture ? shader.texture->handle() : nullptr, (int)cullMode, (int)depthTest, (int)blendMode));
     }
 };
 

@@ -45,6 +45,7 @@
 #include "swr_character.hip.h"
 #include "swr_deliver.hip.h"
 #include "swr_post.hip.h"
+#include "swr_mesh_deform.hip.h"
 
 using namespace swr;
 
@@ -569,6 +570,7 @@ void swr_destroy(swr_context* c) {
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->ray_stream) { (void)hipStreamSynchronize(c->ray_stream); (void)hipStreamDestroy(c->ray_stream); }
     release(c->ray_host);
+    for (auto& ps : c->palettes) { release(ps.host); release(ps.dev); if (ps.done) (void)hipEventDestroy(ps.done); }
     if (c->rtt_frame_ev) (void)hipEventDestroy(c->rtt_frame_ev);
     if (c->rtt_done_ev) (void)hipEventDestroy(c->rtt_done_ev);
     for (int i = 0; i < 2; ++i) {
@@ -1139,6 +1141,202 @@ int swr_mesh_destroy(swr_context* c, swr_mesh* m) {
     int rc = flush_and_sync_locked(c); if (rc) return rc;
     destroy_mesh(m);
     return SWR_OK;
+}
+
+// ---- deforming meshes: key-frame blend and matrix-palette skinning into a retained mesh
+namespace {
+// a retained mesh of this context, or the message why not
+int deform_mesh_check(swr_context* c, const swr_mesh* m, const char* null_msg) {
+    if (!m) return fail(c, SWR_ERR_INVALID_ARG, null_msg);
+    if (m->transient) return fail(c, SWR_ERR_INVALID_ARG, "a transient mesh (swr_render_mesh_arrays) cannot be deformed, copied or read back");
+    if (m->owner != c) return fail(c, SWR_ERR_INVALID_ARG, "the mesh belongs to another context");
+    return SWR_OK;
+}
+
+bool batch_reads(const std::vector<DrawCmd>& draws, const swr_mesh* m) {
+    for (const DrawCmd& d : draws) if (d.mesh == m) return true;
+    return false;
+}
+
+// Everything that must happen before a kernel may WRITE dst's vertices; returns the stream it runs on.
+//   A. immediate-mode semantics: draws recorded so far that reference dst are launched first (they see the old vertices) -- and only
+//      then: a loop that deforms sixteen players and draws them stays one batch;
+//   B. an optimistic batch in flight that references dst may be replayed later (validate_locked), and a replay runs the front end
+//      again: it must read the vertices the batch saw, so the streams are drained and the batches validated before the first write
+//      (transient meshes solve the same problem through c->garbage: their buffers are not reused before the streams were idle).
+//      A loop that presents every frame has retired those batches in swr_present_wait: nothing to wait for there.
+// The deform runs where make_mesh uploads (use_front_stream): only front-end kernels read a mesh, and every front end issued later
+// is behind it -- on the front stream by stream order, on the context's stream through f_tail_pending (execute_batch).
+int deform_begin(swr_context* c, const swr_mesh* dst, hipStream_t* stream) {
+    int rc;
+    if (batch_reads(c->draws, dst) && (rc = flush_locked(c))) return rc;
+    bool in_flight = false;
+    for (const Batch& b : c->inflight) in_flight = in_flight || batch_reads(b.draws, dst);
+    if (in_flight && (rc = sync_locked(c))) return rc;
+    if ((rc = ensure_front_stream(c))) return rc;
+    *stream = use_front_stream(c);
+    return SWR_OK;
+}
+
+// ... and after it: what the host knows about dst's old vertices is void.
+//   C. readers on the ray stream (swr_raycast, swr_character_update, swr_mesh_readback) are ordered behind swr_mesh::uploaded: it is
+//      recorded again behind the deform.  The query entry points return only after their kernels finished (they wait for their own
+//      result under the context mutex), so no ray-stream reader of dst is in flight when a deform is issued;
+//   D. the bounding sphere is computed again on first use (swr_mesh_bounds, swr_render_mesh_culled follow the pose);
+//   E. the host-side box is gone: band_rejects keeps the draw on every rank (conservative and correct).
+int deform_end(swr_context* c, swr_mesh* dst, hipStream_t stream) {
+    SWR_HIP(c, hipEventRecord(dst->uploaded, stream));
+    dst->upload_seen = false;
+    dst->bounds_ready = false;
+    dst->has_box = false;
+    return SWR_OK;
+}
+
+// A palette's way to the device without a wait (F): the first slot whose last kernel is over, else a new one.
+int palette_slot(swr_context* c, size_t bytes, PaletteSlot** out) {
+    PaletteSlot* s = nullptr;
+    const size_t n = c->palettes.size();
+    for (size_t k = 0; k < n && !s; ++k) {
+        PaletteSlot& q = c->palettes[(c->palette_next + k) % n];
+        if (q.busy && hipEventQuery(q.done) == hipSuccess) q.busy = false;
+        if (!q.busy) { s = &q; c->palette_next = (c->palette_next + k + 1) % n; }
+    }
+    if (!s && n < SWR_PALETTE_SLOTS_MAX) {
+        c->palettes.emplace_back();
+        s = &c->palettes.back();
+        SWR_HIP(c, hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+    }
+    if (!s) {       // back-pressure: SWR_PALETTE_SLOTS_MAX palettes queued and none read yet
+        s = &c->palettes[c->palette_next % n];
+        c->palette_next = (c->palette_next + 1) % n;
+        SWR_HIP(c, hipEventSynchronize(s->done));
+        s->busy = false;
+    }
+    // (a free slot's buffers are idle: growing them frees nothing a kernel reads)
+    if (s->host.cap < bytes) SWR_HIP(c, ensure_pinned(s->host, std::max<size_t>(bytes, 4096)));
+    int rc = ensure(c, s->dev, std::max<size_t>(bytes, 4096)); if (rc) return rc;
+    *out = s;
+    return SWR_OK;
+}
+}  // namespace
+
+int swr_mesh_create_like(swr_context* c, const swr_mesh* src, swr_mesh** out) {
+    SWR_ENTER(c);
+    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "out is null");
+    int rc = deform_mesh_check(c, src, "the source mesh is null"); if (rc) return rc;
+    if ((rc = ensure_front_stream(c))) return rc;
+    swr_mesh* m = new swr_mesh();
+    m->n_verts = src->n_verts; m->n_idx = src->n_idx; m->owner = c;
+    memcpy(m->box_lo, src->box_lo, sizeof m->box_lo); memcpy(m->box_hi, src->box_hi, sizeof m->box_hi);
+    m->has_box = src->has_box;
+    const size_t vbytes = (size_t)src->n_verts * sizeof(swr_vertex), ibytes = (size_t)src->n_idx * 2;
+    // behind src's upload or its last deform, on their stream: the arrays do not cross PCIe again
+    const hipStream_t s = use_front_stream(c);
+    hipError_t e = hipSuccess;
+    if (vbytes) { e = hipMalloc((void**)&m->d_verts, vbytes); if (e == hipSuccess) m->cap_verts = vbytes; }
+    if (e == hipSuccess && ibytes) { e = hipMalloc((void**)&m->d_idx, ibytes + 8); if (e == hipSuccess) m->cap_idx = ibytes + 8; }
+    if (e == hipSuccess && vbytes) e = hipMemcpyAsync(m->d_verts, src->d_verts, vbytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && ibytes) e = hipMemcpyAsync(m->d_idx, src->d_idx, ibytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->uploaded, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(m->uploaded, s);
+    if (e != hipSuccess) {
+        destroy_mesh(m);
+        c->err = std::string("mesh copy failed: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+    }
+    *out = m;
+    return SWR_OK;
+}
+
+int swr_mesh_readback(swr_context* c, const swr_mesh* mesh, swr_vertex* out) {
+    SWR_ENTER(c);
+    int rc = deform_mesh_check(c, mesh, "the mesh is null"); if (rc) return rc;
+    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "the destination is null");
+    if (mesh->n_verts == 0) return SWR_OK;
+    // a reader on the ray stream: behind the upload or the last deform (swr_mesh::uploaded) and behind nothing else -- recorded draws
+    // are not flushed, a frame in flight is not waited for
+    if ((rc = ensure_ray_stream(c))) return rc;
+    swr_mesh* m = const_cast<swr_mesh*>(mesh);
+    if (!m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
+    SWR_HIP(c, hipMemcpyAsync(out, m->d_verts, (size_t)m->n_verts * sizeof(swr_vertex), hipMemcpyDeviceToHost, c->ray_stream));
+    SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
+    return SWR_OK;
+}
+
+int swr_mesh_blend(swr_context* c, swr_mesh* dst, const swr_mesh* a, const swr_mesh* b, float t) {
+    SWR_ENTER(c);
+    int rc;
+    if ((rc = deform_mesh_check(c, dst, "the destination mesh is null"))) return rc;
+    if ((rc = deform_mesh_check(c, a, "key frame a is null"))) return rc;
+    if ((rc = deform_mesh_check(c, b, "key frame b is null"))) return rc;
+    if (dst == a || dst == b) return fail(c, SWR_ERR_INVALID_ARG, "the destination mesh is one of the key frames (make a target with swr_mesh_create_like)");
+    if (a->n_verts != dst->n_verts || b->n_verts != dst->n_verts) return fail(c, SWR_ERR_INVALID_ARG, "the key frames and the destination must have equal vertex counts");
+    if (dst->n_verts == 0) return SWR_OK;
+    hipStream_t s = nullptr;
+    if ((rc = deform_begin(c, dst, &s))) return rc;
+    const uint32_t n_words = 3u * (uint32_t)dst->n_verts;
+    hipLaunchKernelGGL(k_mesh_blend, dim3((n_words + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK), dim3(SWR_DEFORM_BLOCK), 0, s,
+                       reinterpret_cast<const float4*>(a->d_verts), reinterpret_cast<const float4*>(b->d_verts),
+                       reinterpret_cast<float4*>(dst->d_verts), n_words, t);
+    SWR_HIP(c, hipGetLastError());
+    return deform_end(c, dst, s);
+}
+
+int swr_mesh_set_skin(swr_context* c, swr_mesh* m, const uint16_t* joints4, const float* weights4) {
+    SWR_ENTER(c);
+    int rc = deform_mesh_check(c, m, "the mesh is null"); if (rc) return rc;
+    if ((joints4 == nullptr) != (weights4 == nullptr)) return fail(c, SWR_ERR_INVALID_ARG, "pass both joints4 and weights4, or NULL for both (which removes the attributes)");
+    if (!joints4) {
+        // (hipFree waits for the device: a queued k_mesh_skin has read them by then)
+        if (m->d_joints) SWR_HIP(c, hipFree(m->d_joints));
+        m->d_joints = nullptr;
+        if (m->d_weights) SWR_HIP(c, hipFree(m->d_weights));
+        m->d_weights = nullptr;
+        m->max_joint = -1; m->has_skin = false;
+        return SWR_OK;
+    }
+    const size_t nv = (size_t)m->n_verts;
+    int max_joint = -1;
+    for (size_t i = 0; i < 4 * nv; ++i) max_joint = std::max(max_joint, (int)joints4[i]);
+    if ((rc = ensure_front_stream(c))) return rc;
+    if (nv) {
+        // a second call replaces the attributes in place, on the stream the skinning kernels run on (behind those queued so far)
+        if (!m->d_joints) SWR_HIP(c, hipMalloc((void**)&m->d_joints, nv * sizeof(ushort4)));
+        if (!m->d_weights) SWR_HIP(c, hipMalloc((void**)&m->d_weights, nv * sizeof(float4)));
+        const hipStream_t s = use_front_stream(c);
+        SWR_HIP(c, hipMemcpyAsync(m->d_joints, joints4, nv * sizeof(ushort4), hipMemcpyHostToDevice, s));
+        SWR_HIP(c, hipMemcpyAsync(m->d_weights, weights4, nv * sizeof(float4), hipMemcpyHostToDevice, s));
+    }
+    m->max_joint = max_joint; m->has_skin = true;
+    return SWR_OK;
+}
+
+int swr_mesh_skin(swr_context* c, swr_mesh* dst, const swr_mesh* src, const float* palette, int n_joints) {
+    SWR_ENTER(c);
+    int rc;
+    if ((rc = deform_mesh_check(c, dst, "the destination mesh is null"))) return rc;
+    if ((rc = deform_mesh_check(c, src, "the source mesh is null"))) return rc;
+    if (!palette) return fail(c, SWR_ERR_INVALID_ARG, "the palette is null");
+    if (dst == src) return fail(c, SWR_ERR_INVALID_ARG, "the destination mesh is the source (make a target with swr_mesh_create_like)");
+    if (src->n_verts != dst->n_verts) return fail(c, SWR_ERR_INVALID_ARG, "the source and the destination must have equal vertex counts");
+    if (!src->has_skin) return fail(c, SWR_ERR_INVALID_ARG, "the source mesh has no skin attributes (swr_mesh_set_skin)");
+    if (n_joints > 65535) return fail(c, SWR_ERR_UNSUPPORTED, "a palette holds at most 65535 joints (16-bit joint indices)");
+    if (n_joints <= src->max_joint) return fail(c, SWR_ERR_INVALID_ARG, "n_joints must exceed the largest joint index the source's skin attributes use");
+    if (dst->n_verts == 0) return SWR_OK;
+    hipStream_t s = nullptr;
+    if ((rc = deform_begin(c, dst, &s))) return rc;
+    const size_t bytes = (size_t)n_joints * 64;
+    PaletteSlot* slot = nullptr;
+    if ((rc = palette_slot(c, bytes, &slot))) return rc;
+    memcpy(slot->host.p, palette, bytes);
+    SWR_HIP(c, hipMemcpyAsync(slot->dev.p, slot->host.p, bytes, hipMemcpyHostToDevice, s));
+    const dim3 grid(((uint32_t)dst->n_verts + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK), block(SWR_DEFORM_BLOCK);
+    hipLaunchKernelGGL(k_mesh_skin, grid, block, 0, s, (const swr_vertex*)src->d_verts, (const ushort4*)src->d_joints,
+                       (const float4*)src->d_weights, (const float*)slot->dev.p, dst->d_verts, (uint32_t)dst->n_verts, c->nm_flags);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipEventRecord(slot->done, s));
+    slot->busy = true;
+    return deform_end(c, dst, s);
 }
 
 int swr_set_state(swr_context* c, float near_clip, float far_clip, int debug_mode) {

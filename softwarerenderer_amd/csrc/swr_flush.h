@@ -12,6 +12,8 @@ void destroy_mesh(swr_mesh* m) {
     if (m->d_idx) (void)hipFree(m->d_idx);
     if (m->d_bounds) (void)hipFree(m->d_bounds);
     if (m->uploaded) (void)hipEventDestroy(m->uploaded);
+    if (m->d_joints) (void)hipFree(m->d_joints);
+    if (m->d_weights) (void)hipFree(m->d_weights);
     delete m;
 }
 // A transient mesh (swr_render_mesh_arrays: the reference's RenderMesh(vertices, indices, ...) makes one per call) whose batch is
@@ -783,7 +785,7 @@ int make_mesh(swr_context* c, const swr_vertex* v, int nv, const uint16_t* idx, 
         }
     }
     if (!m) m = new swr_mesh();
-    m->n_verts = nv; m->n_idx = ni; m->transient = transient;
+    m->n_verts = nv; m->n_idx = ni; m->transient = transient; m->owner = c;
     if (nv > 0) {                                  // exact AABB (min / max only): input to band_rejects
         bool ok = true;
         for (int k = 0; k < 3; ++k) { m->box_lo[k] = v[0].position[k]; m->box_hi[k] = v[0].position[k]; }

@@ -15,6 +15,12 @@ struct swr_mesh {
     bool has_box = false;
     hipEvent_t uploaded = nullptr;            // retained meshes: recorded behind the upload, for readers on another stream (swr_raycast)
     bool upload_seen = false;                 // ... the ray stream has been ordered behind it
+    swr_context* owner = nullptr;             // the context that made it (the deform calls refuse another context's mesh)
+    // static skin attributes (swr_mesh_set_skin): four joint indices and four weights per vertex, uploaded once
+    ushort4* d_joints = nullptr;
+    float4* d_weights = nullptr;
+    bool has_skin = false;                    // (a mesh without vertices has the attributes and no arrays)
+    int max_joint = -1;                       // largest joint index used (host, at the upload): swr_mesh_skin needs a longer palette
 };
 struct swr_texture {
     uint8_t* d_rgba = nullptr;
@@ -78,6 +84,9 @@ struct EventSpan { int stage; hipEvent_t a, b; };
 #define SWR_SLOTS 3
 struct PinnedBuf { void* p = nullptr; size_t cap = 0; };      // a pinned host block (ensure_pinned)
 struct FrameSlot { PinnedBuf host; hipEvent_t done = nullptr; bool busy = false; };
+// one joint palette on its way to the device (swr_mesh_skin): pinned staging, its device copy, an event behind the kernel that reads it
+struct PaletteSlot { PinnedBuf host; DevBuf dev; hipEvent_t done = nullptr; bool busy = false; };
+#define SWR_PALETTE_SLOTS_MAX 256
 
 // Everything of a batch that its raster kernel reads (or that a front-end kernel and the raster kernel share).  With frames
 // pipelined two sets alternate per flush, so the front end of flush N+1 never writes what the raster kernel of flush N reads;
@@ -239,6 +248,11 @@ struct swr_context {
     DevBuf d_ray, d_ray_best;                  // rays | targets | hit records; the pairs' keys, all SWR_RAY_NO_HIT between calls (k_ray_finish)
     PinnedBuf ray_host;                        // staging block of small queries
     DevBuf d_char;                             // swr_character_update: controllers | inputs | ring | targets | work | active | rays x 2 | results
+
+    // swr_mesh_skin: a palette's slot is free again once the kernel that read it is over (event query, no wait); the list grows while
+    // none is free, so several calls per frame never overwrite a palette a queued kernel has not read
+    std::vector<PaletteSlot> palettes;
+    size_t palette_next = 0;
 
     int profiling = 0;                         // 0 off, 1 every stage, 2 only the raster kernel (2 events per flush)
     std::vector<EventSpan> spans;

@@ -7,6 +7,9 @@ Host-side: it only PRODUCES inputs of the hot path.  What is reproduced from Mod
   * vertex de-duplication on (position, normal, uv) in first-seen order, 16-bit indices        :165-218
   * PostProcessSteps.FlipUVs (v -> 1 - v), white default vertex colour, diffuse texture path  :145-150,184-186,240-270
   * a directory of model files = animation frames sorted by name                              :79-115
+Beyond the reference (build-defined): a glTF primitive's JOINTS_0 / WEIGHTS_0 and a skin's inverseBindMatrices are
+read and kept beside the vertices they belong to (Mesh.joints, Mesh.weights, Model.Skins), the inputs of Mesh.SkinFrom; animation
+channels are not sampled -- the caller supplies the joint matrices.  Model.FramePair names the two key frames around a time.
 Where Assimp's own numerics matter (normal generation when a mesh has none, TRS composition) this loader is
 build-defined -- AssimpNet 5.0.0-beta1 is not available, so those results are unpinned.
 One deliberate difference: the reference wraps its ushort index silently past 65,535 unique vertices
@@ -30,12 +33,16 @@ MAX_VERTS = 65535
 class Mesh:
     """public class Mesh (ModelLoader.cs:43-60)."""
 
-    def __init__(self, vertices: np.ndarray, indices: np.ndarray, material: Optional[dict] = None, root: str = ""):
+    def __init__(self, vertices: np.ndarray, indices: np.ndarray, material: Optional[dict] = None, root: str = "",
+                 joints: Optional[np.ndarray] = None, weights: Optional[np.ndarray] = None, skin: Optional[int] = None):
         self.Vertices = vertices
         self.BaseVertices = vertices.copy()
         self.Indices = indices
         self.Material = material or {}
         self.ModelRootPath = root
+        self.joints = joints               # (n, 4) uint16 indices into the skin's joint list, or None: JOINTS_0
+        self.weights = weights             # (n, 4) float32, as stored (not renormalised), or None: WEIGHTS_0
+        self.Skin = skin                   # index into Model.Skins, or None
         self._gpu = None
 
     def Upload(self, device):
@@ -43,6 +50,8 @@ class Mesh:
         from .rasterizer import Mesh as GpuMesh
         if self._gpu is None:
             self._gpu = GpuMesh(device, self.Vertices, self.Indices)
+            if self.joints is not None and self.weights is not None:
+                self._gpu.SetSkin(self.joints, self.weights)
         return self._gpu
 
 
@@ -104,11 +113,17 @@ def _face_normals(pos: np.ndarray, tris: np.ndarray) -> np.ndarray:
     return (n / ln).astype(F)
 
 
-def _build_meshes(pos, nrm, uv, col, tri_idx, material, root) -> List[Mesh]:
-    """De-duplicate on (position, normal, uv) in first-seen order (ModelLoader.cs:165-218); split at 65,535 vertices."""
+def _build_meshes(pos, nrm, uv, col, tri_idx, material, root, joints=None, weights=None, skin=None) -> List[Mesh]:
+    """De-duplicate on (position, normal, uv) in first-seen order (ModelLoader.cs:165-218); split at 65,535 vertices.  Skin
+    attributes (joints, weights: four per source vertex) follow the vertex they belong to: they join the key, so two corners that agree
+    in position, normal and uv and differ in their influences stay two vertices; without them the key is the reference's."""
     meshes: List[Mesh] = []
     keys = np.concatenate([pos, nrm, uv], axis=1).astype(F)
     key_bytes = keys.view(np.uint8).reshape(keys.shape[0], -1)
+    skinned = joints is not None and weights is not None
+    if skinned:
+        key_bytes = np.concatenate([key_bytes, np.ascontiguousarray(joints, dtype=np.uint16).view(np.uint8).reshape(keys.shape[0], -1),
+                                    np.ascontiguousarray(weights, dtype=F).view(np.uint8).reshape(keys.shape[0], -1)], axis=1)
     table: Dict[bytes, int] = {}
     verts: List[int] = []
     idx: List[int] = []
@@ -119,7 +134,11 @@ def _build_meshes(pos, nrm, uv, col, tri_idx, material, root) -> List[Mesh]:
         v = np.zeros(len(verts), dtype=VERTEX_DTYPE)
         sel = np.asarray(verts, dtype=np.int64)
         v["position"], v["uv"], v["normal"], v["color"] = pos[sel], uv[sel], nrm[sel], col[sel]
-        meshes.append(Mesh(v, np.asarray(idx, dtype=np.uint16), material, root))
+        if skinned:
+            meshes.append(Mesh(v, np.asarray(idx, dtype=np.uint16), material, root, np.ascontiguousarray(joints[sel], dtype=np.uint16),
+                               np.ascontiguousarray(weights[sel], dtype=F), skin))
+        else:
+            meshes.append(Mesh(v, np.asarray(idx, dtype=np.uint16), material, root))
 
     for tri in tri_idx.reshape(-1, 3):
         new = sum(1 for vi in tri if key_bytes[vi].tobytes() not in table)
@@ -184,10 +203,27 @@ class _Gltf:
         return out
 
 
-def _load_gltf(path: str) -> List[Mesh]:
+def _gltf_skins(g: "_Gltf") -> List[dict]:
+    """The document's skins: {"Name", "Joints": node indices, "InverseBindMatrices": (n, 4, 4) float32}.  glTF stores the matrices
+    column-major for column vectors; read row-major they ARE the row-vector matrices (as _node_matrix reads a node's).  A skin
+    without the accessor has identities."""
+    out = []
+    for s in g.doc.get("skins", []):
+        joints = [int(j) for j in s.get("joints", [])]
+        if "inverseBindMatrices" in s:
+            ibm = g.accessor(s["inverseBindMatrices"]).astype(F).reshape(-1, 4, 4)
+        else:
+            ibm = np.tile(np.eye(4, dtype=F), (len(joints), 1, 1))
+        out.append({"Name": s.get("name", ""), "Joints": joints, "InverseBindMatrices": np.ascontiguousarray(ibm)})
+    return out
+
+
+def _load_gltf(path: str, skins_out: Optional[list] = None) -> List[Mesh]:
     g = _Gltf(path)
     doc = g.doc
     meshes: List[Mesh] = []
+    if skins_out is not None:
+        skins_out.extend(_gltf_skins(g))
 
     def process(node_i: int, parent: np.ndarray):
         node = doc["nodes"][node_i]
@@ -212,8 +248,12 @@ def _load_gltf(path: str) -> List[Mesh]:
                 if "COLOR_0" in att:
                     c = g.accessor(att["COLOR_0"]).astype(F)
                     col[:, :c.shape[1]] = c
+                joints = weights = None
+                if "JOINTS_0" in att and "WEIGHTS_0" in att:
+                    joints = g.accessor(att["JOINTS_0"]).astype(np.uint16)[:, :4]        # u8 or u16 indices into the skin's joint list
+                    weights = g.accessor(att["WEIGHTS_0"]).astype(F)[:, :4]               # float, or normalised u8 / u16 (accessor)
                 meshes.extend(_build_meshes(_transform_points(pos, glob), _transform_normals(nrm, rot), uv, col, tri,
-                                            g.material(prim.get("material")), g.root))
+                                            g.material(prim.get("material")), g.root, joints, weights, node.get("skin")))
         for ch in node.get("children", []):
             process(ch, glob)                                                  # :296-299
 
@@ -285,18 +325,31 @@ class Model:
         self.Meshes: List[Mesh] = []
         self.Lights: list = []             # Light.cs is dead data for the renderer
         self.AnimationFrames: List["Model"] = []
+        self.Skins: List[dict] = []        # glTF skins (build-defined): joint node indices and inverse bind matrices, see _gltf_skins
+
+    def FramePair(self, time: float, fps: float = 30.0):
+        """(i, j, t): the key frames AnimationFrames[i] and [j] around `time` seconds at `fps` frames a second, and the blend
+        factor t in [0, 1) as a float32 (a fraction that would round up to 1.0 is the float32 just below it) -- Mesh.BlendFrom's
+        caller-side helper.  Frame k = floor(time * fps) is where PlayAnimation
+        (ModelLoader.cs:331-348) stands after `time`; it wraps as the reference's index does, so the last frame blends into the first."""
+        n = len(self.AnimationFrames)
+        if n == 0:
+            raise ValueError("the model has no animation frames")
+        f = float(time) * float(fps)
+        k = int(np.floor(f))
+        return k % n, (k + 1) % n, min(F(f - k), np.nextafter(F(1.0), F(0.0)))
 
     def LoadModel(self, file_path: str) -> "Model":
         path = os.path.abspath(file_path)
         cached = Model._model_cache.get(path)
         if cached is not None:                                                  # ModelLoader.cs:80-86,118-124
-            self.Meshes, self.Lights, self.AnimationFrames = cached.Meshes, cached.Lights, cached.AnimationFrames
+            self.Meshes, self.Lights, self.AnimationFrames, self.Skins = cached.Meshes, cached.Lights, cached.AnimationFrames, cached.Skins
             return self
         if os.path.isdir(path):                                                 # a directory = animation frames, :79-115
             files = sorted(f for f in os.listdir(path) if os.path.splitext(f)[1].lower() in Model.SUPPORTED)
             self.AnimationFrames = [Model()._load_single(os.path.join(path, f)) for f in files]
             if self.AnimationFrames:
-                self.Meshes, self.Lights = self.AnimationFrames[0].Meshes, self.AnimationFrames[0].Lights
+                self.Meshes, self.Lights, self.Skins = self.AnimationFrames[0].Meshes, self.AnimationFrames[0].Lights, self.AnimationFrames[0].Skins
         elif os.path.isfile(path):
             self._load_single(path)
         else:
@@ -307,7 +360,8 @@ class Model:
     def _load_single(self, path: str) -> "Model":
         ext = os.path.splitext(path)[1].lower()
         if ext == ".gltf":
-            self.Meshes = _load_gltf(path)
+            self.Skins = []
+            self.Meshes = _load_gltf(path, self.Skins)
         elif ext == ".obj":
             self.Meshes = _load_obj(path)
         else:

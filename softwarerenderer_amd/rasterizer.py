@@ -983,6 +983,45 @@ class Mesh:
         self._dev._ck(self._dev._lib.swr_mesh_bounds(self._dev._ctx, self._h, _fptr(out)))
         return out
 
+    # ---- deforming meshes (build-defined)
+    def Like(self) -> "Mesh":
+        """swr_mesh_create_like: a retained mesh with this one's vertices and indices, copied on the GPU -- a deform target."""
+        m = Mesh.__new__(Mesh)
+        m._dev, m.n_vertices, m.n_indices, m._h = self._dev, self.n_vertices, self.n_indices, C.c_void_p()
+        self._dev._ck(self._dev._lib.swr_mesh_create_like(self._dev._ctx, self._h, C.byref(m._h)))
+        return m
+
+    def Read(self) -> np.ndarray:
+        """swr_mesh_readback: the vertices as the device holds them (VERTEX_DTYPE); flushes nothing."""
+        out = np.zeros(self.n_vertices, dtype=VERTEX_DTYPE)
+        self._dev._ck(self._dev._lib.swr_mesh_readback(self._dev._ctx, self._h, out.ctypes.data))
+        return out
+
+    def BlendFrom(self, a: "Mesh", b: "Mesh", t: float) -> "Mesh":
+        """swr_mesh_blend: this mesh's vertices = a * (1 - t) + b * t, every scalar, in the build's Lerp model; t is not clamped."""
+        self._dev._ck(self._dev._lib.swr_mesh_blend(self._dev._ctx, self._h, a._h if a is not None else None,
+                                                    b._h if b is not None else None, C.c_float(float(np.float32(t)))))
+        return self
+
+    def SetSkin(self, joints, weights) -> "Mesh":
+        """swr_mesh_set_skin: four joint indices (uint16) and four weights (float32) per vertex, retained; (None, None) removes them."""
+        if joints is None and weights is None:
+            self._dev._ck(self._dev._lib.swr_mesh_set_skin(self._dev._ctx, self._h, None, None))
+            return self
+        j = np.ascontiguousarray(joints, dtype=np.uint16).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if j.size != 4 * self.n_vertices or w.size != 4 * self.n_vertices:
+            raise ValueError("joints and weights must hold four entries per vertex")
+        self._dev._ck(self._dev._lib.swr_mesh_set_skin(self._dev._ctx, self._h, j.ctypes.data, w.ctypes.data))
+        return self
+
+    def SkinFrom(self, src: "Mesh", palette) -> "Mesh":
+        """swr_mesh_skin: this mesh's vertices = src's, skinned by `palette` (n_joints x 4 x 4, row-major for row vectors: glTF's
+        jointMatrix, the caller's) with src's skin attributes, under the device's Transform / TransformNormal model."""
+        p = np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 16)
+        self._dev._ck(self._dev._lib.swr_mesh_skin(self._dev._ctx, self._h, src._h if src is not None else None, _fptr(p), int(p.shape[0])))
+        return self
+
     def Dispose(self):
         if self._h:
             self._dev._ck(self._dev._lib.swr_mesh_destroy(self._dev._ctx, self._h))
