@@ -253,6 +253,16 @@ namespace SoftwareRenderer
         [DllImport(Lib)] public static extern int swr_mesh_blend(IntPtr ctx, IntPtr dst, IntPtr a, IntPtr b, float t);
         [DllImport(Lib)] public static extern int swr_mesh_set_skin(IntPtr ctx, IntPtr src, ushort* joints4, float* weights4);
         [DllImport(Lib)] public static extern int swr_mesh_skin(IntPtr ctx, IntPtr dst, IntPtr src, Matrix4x4* palette, int nJoints);
+        // skeletal animation (include/swr.h "SKELETAL ANIMATION"): clips to palettes on the GPU, one skin launch for a crowd
+        [DllImport(Lib)] public static extern int swr_skeleton_create(IntPtr ctx, int nNodes, int* parent, Matrix4x4* restLocal, float* restT, float* restR, float* restS, int nJoints, int* jointNode, Matrix4x4* inverseBind, out IntPtr skeleton);
+        [DllImport(Lib)] public static extern int swr_skeleton_destroy(IntPtr ctx, IntPtr skeleton);
+        [DllImport(Lib)] public static extern int swr_skeleton_add_clip(IntPtr ctx, IntPtr skeleton, SwrAnimChannel* channels, int nChannels, out int clipIndex);
+        [DllImport(Lib)] public static extern int swr_pose_set_create(IntPtr ctx, int nInstances, int nJoints, out IntPtr set);
+        [DllImport(Lib)] public static extern int swr_pose_set_destroy(IntPtr ctx, IntPtr set);
+        [DllImport(Lib)] public static extern int swr_pose_set_sample(IntPtr ctx, IntPtr set, IntPtr skeleton, SwrPoseRequest* requests, int n);
+        [DllImport(Lib)] public static extern int swr_pose_set_upload(IntPtr ctx, IntPtr set, int first, int n, Matrix4x4* palettes);
+        [DllImport(Lib)] public static extern int swr_pose_set_readback(IntPtr ctx, IntPtr set, Matrix4x4* outPalettes);
+        [DllImport(Lib)] public static extern int swr_mesh_skin_batch(IntPtr ctx, int n, IntPtr* dst, IntPtr* src, IntPtr set, int* instance);
         [DllImport(Lib)] public static extern int swr_set_state(IntPtr ctx, float nearClip, float farClip, int debugMode);
         [DllImport(Lib)] public static extern int swr_initialize_tile_locks(IntPtr ctx, int width, int height);
         [DllImport(Lib)] public static extern int swr_render_mesh(IntPtr ctx, IntPtr mesh, Matrix4x4* model, Matrix4x4* view, Matrix4x4* projection, int program, SwrUniforms* uniforms, IntPtr texture, int cullMode, int depthTest, int blendMode);
@@ -571,6 +581,18 @@ namespace SoftwareRenderer
                 SwrContext.Check(Native.swr_mesh_skin(SwrContext.Handle, dst, Rasterizer.Retain(Source), p, palette.Length));
         }
 
+        /// targets[k].Target = targets[k].Source skinned by the palette of instances[k] of `set`, all of them in ONE kernel launch: word
+        /// for word what Skin gives with that palette.  Two targets may share a Source or an instance.
+        public static void SkinBatch(DeformedMesh[] targets, PoseSetNative set, int[] instances)
+        {
+            if (instances.Length != targets.Length) throw new ArgumentException("one instance per target");
+            var d = new IntPtr[Math.Max(targets.Length, 1)];
+            var s = new IntPtr[Math.Max(targets.Length, 1)];
+            for (int k = 0; k < targets.Length; ++k) { d[k] = targets[k].dst; s[k] = Rasterizer.Retain(targets[k].Source); }
+            fixed (IntPtr* pd = d) fixed (IntPtr* ps = s) fixed (int* pi = instances)
+                SwrContext.Check(Native.swr_mesh_skin_batch(SwrContext.Handle, targets.Length, pd, ps, set.Handle, pi));
+        }
+
         /// The pose as the device holds it.
         public Shaders.VertexInput[] Read()
         {
@@ -579,6 +601,135 @@ namespace SoftwareRenderer
                 SwrContext.Check(Native.swr_mesh_readback(SwrContext.Handle, dst, v));
             return outv;
         }
+    }
+
+    // ---------------------------------------------------------------- skeletal animation ----
+    // Build-defined (DESIGN.md section 29; the reference has no skeletal animation): a skeleton with its clips lives on the GPU, a
+    // whole crowd is posed there in one call (PoseSetNative.Sample), and every mesh of the crowd is skinned from the pose set in one
+    // kernel launch (DeformedMesh.SkinBatch).  Key search, Quaternion.Lerp (the NORMALISED lerp, not a slerp), the S x R x T compose
+    // and the hierarchy's products have one definition for every numerics build; only the skinning follows the Transform flags.
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct SwrAnimChannel            // swr_anim_channel: one glTF animation channel with its sampler
+    {
+        public int Node;
+        public int Path;                           // 0 translation, 1 rotation, 2 scale
+        public int Interpolation;                  // 0 STEP, 1 LINEAR (2, CUBICSPLINE, is refused)
+        public int NKeys;
+        public float* Times;                       // NKeys, non-decreasing
+        public float* Values;                      // NKeys x 3 (x 4 for a rotation, xyzw)
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SwrPoseRequest                   // swr_pose_request (20 bytes)
+    {
+        public int ClipA;
+        public float TimeA;
+        public int ClipB;                          // -1: none
+        public float TimeB;
+        public float Weight;                       // used as it is, not clamped
+    }
+
+    /// One channel of a clip in managed arrays (SkeletonNative.AddClip pins them for the call).
+    public sealed class AnimationChannel
+    {
+        public int Node, Path, Interpolation = 1;
+        public float[] Times = Array.Empty<float>();
+        public float[] Values = Array.Empty<float>();
+    }
+
+    public sealed unsafe class SkeletonNative : IDisposable
+    {
+        internal IntPtr Handle;
+        public readonly int NodeCount, JointCount;
+
+        /// parent[i] < i or -1 (several roots are allowed); restT / restS three floats per node, restR four (xyzw); jointNode the
+        /// node each joint is.  Matrices are System.Numerics' own layout (row-major, row vectors).
+        public SkeletonNative(int[] parent, Matrix4x4[] restLocal, float[] restT, float[] restR, float[] restS, int[] jointNode, Matrix4x4[] inverseBind)
+        {
+            NodeCount = parent.Length; JointCount = jointNode.Length;
+            if (restLocal.Length != NodeCount || restT.Length != 3 * NodeCount || restR.Length != 4 * NodeCount || restS.Length != 3 * NodeCount || inverseBind.Length != JointCount)
+                throw new ArgumentException("the skeleton's arrays do not match its node and joint counts");
+            fixed (int* p = parent) fixed (Matrix4x4* l = restLocal) fixed (float* t = restT) fixed (float* r = restR) fixed (float* s = restS)
+            fixed (int* j = jointNode) fixed (Matrix4x4* b = inverseBind)
+                SwrContext.Check(Native.swr_skeleton_create(SwrContext.Handle, NodeCount, p, l, t, r, s, JointCount, j, b, out Handle));
+        }
+
+        /// The clip's index.  A load-time call: it may reallocate the skeleton's clips and wait for the device.
+        public int AddClip(IReadOnlyList<AnimationChannel> channels)
+        {
+            var recs = new SwrAnimChannel[Math.Max(channels.Count, 1)];
+            var pins = new List<GCHandle>();
+            try
+            {
+                for (int k = 0; k < channels.Count; ++k)
+                {
+                    var c = channels[k];
+                    if (c.Values.Length != c.Times.Length * (c.Path == 1 ? 4 : 3))
+                        throw new ArgumentException("a channel's values must hold 3 floats per key (4 for a rotation)");
+                    var ht = GCHandle.Alloc(c.Times, GCHandleType.Pinned); pins.Add(ht);
+                    var hv = GCHandle.Alloc(c.Values, GCHandleType.Pinned); pins.Add(hv);
+                    recs[k] = new SwrAnimChannel { Node = c.Node, Path = c.Path, Interpolation = c.Interpolation, NKeys = c.Times.Length,
+                                                   Times = (float*)ht.AddrOfPinnedObject(), Values = (float*)hv.AddrOfPinnedObject() };
+                }
+                int index;
+                fixed (SwrAnimChannel* r = recs)
+                    SwrContext.Check(Native.swr_skeleton_add_clip(SwrContext.Handle, Handle, r, channels.Count, out index));
+                return index;
+            }
+            finally { foreach (var h in pins) h.Free(); }
+        }
+
+        public void Dispose()
+        {
+            if (Handle != IntPtr.Zero) Native.swr_skeleton_destroy(SwrContext.Handle, Handle);
+            Handle = IntPtr.Zero;
+            GC.SuppressFinalize(this);
+        }
+        ~SkeletonNative() { if (Handle != IntPtr.Zero) Native.swr_skeleton_destroy(SwrContext.Handle, Handle); }
+    }
+
+    public sealed unsafe class PoseSetNative : IDisposable
+    {
+        internal IntPtr Handle;
+        public readonly int InstanceCount, JointCount;
+
+        public PoseSetNative(int instances, int joints)
+        {
+            InstanceCount = instances; JointCount = joints;
+            SwrContext.Check(Native.swr_pose_set_create(SwrContext.Handle, instances, joints, out Handle));
+        }
+
+        /// Instance i from requests[i], sampled and composed on the GPU; no host wait.
+        public void Sample(SkeletonNative skeleton, SwrPoseRequest[] requests)
+        {
+            fixed (SwrPoseRequest* r = requests)
+                SwrContext.Check(Native.swr_pose_set_sample(SwrContext.Handle, Handle, skeleton.Handle, r, requests.Length));
+        }
+
+        /// Host-made palettes (JointCount matrices per instance) into instances first, first + 1, ...; no host wait.
+        public void Upload(int first, Matrix4x4[] palettes)
+        {
+            if (palettes.Length % JointCount != 0) throw new ArgumentException("palettes must hold JointCount matrices per instance");
+            fixed (Matrix4x4* p = palettes)
+                SwrContext.Check(Native.swr_pose_set_upload(SwrContext.Handle, Handle, first, palettes.Length / JointCount, p));
+        }
+
+        /// InstanceCount x JointCount matrices as the device holds them.
+        public Matrix4x4[] Read()
+        {
+            var outp = new Matrix4x4[InstanceCount * JointCount];
+            fixed (Matrix4x4* p = outp)
+                SwrContext.Check(Native.swr_pose_set_readback(SwrContext.Handle, Handle, p));
+            return outp;
+        }
+
+        public void Dispose()
+        {
+            if (Handle != IntPtr.Zero) Native.swr_pose_set_destroy(SwrContext.Handle, Handle);
+            Handle = IntPtr.Zero;
+            GC.SuppressFinalize(this);
+        }
+        ~PoseSetNative() { if (Handle != IntPtr.Zero) Native.swr_pose_set_destroy(SwrContext.Handle, Handle); }
     }
 
     // ---------------------------------------------------------------- Physics ----

@@ -436,6 +436,65 @@ int  swr_mesh_set_skin(swr_context* ctx, swr_mesh* src, const uint16_t* joints4,
  * scaled joint (that needs the inverse transpose, which the caller would have to supply as a second palette: not built). */
 int  swr_mesh_skin(swr_context* ctx, swr_mesh* dst, const swr_mesh* src, const float* palette, int n_joints);
 
+/* SKELETAL ANIMATION (build-defined) --------------------------------------------------------------------------
+ * Clips are sampled and joint hierarchies evaluated on the GPU for a whole crowd in one call, into a POSE SET (n_instances x n_joints
+ * palettes that stay on the device); every mesh of the crowd is then skinned from the set in one launch (swr_mesh_skin_batch).
+ * ONE definition for every numerics build and either Transform flag: plain float32, no fused multiply-add, sums left to right.
+ *   key search  times T[0 .. n-1] at time t: !(t > T[0]) gives key 0 as stored (a NaN t lands here); t >= T[n-1] gives key n-1; else
+ *               k = the largest index with T[k] <= t and u = (t - T[k]) / (T[k+1] - T[k]).  STEP: key k.  LINEAR: a*(1-u) + b*u per
+ *               scalar for T and S, Quaternion.Lerp(a, b, u) for R -- the NORMALISED lerp, not glTF's spherical one
+ *   two clips   each of T, R, S from clip_a and clip_b (the node's rest value where a clip has no channel), combined by the same two
+ *               lerps at u = weight, unclamped.  clip_b < 0: clip_a alone
+ *   local       a node no channel of the request's clip(s) targets keeps its rest matrix's words; a targeted one is
+ *               S x Matrix4x4.CreateFromQuaternion(R) x T
+ *   hierarchy   world[i] = local[i] x world[parent[i]] (the parent's world finished first; Matrix4x4.Multiply), world = local for a
+ *               root; palette[j] = inverse_bind[j] x world[node[j]]
+ * Matrices are 16 floats, row-major for row vectors; quaternions are xyzw.
+ * ORDER: swr_pose_set_sample, _upload and swr_mesh_skin_batch run on the stream swr_mesh_skin runs on and are ordered among themselves
+ * by it alone; none waits for the device.  swr_pose_set_readback waits for the set's last write only.
+ * LIMITS: n_nodes and n_joints <= 65535, n_instances x n_joints <= 2^24; beyond: SWR_ERR_UNSUPPORTED. */
+typedef struct swr_skeleton swr_skeleton;
+typedef struct swr_pose_set swr_pose_set;
+#define SWR_ANIM_PATH_TRANSLATION 0
+#define SWR_ANIM_PATH_ROTATION    1
+#define SWR_ANIM_PATH_SCALE       2
+#define SWR_ANIM_STEP        0
+#define SWR_ANIM_LINEAR      1
+#define SWR_ANIM_CUBICSPLINE 2        /* refused: SWR_ERR_UNSUPPORTED */
+#define SWR_SKELETON_MAX_NODES 65535
+/* n_keys >= 1 non-decreasing key times; values: n_keys x 3 floats (translation, scale) or x 4 (rotation) */
+typedef struct swr_anim_channel { int32_t node, path, interpolation, n_keys; const float* times; const float* values; } swr_anim_channel;
+/* instance i of a set: clip_a at time_a, blended with clip_b at time_b by weight (clip_b = -1: none) */
+typedef struct swr_pose_request { int32_t clip_a; float time_a; int32_t clip_b; float time_b; float weight; } swr_pose_request;   /* 20 B */
+/* parent[i] < i or -1 (several roots are allowed); rest_local n_nodes x 16, rest_t x 3, rest_r x 4, rest_s x 3; joint_node[j] is the
+ * node joint j is, inverse_bind n_joints x 16.  SWR_ERR_INVALID_ARG: a NULL pointer, n_nodes < 1, n_joints < 0, a parent or a
+ * joint's node out of range.  Uploads and waits: a load-time call. */
+int  swr_skeleton_create(swr_context* ctx, int n_nodes, const int32_t* parent, const float* rest_local, const float* rest_t,
+                         const float* rest_r, const float* rest_s, int n_joints, const int32_t* joint_node, const float* inverse_bind,
+                         swr_skeleton** out);
+int  swr_skeleton_destroy(swr_context* ctx, swr_skeleton* skeleton);
+/* All clips of a skeleton live in one device blob, so one launch serves instances that play different clips.  Adding one may
+ * reallocate the blob and wait for the device: a load-time call.  SWR_ERR_UNSUPPORTED: a CUBICSPLINE channel.  SWR_ERR_INVALID_ARG,
+ * the skeleton unchanged: a node or path out of range, an unknown interpolation, two channels on one (node, path), decreasing (or
+ * NaN) key times, n_keys < 1, a NULL pointer.  n_channels = 0 is a clip that leaves every node at rest. */
+int  swr_skeleton_add_clip(swr_context* ctx, swr_skeleton* skeleton, const swr_anim_channel* channels, int n_channels, int* clip_index);
+int  swr_pose_set_create(swr_context* ctx, int n_instances, int n_joints, swr_pose_set** out);
+int  swr_pose_set_destroy(swr_context* ctx, swr_pose_set* set);
+/* instance i = requests[i] for i < n <= n_instances; the other instances keep their palettes.  The set's n_joints must be the
+ * skeleton's.  SWR_ERR_INVALID_ARG, nothing written: a clip index that is not a clip of the skeleton (clip_b < 0 excepted) */
+int  swr_pose_set_sample(swr_context* ctx, swr_pose_set* set, const swr_skeleton* skeleton, const swr_pose_request* requests, int n);
+/* palettes made on the host: instances first .. first + n - 1, n x n_joints x 16 floats (pinned staging, no wait) */
+int  swr_pose_set_upload(swr_context* ctx, swr_pose_set* set, int first, int n, const float* palettes);
+/* n_instances x n_joints x 16 floats as the device holds them; a set never written reads zeros */
+int  swr_pose_set_readback(swr_context* ctx, const swr_pose_set* set, float* out);
+/* dst[k] = skin(src[k]) by the palette of instance[k], for all k < n in ONE kernel launch: word for word what swr_mesh_skin gives
+ * with that palette.  Two jobs may share a src or an instance.  ORDER: swr_mesh_skin's, applied once over all destinations.
+ * SWR_ERR_INVALID_ARG, nothing written, the context usable: a NULL pointer, a dst that appears twice or is any job's src, unequal
+ * vertex counts, a src without skin attributes, an instance out of range, a set whose n_joints is not above the src's largest joint
+ * index, a mesh or set of another context, a transient mesh.  n = 0 or only empty meshes: SWR_OK, nothing launched. */
+int  swr_mesh_skin_batch(swr_context* ctx, int n, swr_mesh* const* dst, const swr_mesh* const* src, const swr_pose_set* set,
+                         const int32_t* instance);
+
 /* state ≙ public statics Rasterizer.NearClip / FarClip / RenderDebugMode, Rasterizer.cs:20-22 */
 int  swr_set_state(swr_context* ctx, float near_clip, float far_clip, int debug_mode);
 /* Rasterizer.InitializeTileLocks, Rasterizer.cs:69-93: width/height <= 0 -> SWR_ERR_INVALID_ARG */

@@ -12,7 +12,7 @@ Layout:
 Importing the package does not touch the GPU; creating a `Device` does.
 """
 from .rasterizer import (BlendMode, CharacterController, CullMode, DebugMode, DepthReduce, DepthTest, Device, FrustumCuller, MainWindow, Mesh, Physics, PostProgram, Program,  # noqa: F401
-                         Rasterizer, RaycastFaceMask, ShaderProgram, Shaders, Texture, VERTEX_DTYPE, default_uniforms)
+                         PoseSet, Rasterizer, RaycastFaceMask, ShaderProgram, Shaders, Skeleton, Texture, VERTEX_DTYPE, default_uniforms)
 
 __all__ = ["BlendMode", "CharacterController", "CullMode", "DebugMode", "DepthReduce", "DepthTest", "Device", "FrustumCuller", "MainWindow", "Mesh", "Physics", "PostProgram", "Program",
-           "Rasterizer", "RaycastFaceMask", "ShaderProgram", "Shaders", "Texture", "VERTEX_DTYPE", "default_uniforms"]
+           "PoseSet", "Rasterizer", "RaycastFaceMask", "ShaderProgram", "Shaders", "Skeleton", "Texture", "VERTEX_DTYPE", "default_uniforms"]

@@ -102,6 +102,19 @@ class CharacterTrace(C.Structure):  # swr_character_trace (48 bytes)
                 ("chain_attempts", C.c_int32 * 2), ("chain_stop", C.c_int32 * 2)]
 
 
+class AnimChannel(C.Structure):  # swr_anim_channel (32 bytes): one glTF animation channel with its sampler
+    _fields_ = [("node", C.c_int32), ("path", C.c_int32), ("interpolation", C.c_int32), ("n_keys", C.c_int32),
+                ("times", C.c_void_p), ("values", C.c_void_p)]
+
+
+class PoseRequest(C.Structure):  # swr_pose_request (20 bytes)
+    _fields_ = [("clip_a", C.c_int32), ("time_a", C.c_float), ("clip_b", C.c_int32), ("time_b", C.c_float), ("weight", C.c_float)]
+
+
+SWR_ANIM_PATH_TRANSLATION, SWR_ANIM_PATH_ROTATION, SWR_ANIM_PATH_SCALE = 0, 1, 2
+SWR_ANIM_STEP, SWR_ANIM_LINEAR, SWR_ANIM_CUBICSPLINE = 0, 1, 2
+SWR_SKELETON_MAX_NODES = 65535
+
 SWR_RAY_FACES_ALL, SWR_RAY_IGNORE_BACKFACES, SWR_RAY_IGNORE_FRONTFACES, SWR_RAY_CROSS_FUSED = 0, 1, 2, 0x100
 
 # every symbol include/swr.h declares; tests/test_abi.py checks the library exports all of them
@@ -129,6 +142,8 @@ EXPORTS = [
     "swr_texture_update_face_from_depth", "swr_texture_update_face_from_post", "swr_texture_readback_face", "swr_cube_face_view",
     "swr_texture_cube_face", "swr_texture_sample_cube", "swr_texture_sample_cube_depth",
     "swr_mesh_create_like", "swr_mesh_readback", "swr_mesh_blend", "swr_mesh_set_skin", "swr_mesh_skin",
+    "swr_skeleton_create", "swr_skeleton_destroy", "swr_skeleton_add_clip", "swr_pose_set_create", "swr_pose_set_destroy",
+    "swr_pose_set_sample", "swr_pose_set_upload", "swr_pose_set_readback", "swr_mesh_skin_batch",
 ]
 
 _libs = {}
@@ -270,6 +285,15 @@ def load(name: str = None) -> C.CDLL:
         "swr_mesh_blend": (I, [P, P, P, P, F]),
         "swr_mesh_set_skin": (I, [P, P, P, P]),
         "swr_mesh_skin": (I, [P, P, P, fp, I]),
+        "swr_skeleton_create": (I, [P, I, P, P, P, P, P, I, P, P, C.POINTER(P)]),
+        "swr_skeleton_destroy": (I, [P, P]),
+        "swr_skeleton_add_clip": (I, [P, P, P, I, C.POINTER(I)]),
+        "swr_pose_set_create": (I, [P, I, I, C.POINTER(P)]),
+        "swr_pose_set_destroy": (I, [P, P]),
+        "swr_pose_set_sample": (I, [P, P, P, P, I]),
+        "swr_pose_set_upload": (I, [P, P, I, I, P]),
+        "swr_pose_set_readback": (I, [P, P, P]),
+        "swr_mesh_skin_batch": (I, [P, I, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

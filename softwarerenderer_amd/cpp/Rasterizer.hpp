@@ -29,6 +29,8 @@ using Matrix4x4 = std::array<float, 16>;     // M11..M44 row-major, row-vector c
 using Vector4 = std::array<float, 4>;
 
 class Texture;
+class Mesh;
+class PoseSet;
 class Device {                                // one swr_context = one GPU
 public:
     explicit Device(int device_id = 0) {
@@ -62,6 +64,10 @@ public:
     // a texture of this device in slot 1 .. SWR_PROGRAM_TEXTURES - 1 of a user program (null unbinds; slot 0 is the draw's texture),
     // read in both halves with swr_sample / swr_texel(env, slot, ..); captured, with the texture's filter, by each draw when recorded
     inline void SetProgramTexture(int id, int slot, const Texture* texture) const;
+    // dsts[k] = srcs[k] skinned by the palette of instances[k] of `set`, all jobs in ONE kernel launch (swr_mesh_skin_batch): word for
+    // word what Mesh::SkinFrom gives with that palette; two jobs may share a source or an instance
+    inline void SkinBatch(const std::vector<Mesh*>& dsts, const std::vector<const Mesh*>& srcs, const PoseSet& set,
+                          const std::vector<int32_t>& instances) const;
 private:
     swr_context* ctx_ = nullptr;
 };
@@ -373,6 +379,97 @@ private:
     swr_mesh* h_ = nullptr;
     int n_vertices_ = 0;
 };
+
+// Skeletal animation (build-defined, include/swr.h "SKELETAL ANIMATION"): a skeleton with its clips, sampled on the GPU into a pose
+// set -- one palette per instance of a crowd -- that Device::SkinBatch skins every mesh of the crowd from in one launch.
+struct AnimationChannel {                      // one glTF animation channel with its sampler
+    int node = 0;
+    int path = SWR_ANIM_PATH_TRANSLATION;      // SWR_ANIM_PATH_*
+    int interpolation = SWR_ANIM_LINEAR;       // SWR_ANIM_STEP | SWR_ANIM_LINEAR (CUBICSPLINE is refused)
+    std::vector<float> times;                  // n_keys, non-decreasing
+    std::vector<float> values;                 // n_keys x 3 (x 4 for a rotation, xyzw)
+};
+using PoseRequest = swr_pose_request;          // { clip_a, time_a, clip_b (-1: none), time_b, weight }
+
+class Skeleton {
+public:
+    // parent[i] < i or -1; restLocal one Matrix4x4 per node; restT / restS 3 floats per node, restR 4 (xyzw); jointNode the node each
+    // joint is, inverseBind one Matrix4x4 per joint
+    Skeleton(const Device& dev, const std::vector<int32_t>& parent, const std::vector<Matrix4x4>& restLocal, const std::vector<float>& restT,
+             const std::vector<float>& restR, const std::vector<float>& restS, const std::vector<int32_t>& jointNode,
+             const std::vector<Matrix4x4>& inverseBind)
+        : dev_(dev), n_nodes_((int)parent.size()), n_joints_((int)jointNode.size()) {
+        const size_t n = parent.size();
+        if (restLocal.size() != n || restT.size() != 3 * n || restR.size() != 4 * n || restS.size() != 3 * n || inverseBind.size() != jointNode.size())
+            throw std::invalid_argument("the skeleton's arrays do not match its node and joint counts");
+        dev_.check(swr_skeleton_create(dev_.ctx(), (int)n, parent.data(), n ? restLocal[0].data() : nullptr, restT.data(), restR.data(), restS.data(),
+                                       n_joints_, jointNode.data(), n_joints_ ? inverseBind[0].data() : nullptr, &h_));
+    }
+    ~Skeleton() { if (h_) swr_skeleton_destroy(dev_.ctx(), h_); }
+    Skeleton(const Skeleton&) = delete;
+    Skeleton& operator=(const Skeleton&) = delete;
+    swr_skeleton* handle() const { return h_; }
+    int NodeCount() const { return n_nodes_; }
+    int JointCount() const { return n_joints_; }
+    // the clip's index; a load-time call (it may wait for the device)
+    int AddClip(const std::vector<AnimationChannel>& channels) {
+        std::vector<swr_anim_channel> recs;
+        for (const AnimationChannel& c : channels) {
+            if (c.values.size() != c.times.size() * (c.path == SWR_ANIM_PATH_ROTATION ? 4u : 3u))
+                throw std::invalid_argument("a channel's values must hold 3 floats per key (4 for a rotation)");
+            recs.push_back(swr_anim_channel{ c.node, c.path, c.interpolation, (int32_t)c.times.size(), c.times.data(), c.values.data() });
+        }
+        int index = -1;
+        dev_.check(swr_skeleton_add_clip(dev_.ctx(), h_, recs.data(), (int)recs.size(), &index));
+        return index;
+    }
+private:
+    const Device& dev_;
+    swr_skeleton* h_ = nullptr;
+    int n_nodes_ = 0, n_joints_ = 0;
+};
+
+class PoseSet {
+public:
+    PoseSet(const Device& dev, int nInstances, int nJoints) : dev_(dev), n_instances_(nInstances), n_joints_(nJoints) {
+        dev_.check(swr_pose_set_create(dev_.ctx(), nInstances, nJoints, &h_));
+    }
+    ~PoseSet() { if (h_) swr_pose_set_destroy(dev_.ctx(), h_); }
+    PoseSet(const PoseSet&) = delete;
+    PoseSet& operator=(const PoseSet&) = delete;
+    swr_pose_set* handle() const { return h_; }
+    int InstanceCount() const { return n_instances_; }
+    int JointCount() const { return n_joints_; }
+    // instance i from requests[i], sampled and composed on the GPU; no host wait
+    void Sample(const Skeleton& skeleton, const std::vector<PoseRequest>& requests) {
+        dev_.check(swr_pose_set_sample(dev_.ctx(), h_, skeleton.handle(), requests.data(), (int)requests.size()));
+    }
+    // host-made palettes into instances first .. first + palettes.size() / JointCount() - 1; no host wait
+    void Upload(int first, const std::vector<Matrix4x4>& palettes) {
+        if (palettes.size() % (size_t)n_joints_) throw std::invalid_argument("palettes must hold JointCount() matrices per instance");
+        dev_.check(swr_pose_set_upload(dev_.ctx(), h_, first, (int)(palettes.size() / (size_t)n_joints_), palettes.empty() ? nullptr : palettes[0].data()));
+    }
+    // InstanceCount() x JointCount() matrices as the device holds them
+    std::vector<Matrix4x4> Read() const {
+        std::vector<Matrix4x4> out((size_t)n_instances_ * (size_t)n_joints_);
+        dev_.check(swr_pose_set_readback(dev_.ctx(), h_, out[0].data()));
+        return out;
+    }
+private:
+    const Device& dev_;
+    swr_pose_set* h_ = nullptr;
+    int n_instances_ = 0, n_joints_ = 0;
+};
+
+inline void Device::SkinBatch(const std::vector<Mesh*>& dsts, const std::vector<const Mesh*>& srcs, const PoseSet& set,
+                              const std::vector<int32_t>& instances) const {
+    if (srcs.size() != dsts.size() || instances.size() != dsts.size()) throw std::invalid_argument("dsts, srcs and instances must have equal lengths");
+    std::vector<swr_mesh*> d;
+    std::vector<const swr_mesh*> s;
+    for (const Mesh* m : dsts) d.push_back(m ? m->handle() : nullptr);
+    for (const Mesh* m : srcs) s.push_back(m ? m->handle() : nullptr);
+    check(swr_mesh_skin_batch(ctx_, (int)d.size(), d.data(), s.data(), set.handle(), instances.data()));
+}
 
 class Rasterizer {                            // public static class Rasterizer, Rasterizer.cs:12
 public:

@@ -46,6 +46,7 @@
 #include "swr_deliver.hip.h"
 #include "swr_post.hip.h"
 #include "swr_mesh_deform.hip.h"
+#include "swr_animation.hip.h"
 
 using namespace swr;
 
@@ -571,6 +572,7 @@ void swr_destroy(swr_context* c) {
     if (c->ray_stream) { (void)hipStreamSynchronize(c->ray_stream); (void)hipStreamDestroy(c->ray_stream); }
     release(c->ray_host);
     for (auto& ps : c->palettes) { release(ps.host); release(ps.dev); if (ps.done) (void)hipEventDestroy(ps.done); }
+    c->pose_events.clear();
     if (c->rtt_frame_ev) (void)hipEventDestroy(c->rtt_frame_ev);
     if (c->rtt_done_ev) (void)hipEventDestroy(c->rtt_done_ev);
     for (int i = 0; i < 2; ++i) {
@@ -1186,6 +1188,7 @@ int deform_begin(swr_context* c, const swr_mesh* dst, hipStream_t* stream) {
 //   E. the host-side box is gone: band_rejects keeps the draw on every rank (conservative and correct).
 int deform_end(swr_context* c, swr_mesh* dst, hipStream_t stream) {
     SWR_HIP(c, hipEventRecord(dst->uploaded, stream));
+    dst->posed.reset();
     dst->upload_seen = false;
     dst->bounds_ready = false;
     dst->has_box = false;
@@ -1193,7 +1196,7 @@ int deform_end(swr_context* c, swr_mesh* dst, hipStream_t stream) {
 }
 
 // A palette's way to the device without a wait (F): the first slot whose last kernel is over, else a new one.
-int palette_slot(swr_context* c, size_t bytes, PaletteSlot** out) {
+int palette_slot(swr_context* c, size_t bytes, PaletteSlot** out, bool device_copy = true) {
     PaletteSlot* s = nullptr;
     const size_t n = c->palettes.size();
     for (size_t k = 0; k < n && !s; ++k) {
@@ -1214,7 +1217,8 @@ int palette_slot(swr_context* c, size_t bytes, PaletteSlot** out) {
     }
     // (a free slot's buffers are idle: growing them frees nothing a kernel reads)
     if (s->host.cap < bytes) SWR_HIP(c, ensure_pinned(s->host, std::max<size_t>(bytes, 4096)));
-    int rc = ensure(c, s->dev, std::max<size_t>(bytes, 4096)); if (rc) return rc;
+    // (device_copy = false: staging for a copy that goes elsewhere, swr_pose_set_upload)
+    if (device_copy) { int rc = ensure(c, s->dev, std::max<size_t>(bytes, 4096)); if (rc) return rc; }
     *out = s;
     return SWR_OK;
 }
@@ -1257,7 +1261,7 @@ int swr_mesh_readback(swr_context* c, const swr_mesh* mesh, swr_vertex* out) {
     // are not flushed, a frame in flight is not waited for
     if ((rc = ensure_ray_stream(c))) return rc;
     swr_mesh* m = const_cast<swr_mesh*>(mesh);
-    if (!m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
+    if (!m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->posed ? m->posed->ev : m->uploaded, 0)); m->upload_seen = true; }
     SWR_HIP(c, hipMemcpyAsync(out, m->d_verts, (size_t)m->n_verts * sizeof(swr_vertex), hipMemcpyDeviceToHost, c->ray_stream));
     SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
     return SWR_OK;
@@ -1337,6 +1341,318 @@ int swr_mesh_skin(swr_context* c, swr_mesh* dst, const swr_mesh* src, const floa
     SWR_HIP(c, hipEventRecord(slot->done, s));
     slot->busy = true;
     return deform_end(c, dst, s);
+}
+
+// ---- skeletal animation: clips to palettes on the GPU, one skin launch for a crowd
+namespace {
+int skeleton_check(swr_context* c, const swr_skeleton* k) {
+    if (!k) return fail(c, SWR_ERR_INVALID_ARG, "the skeleton is null");
+    if (k->owner != c) return fail(c, SWR_ERR_INVALID_ARG, "the skeleton belongs to another context");
+    return SWR_OK;
+}
+int pose_set_check(swr_context* c, const swr_pose_set* p) {
+    if (!p) return fail(c, SWR_ERR_INVALID_ARG, "the pose set is null");
+    if (p->owner != c) return fail(c, SWR_ERR_INVALID_ARG, "the pose set belongs to another context");
+    return SWR_OK;
+}
+// behind a write of the set on stream s: what swr_pose_set_readback orders itself by
+int pose_set_written(swr_context* c, swr_pose_set* p, hipStream_t s) {
+    SWR_HIP(c, hipEventRecord(p->written, s));
+    p->written_seen = false;
+    return SWR_OK;
+}
+void destroy_skeleton(swr_skeleton* k) {
+    if (k->d_static) (void)hipFree(k->d_static);
+    if (k->d_clips) (void)hipFree(k->d_clips);
+    delete k;
+}
+void destroy_pose_set(swr_pose_set* p) {
+    if (p->d_palettes) (void)hipFree(p->d_palettes);
+    if (p->d_worlds) (void)hipFree(p->d_worlds);
+    if (p->written) (void)hipEventDestroy(p->written);
+    delete p;
+}
+}  // namespace
+
+int swr_skeleton_create(swr_context* c, int n_nodes, const int32_t* parent, const float* rest_local, const float* rest_t,
+                        const float* rest_r, const float* rest_s, int n_joints, const int32_t* joint_node, const float* inverse_bind,
+                        swr_skeleton** out) {
+    SWR_ENTER(c);
+    if (!out || !parent || !rest_local || !rest_t || !rest_r || !rest_s) return fail(c, SWR_ERR_INVALID_ARG, "a skeleton array is null");
+    if (n_nodes < 1 || n_joints < 0) return fail(c, SWR_ERR_INVALID_ARG, "a skeleton has at least one node and no negative joint count");
+    if (n_joints > 0 && (!joint_node || !inverse_bind)) return fail(c, SWR_ERR_INVALID_ARG, "joint_node or inverse_bind is null");
+    if (n_nodes > SWR_SKELETON_MAX_NODES || n_joints > 65535) return fail(c, SWR_ERR_UNSUPPORTED, "a skeleton holds at most 65535 nodes and 65535 joints");
+    const size_t nn = (size_t)n_nodes, nj = (size_t)n_joints;
+    std::vector<int32_t> depth(nn), order(nn);
+    int n_levels = 0;
+    for (size_t i = 0; i < nn; ++i) {
+        if (parent[i] < -1 || parent[i] >= (int32_t)i) return fail(c, SWR_ERR_INVALID_ARG, "nodes must be in topological order: parent[i] < i, or -1 for a root");
+        depth[i] = parent[i] < 0 ? 0 : depth[(size_t)parent[i]] + 1;
+        n_levels = std::max(n_levels, depth[i] + 1);
+    }
+    for (size_t j = 0; j < nj; ++j)
+        if (joint_node[j] < 0 || joint_node[j] >= n_nodes) return fail(c, SWR_ERR_INVALID_ARG, "a joint's node index is out of range");
+    // the level table: nodes by depth, in index order within a level (a counting sort)
+    std::vector<int32_t> level_start((size_t)n_levels + 1, 0);
+    for (size_t i = 0; i < nn; ++i) ++level_start[(size_t)depth[i] + 1];
+    for (int l = 0; l < n_levels; ++l) level_start[(size_t)l + 1] += level_start[(size_t)l];
+    { std::vector<int32_t> at(level_start.begin(), level_start.end() - 1); for (size_t i = 0; i < nn; ++i) order[(size_t)at[(size_t)depth[i]]++] = (int32_t)i; }
+    // one blob of 32-bit words, the matrices first (16-byte loads)
+    const size_t o_local = 0, o_ib = o_local + 16 * nn, o_t = o_ib + 16 * nj, o_r = o_t + 3 * nn, o_s = o_r + 4 * nn, o_parent = o_s + 3 * nn,
+                 o_order = o_parent + nn, o_level = o_order + nn, o_joint = o_level + (size_t)n_levels + 1, words = o_joint + nj;
+    std::vector<uint32_t> blob(words);
+    memcpy(&blob[o_local], rest_local, 64 * nn); memcpy(&blob[o_t], rest_t, 12 * nn); memcpy(&blob[o_r], rest_r, 16 * nn);
+    memcpy(&blob[o_s], rest_s, 12 * nn); memcpy(&blob[o_parent], parent, 4 * nn); memcpy(&blob[o_order], order.data(), 4 * nn);
+    memcpy(&blob[o_level], level_start.data(), 4 * ((size_t)n_levels + 1));
+    if (nj) { memcpy(&blob[o_ib], inverse_bind, 64 * nj); memcpy(&blob[o_joint], joint_node, 4 * nj); }
+    swr_skeleton* k = new swr_skeleton();
+    k->owner = c; k->n_nodes = n_nodes; k->n_joints = n_joints; k->n_levels = n_levels;
+    k->clips.assign(1, 0u);
+    hipError_t e = hipMalloc(&k->d_static, words * 4);
+    if (e == hipSuccess) e = hipMemcpy(k->d_static, blob.data(), words * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        destroy_skeleton(k);
+        c->err = std::string("skeleton upload failed: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+    }
+    *out = k;
+    return SWR_OK;
+}
+
+int swr_skeleton_destroy(swr_context* c, swr_skeleton* k) {
+    SWR_ENTER(c);
+    if (!k) return SWR_OK;
+    int rc = skeleton_check(c, k); if (rc) return rc;
+    destroy_skeleton(k);                       // (hipFree waits for the device: a queued k_pose_sample has read it by then)
+    return SWR_OK;
+}
+
+int swr_skeleton_add_clip(swr_context* c, swr_skeleton* k, const swr_anim_channel* channels, int n_channels, int* clip_index) {
+    SWR_ENTER(c);
+    int rc = skeleton_check(c, k); if (rc) return rc;
+    if (!clip_index || n_channels < 0 || (n_channels > 0 && !channels)) return fail(c, SWR_ERR_INVALID_ARG, "channels or clip_index is null, or n_channels is negative");
+    const size_t nn = (size_t)k->n_nodes;
+    size_t words = k->clips.size() + 3 * nn;
+    std::vector<uint8_t> taken(3 * nn, 0);
+    for (int i = 0; i < n_channels; ++i) {
+        const swr_anim_channel& ch = channels[i];
+        if (ch.interpolation == SWR_ANIM_CUBICSPLINE) return fail(c, SWR_ERR_UNSUPPORTED, "CUBICSPLINE interpolation is not supported (STEP and LINEAR are)");
+        if (ch.interpolation != SWR_ANIM_STEP && ch.interpolation != SWR_ANIM_LINEAR) return fail(c, SWR_ERR_INVALID_ARG, "unknown interpolation");
+        if (ch.node < 0 || ch.node >= k->n_nodes) return fail(c, SWR_ERR_INVALID_ARG, "a channel's node index is out of range");
+        if (ch.path < SWR_ANIM_PATH_TRANSLATION || ch.path > SWR_ANIM_PATH_SCALE) return fail(c, SWR_ERR_INVALID_ARG, "a channel's path is none of translation, rotation, scale");
+        if (ch.n_keys < 1) return fail(c, SWR_ERR_INVALID_ARG, "a channel needs at least one key");
+        if (!ch.times || !ch.values) return fail(c, SWR_ERR_INVALID_ARG, "a channel's times or values are null");
+        uint8_t& t = taken[3 * (size_t)ch.node + (size_t)ch.path];
+        if (t) return fail(c, SWR_ERR_INVALID_ARG, "two channels target the same node and path");
+        t = 1;
+        for (int q = 0; q + 1 < ch.n_keys; ++q)
+            if (!(ch.times[q + 1] >= ch.times[q])) return fail(c, SWR_ERR_INVALID_ARG, "key times must not decrease (or be NaN)");
+        words += 2 + (size_t)ch.n_keys * (ch.path == SWR_ANIM_PATH_ROTATION ? 5 : 4);
+    }
+    if (words >= ((size_t)1 << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "the skeleton's clips exceed 2^30 words");
+    // the new blob on the host, then in a new allocation; the old one is freed once the device is idle (a queued k_pose_sample may
+    // read it) -- a load-time call
+    std::vector<uint32_t> blob = k->clips;
+    const uint32_t base = (uint32_t)blob.size();
+    blob.resize(words, 0u);
+    size_t at = base + 3 * nn;
+    for (int i = 0; i < n_channels; ++i) {
+        const swr_anim_channel& ch = channels[i];
+        const size_t comps = ch.path == SWR_ANIM_PATH_ROTATION ? 4 : 3, nk = (size_t)ch.n_keys;
+        blob[base + 3 * (size_t)ch.node + (size_t)ch.path] = (uint32_t)at;
+        blob[at] = (uint32_t)ch.interpolation; blob[at + 1] = (uint32_t)ch.n_keys;
+        memcpy(&blob[at + 2], ch.times, 4 * nk);
+        memcpy(&blob[at + 2 + nk], ch.values, 4 * nk * comps);
+        at += 2 + nk * (1 + comps);
+    }
+    uint32_t* d_new = nullptr;
+    SWR_HIP(c, hipMalloc((void**)&d_new, words * 4));
+    hipError_t e = hipMemcpy(d_new, blob.data(), words * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && k->d_clips) { e = hipDeviceSynchronize(); ++c->host_syncs; }
+    if (e != hipSuccess) { (void)hipFree(d_new); SWR_HIP(c, e); }
+    if (k->d_clips) (void)hipFree(k->d_clips);
+    k->d_clips = d_new;
+    k->clips.swap(blob);
+    *clip_index = (int)k->clip_base.size();
+    k->clip_base.push_back(base);
+    return SWR_OK;
+}
+
+int swr_pose_set_create(swr_context* c, int n_instances, int n_joints, swr_pose_set** out) {
+    SWR_ENTER(c);
+    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "out is null");
+    if (n_instances < 1 || n_joints < 1) return fail(c, SWR_ERR_INVALID_ARG, "a pose set has at least one instance and one joint");
+    if (n_joints > 65535 || (size_t)n_instances * (size_t)n_joints > ((size_t)1 << 24))
+        return fail(c, SWR_ERR_UNSUPPORTED, "a pose set holds at most 65535 joints per instance and 2^24 matrices");
+    swr_pose_set* p = new swr_pose_set();
+    p->owner = c; p->n_instances = n_instances; p->n_joints = n_joints;
+    const size_t bytes = (size_t)n_instances * (size_t)n_joints * 64;
+    hipError_t e = hipMalloc((void**)&p->d_palettes, bytes);
+    if (e == hipSuccess) e = hipMemset(p->d_palettes, 0, bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);          // (the streams of a context do not wait for the null stream)
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->written, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        destroy_pose_set(p);
+        c->err = std::string("pose set allocation failed: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+    }
+    *out = p;
+    return SWR_OK;
+}
+
+int swr_pose_set_destroy(swr_context* c, swr_pose_set* p) {
+    SWR_ENTER(c);
+    if (!p) return SWR_OK;
+    int rc = pose_set_check(c, p); if (rc) return rc;
+    destroy_pose_set(p);                       // (hipFree waits for the device: the kernels queued on the set are over by then)
+    return SWR_OK;
+}
+
+int swr_pose_set_sample(swr_context* c, swr_pose_set* p, const swr_skeleton* k, const swr_pose_request* requests, int n) {
+    SWR_ENTER(c);
+    int rc;
+    if ((rc = pose_set_check(c, p)) || (rc = skeleton_check(c, k))) return rc;
+    if (n < 0 || n > p->n_instances) return fail(c, SWR_ERR_INVALID_ARG, "n must be within 0 .. n_instances");
+    if (n > 0 && !requests) return fail(c, SWR_ERR_INVALID_ARG, "requests is null");
+    if (k->n_joints != p->n_joints) return fail(c, SWR_ERR_INVALID_ARG, "the pose set's joint count is not the skeleton's");
+    const int n_clips = (int)k->clip_base.size();
+    for (int i = 0; i < n; ++i)
+        if (requests[i].clip_a < 0 || requests[i].clip_a >= n_clips || requests[i].clip_b >= n_clips)
+            return fail(c, SWR_ERR_INVALID_ARG, "a request names a clip the skeleton does not have");
+    if (n == 0) return SWR_OK;
+    if ((rc = ensure_front_stream(c))) return rc;
+    if (p->world_nodes < k->n_nodes) {
+        // the node matrices grow to the largest skeleton the set was sampled with (hipFree waits for the device: the first sample, once)
+        if (p->d_worlds) { SWR_HIP(c, hipFree(p->d_worlds)); p->d_worlds = nullptr; p->world_nodes = 0; }
+        SWR_HIP(c, hipMalloc((void**)&p->d_worlds, (size_t)p->n_instances * (size_t)k->n_nodes * 64));
+        p->world_nodes = k->n_nodes;
+    }
+    const hipStream_t s = use_front_stream(c);
+    const size_t bytes = (size_t)n * sizeof(PoseRequestDev);
+    PaletteSlot* slot = nullptr;
+    if ((rc = palette_slot(c, bytes, &slot))) return rc;
+    PoseRequestDev* rq = static_cast<PoseRequestDev*>(slot->host.p);
+    for (int i = 0; i < n; ++i) {
+        const swr_pose_request& r = requests[i];
+        rq[i] = PoseRequestDev{ k->clip_base[(size_t)r.clip_a], r.time_a, r.clip_b < 0 ? SWR_ANIM_NO_CLIP : k->clip_base[(size_t)r.clip_b], r.time_b, r.weight };
+    }
+    SWR_HIP(c, hipMemcpyAsync(slot->dev.p, slot->host.p, bytes, hipMemcpyHostToDevice, s));
+    const size_t nn = (size_t)k->n_nodes, nj = (size_t)k->n_joints;
+    const float* f = static_cast<const float*>(k->d_static);
+    SkeletonDev sk{};
+    sk.rest_local = f; sk.inverse_bind = f + 16 * nn; sk.rest_t = sk.inverse_bind + 16 * nj; sk.rest_r = sk.rest_t + 3 * nn; sk.rest_s = sk.rest_r + 4 * nn;
+    sk.parent = reinterpret_cast<const int32_t*>(sk.rest_s + 3 * nn); sk.order = sk.parent + nn; sk.level_start = sk.order + nn;
+    sk.joint_node = sk.level_start + (size_t)k->n_levels + 1;
+    sk.n_nodes = (uint32_t)k->n_nodes; sk.n_joints = (uint32_t)k->n_joints; sk.n_levels = (uint32_t)k->n_levels;
+    hipLaunchKernelGGL(k_pose_sample, dim3((uint32_t)n), dim3(SWR_POSE_BLOCK), 0, s, sk, (const uint32_t*)k->d_clips,
+                       (const PoseRequestDev*)slot->dev.p, reinterpret_cast<float4*>(p->d_worlds), reinterpret_cast<float4*>(p->d_palettes),
+                       (uint32_t)p->n_joints * 16u);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipEventRecord(slot->done, s));
+    slot->busy = true;
+    return pose_set_written(c, p, s);
+}
+
+int swr_pose_set_upload(swr_context* c, swr_pose_set* p, int first, int n, const float* palettes) {
+    SWR_ENTER(c);
+    int rc = pose_set_check(c, p); if (rc) return rc;
+    if (first < 0 || n < 0 || first > p->n_instances || n > p->n_instances - first) return fail(c, SWR_ERR_INVALID_ARG, "first .. first + n - 1 must be instances of the set");
+    if (n > 0 && !palettes) return fail(c, SWR_ERR_INVALID_ARG, "palettes is null");
+    if (n == 0) return SWR_OK;
+    if ((rc = ensure_front_stream(c))) return rc;
+    const hipStream_t s = use_front_stream(c);
+    const size_t stride = (size_t)p->n_joints * 16, bytes = (size_t)n * stride * 4;
+    PaletteSlot* slot = nullptr;
+    if ((rc = palette_slot(c, bytes, &slot, false))) return rc;
+    memcpy(slot->host.p, palettes, bytes);
+    SWR_HIP(c, hipMemcpyAsync(p->d_palettes + (size_t)first * stride, slot->host.p, bytes, hipMemcpyHostToDevice, s));
+    SWR_HIP(c, hipEventRecord(slot->done, s));
+    slot->busy = true;
+    return pose_set_written(c, p, s);
+}
+
+int swr_pose_set_readback(swr_context* c, const swr_pose_set* set, float* out) {
+    SWR_ENTER(c);
+    int rc = pose_set_check(c, set); if (rc) return rc;
+    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "the destination is null");
+    // a reader on the ray stream, as swr_mesh_readback: behind the set's last write and behind nothing else
+    if ((rc = ensure_ray_stream(c))) return rc;
+    swr_pose_set* p = const_cast<swr_pose_set*>(set);
+    if (!p->written_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, p->written, 0)); p->written_seen = true; }
+    SWR_HIP(c, hipMemcpyAsync(out, p->d_palettes, (size_t)p->n_instances * (size_t)p->n_joints * 64, hipMemcpyDeviceToHost, c->ray_stream));
+    SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
+    return SWR_OK;
+}
+
+int swr_mesh_skin_batch(swr_context* c, int n, swr_mesh* const* dst, const swr_mesh* const* src, const swr_pose_set* set, const int32_t* instance) {
+    SWR_ENTER(c);
+    int rc = pose_set_check(c, set); if (rc) return rc;
+    if (n < 0) return fail(c, SWR_ERR_INVALID_ARG, "n is negative");
+    if (n == 0) return SWR_OK;
+    if (!dst || !src || !instance) return fail(c, SWR_ERR_INVALID_ARG, "dst, src or instance is null");
+    std::vector<const swr_mesh*> dsts((size_t)n);
+    uint64_t blocks = 0;
+    for (int k = 0; k < n; ++k) {
+        if ((rc = deform_mesh_check(c, dst[k], "a destination mesh is null"))) return rc;
+        if ((rc = deform_mesh_check(c, src[k], "a source mesh is null"))) return rc;
+        if (src[k]->n_verts != dst[k]->n_verts) return fail(c, SWR_ERR_INVALID_ARG, "a job's source and destination must have equal vertex counts");
+        if (!src[k]->has_skin) return fail(c, SWR_ERR_INVALID_ARG, "a source mesh has no skin attributes (swr_mesh_set_skin)");
+        if (instance[k] < 0 || instance[k] >= set->n_instances) return fail(c, SWR_ERR_INVALID_ARG, "an instance is not one of the pose set's");
+        if (set->n_joints <= src[k]->max_joint) return fail(c, SWR_ERR_INVALID_ARG, "the pose set's n_joints must exceed the largest joint index a source's skin attributes use");
+        dsts[(size_t)k] = dst[k];
+        blocks += ((uint64_t)dst[k]->n_verts + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK;
+    }
+    std::sort(dsts.begin(), dsts.end());
+    if (std::adjacent_find(dsts.begin(), dsts.end()) != dsts.end()) return fail(c, SWR_ERR_INVALID_ARG, "a destination mesh appears twice in the batch");
+    for (int k = 0; k < n; ++k)
+        if (std::binary_search(dsts.begin(), dsts.end(), src[k])) return fail(c, SWR_ERR_INVALID_ARG, "a destination mesh is a job's source (make a target with swr_mesh_create_like)");
+    if (blocks == 0) return SWR_OK;
+    if (blocks > 0x7fffffffull) return fail(c, SWR_ERR_UNSUPPORTED, "the batch exceeds 2^31 blocks of vertices");
+    // deform_begin's rules A and B, once over all destinations
+    const auto reads_a_dst = [&](const std::vector<DrawCmd>& draws) {
+        for (const DrawCmd& d : draws) if (std::binary_search(dsts.begin(), dsts.end(), (const swr_mesh*)d.mesh)) return true;
+        return false;
+    };
+    if (reads_a_dst(c->draws) && (rc = flush_locked(c))) return rc;
+    bool in_flight = false;
+    for (const Batch& b : c->inflight) in_flight = in_flight || reads_a_dst(b.draws);
+    if (in_flight && (rc = sync_locked(c))) return rc;
+    if ((rc = ensure_front_stream(c))) return rc;
+    const hipStream_t s = use_front_stream(c);
+    // the job table: jobs with vertices, by first block
+    PaletteSlot* slot = nullptr;
+    if ((rc = palette_slot(c, (size_t)n * sizeof(SkinJob), &slot))) return rc;
+    SkinJob* jobs = static_cast<SkinJob*>(slot->host.p);
+    uint32_t n_jobs = 0, first_block = 0;
+    for (int k = 0; k < n; ++k) {
+        if (dst[k]->n_verts == 0) continue;
+        jobs[n_jobs++] = SkinJob{ src[k]->d_verts, src[k]->d_joints, src[k]->d_weights, dst[k]->d_verts, (uint32_t)dst[k]->n_verts, first_block,
+                                  (uint32_t)instance[k] * (uint32_t)set->n_joints * 16u, 0u };
+        first_block += ((uint32_t)dst[k]->n_verts + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK;
+    }
+    SWR_HIP(c, hipMemcpyAsync(slot->dev.p, slot->host.p, (size_t)n_jobs * sizeof(SkinJob), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_mesh_skin_batch, dim3(first_block), dim3(SWR_DEFORM_BLOCK), 0, s, (const SkinJob*)slot->dev.p, n_jobs,
+                       (const float*)set->d_palettes, c->nm_flags);
+    SWR_HIP(c, hipGetLastError());
+    SWR_HIP(c, hipEventRecord(slot->done, s));
+    slot->busy = true;
+    // deform_end for every destination, with ONE event behind the kernel for rule C instead of one per mesh: the destinations share it
+    std::shared_ptr<SharedEvent> ev;
+    for (auto& e : c->pose_events) if (e.use_count() == 1) { ev = e; break; }          // no mesh holds it: its waits were issued long ago
+    if (!ev) {
+        ev = std::make_shared<SharedEvent>();
+        SWR_HIP(c, hipEventCreateWithFlags(&ev->ev, hipEventDisableTiming));
+        c->pose_events.push_back(ev);
+    }
+    SWR_HIP(c, hipEventRecord(ev->ev, s));
+    for (int k = 0; k < n; ++k) {
+        if (dst[k]->n_verts == 0) continue;
+        dst[k]->posed = ev;
+        dst[k]->upload_seen = false;
+        dst[k]->bounds_ready = false;
+        dst[k]->has_box = false;
+    }
+    return SWR_OK;
 }
 
 int swr_set_state(swr_context* c, float near_clip, float far_clip, int debug_mode) {

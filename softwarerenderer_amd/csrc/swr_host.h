@@ -1,7 +1,15 @@
 // swr_host.h -- host side of libswr_hip.so: the context and batch types, device buffers, the frame-slot ring, band geometry,
 // timing spans, the front stream, run-time values as kernel template arguments.  Included by swr_api.hip only (the library's one translation unit).
 #pragma once
+#include <memory>
 #include <type_traits>
+
+// An event several meshes share: swr_mesh_skin_batch records ONE behind its kernel for all its destinations (an event record costs a
+// few microseconds of stream time, per mesh that was most of a small batch); freed with its last holder.
+struct SharedEvent {
+    hipEvent_t ev = nullptr;
+    ~SharedEvent() { if (ev) (void)hipEventDestroy(ev); }
+};
 
 struct swr_mesh {
     float4* d_bounds = nullptr;               // Mesh.SphereBounds (ModelLoader.cs:291), computed on first use
@@ -15,12 +23,32 @@ struct swr_mesh {
     bool has_box = false;
     hipEvent_t uploaded = nullptr;            // retained meshes: recorded behind the upload, for readers on another stream (swr_raycast)
     bool upload_seen = false;                 // ... the ray stream has been ordered behind it
+    std::shared_ptr<SharedEvent> posed;       // set: the last write was a batched skin, and THIS event is behind it (stands in for `uploaded`)
     swr_context* owner = nullptr;             // the context that made it (the deform calls refuse another context's mesh)
     // static skin attributes (swr_mesh_set_skin): four joint indices and four weights per vertex, uploaded once
     ushort4* d_joints = nullptr;
     float4* d_weights = nullptr;
     bool has_skin = false;                    // (a mesh without vertices has the attributes and no arrays)
     int max_joint = -1;                       // largest joint index used (host, at the upload): swr_mesh_skin needs a longer palette
+};
+// Skeletal animation.  A skeleton's static arrays are one device blob; its clips are another (the host keeps
+// a copy: adding a clip re-uploads the whole blob into a new allocation).
+struct swr_skeleton {
+    swr_context* owner = nullptr;
+    int n_nodes = 0, n_joints = 0, n_levels = 0;
+    void* d_static = nullptr;                 // parent | order | level_start | rest_local | rest_t | rest_r | rest_s | joint_node | inverse_bind
+    uint32_t* d_clips = nullptr;
+    std::vector<uint32_t> clips;              // the clip blob (swr_animation.hip.h), word 0 unused
+    std::vector<uint32_t> clip_base;          // word offset of each clip's node table
+};
+struct swr_pose_set {
+    swr_context* owner = nullptr;
+    int n_instances = 0, n_joints = 0;
+    float* d_palettes = nullptr;              // n_instances x n_joints x 16 floats, zero at creation
+    float* d_worlds = nullptr;                // k_pose_sample's node matrices: n_instances x world_nodes x 16 floats
+    int world_nodes = 0;
+    hipEvent_t written = nullptr;             // behind the last sample or upload, for swr_pose_set_readback on the ray stream
+    bool written_seen = true;
 };
 struct swr_texture {
     uint8_t* d_rgba = nullptr;
@@ -253,6 +281,8 @@ struct swr_context {
     // none is free, so several calls per frame never overwrite a palette a queued kernel has not read
     std::vector<PaletteSlot> palettes;
     size_t palette_next = 0;
+    // swr_mesh_skin_batch: the events its destinations share; one that no mesh holds any more is recorded again
+    std::vector<std::shared_ptr<SharedEvent>> pose_events;
 
     int profiling = 0;                         // 0 off, 1 every stage, 2 only the raster kernel (2 events per flush)
     std::vector<EventSpan> spans;

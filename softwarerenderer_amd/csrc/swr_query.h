@@ -30,7 +30,7 @@ int stage_targets(swr_context* c, const swr_ray_target* targets, int n, RayTarge
     *max_tris = 0;
     for (int t = 0; t < n; ++t) {
         swr_mesh* m = const_cast<swr_mesh*>(targets[t].mesh);
-        if (m->uploaded && !m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->uploaded, 0)); m->upload_seen = true; }
+        if (m->uploaded && !m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->posed ? m->posed->ev : m->uploaded, 0)); m->upload_seen = true; }
         out[t].verts = m->d_verts; out[t].idx = m->d_idx; out[t].n_tris = (uint32_t)(m->n_idx / 3); out[t].pad = 0u;
         memcpy(out[t].model, targets[t].model, 64); memcpy(out[t].normal_matrix, targets[t].normal_matrix, 64);
         *max_tris = std::max(*max_tris, out[t].n_tris);

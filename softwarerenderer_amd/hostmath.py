@@ -116,3 +116,31 @@ def normal_matrix(model):
     """Transpose(Invert(model)) as Physics.Raycast forms it (Physics.cs:38), or None where the model does not invert."""
     inv = invert(model)
     return None if inv is None else np.ascontiguousarray(inv.T)
+
+
+def create_from_quaternion(q) -> np.ndarray:
+    """Matrix4x4.CreateFromQuaternion (q = x, y, z, w), in that source's term order, float32 with one rounding per operation: the
+    rotation block of a skeleton node's local matrix (include/swr.h "SKELETAL ANIMATION")."""
+    x, y, z, w = (F(v) for v in np.asarray(q, dtype=F).reshape(4))
+    one, two = F(1.0), F(2.0)
+    with np.errstate(all="ignore"):
+        xx, yy, zz = x * x, y * y, z * z
+        xy, wz, xz, wy, yz, wx = x * y, z * w, z * x, y * w, y * z, x * w
+        m = np.eye(4, dtype=F)
+        m[0, 0], m[0, 1], m[0, 2] = one - two * (yy + zz), two * (xy + wz), two * (xz - wy)
+        m[1, 0], m[1, 1], m[1, 2] = two * (xy - wz), one - two * (zz + xx), two * (yz + wx)
+        m[2, 0], m[2, 1], m[2, 2] = two * (xz + wy), two * (yz - wx), one - two * (yy + xx)
+    return m
+
+
+def quaternion_lerp(a, b, u) -> np.ndarray:
+    """Quaternion.Lerp(a, b, u) in its scalar form: the normalised lerp along the shorter arc (not a slerp); u is not clamped and a
+    zero result gives the NaN it gives."""
+    a, b, u = np.asarray(a, dtype=F).reshape(4), np.asarray(b, dtype=F).reshape(4), F(u)
+    with np.errstate(all="ignore"):
+        u1 = F(1.0) - u
+        dot = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]
+        r = np.array([u1 * a[c] + u * b[c] if dot >= 0 else u1 * a[c] - u * b[c] for c in range(4)], dtype=F)
+        ls = ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3]
+        inv = F(1.0) / np.sqrt(ls)
+        return (r * inv).astype(F)

@@ -8,8 +8,11 @@ Host-side: it only PRODUCES inputs of the hot path.  What is reproduced from Mod
   * PostProcessSteps.FlipUVs (v -> 1 - v), white default vertex colour, diffuse texture path  :145-150,184-186,240-270
   * a directory of model files = animation frames sorted by name                              :79-115
 Beyond the reference (build-defined): a glTF primitive's JOINTS_0 / WEIGHTS_0 and a skin's inverseBindMatrices are
-read and kept beside the vertices they belong to (Mesh.joints, Mesh.weights, Model.Skins), the inputs of Mesh.SkinFrom; animation
-channels are not sampled -- the caller supplies the joint matrices.  Model.FramePair names the two key frames around a time.
+read and kept beside the vertices they belong to (Mesh.joints, Mesh.weights, Model.Skins), the inputs of Mesh.SkinFrom.
+Model.FramePair names the two key frames around a time.  Skeletal animation (build-defined): `animations`
+(samplers, channels, STEP / LINEAR) and every node's TRS or matrix are read into Model.Skeletons -- per skin, its joints plus the
+ancestors they need, renumbered topologically -- and Model.Clips; Model.UploadSkeleton hands both to the GPU, where the channels are
+sampled (softwarerenderer_amd.Skeleton / PoseSet).  CUBICSPLINE raises a ValueError.
 Where Assimp's own numerics matter (normal generation when a mesh has none, TRS composition) this loader is
 build-defined -- AssimpNet 5.0.0-beta1 is not available, so those results are unpinned.
 One deliberate difference: the reference wraps its ushort index silently past 65,535 unique vertices
@@ -218,12 +221,104 @@ def _gltf_skins(g: "_Gltf") -> List[dict]:
     return out
 
 
-def _load_gltf(path: str, skins_out: Optional[list] = None) -> List[Mesh]:
+def compose_trs(t, r, s) -> np.ndarray:
+    """A node's local matrix from T, R (xyzw) and S, as the GPU composes it (include/swr.h "SKELETAL ANIMATION"): row i of
+    Matrix4x4.CreateFromQuaternion(R) times s_i, one rounding each; row 4 = (t, 1); column 4 = (0, 0, 0, 1)."""
+    from .hostmath import create_from_quaternion
+    m = create_from_quaternion(r)
+    sc = np.asarray(s, dtype=F).reshape(3)
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            m[i, :3] = m[i, :3] * sc[i]
+    m[3, :3] = np.asarray(t, dtype=F).reshape(3)
+    return m
+
+
+def _gltf_skeletons(g: "_Gltf", skins: List[dict]) -> List[dict]:
+    """One skeleton per skin: the skin's joints plus every ancestor they need, renumbered so that parent < child (a pre-order walk
+    from the document's roots; a skin may list its joints child-first, and a joint may hang under a node that is no joint).
+      "Nodes"  glTF node index of each skeleton node        "Parent"  skeleton index of its parent, -1 for a root
+      "RestLocal" (n, 4, 4), "RestT" (n, 3), "RestR" (n, 4) xyzw, "RestS" (n, 3): a TRS node's matrix is compose_trs of its
+               values (defaults 0, identity, 1); a node given as a matrix keeps it, with T, R, S at their defaults (glTF animates
+               TRS nodes only)
+      "JointNode" skeleton index of each joint, in the skin's order        "InverseBind" (n_joints, 4, 4)"""
+    nodes = g.doc.get("nodes", [])
+    parent_of = {}
+    for i, n in enumerate(nodes):
+        for ch in n.get("children", []):
+            parent_of[int(ch)] = i
+    out = []
+    for skin in skins:
+        need = set()
+        for j in skin["Joints"]:
+            k = j
+            while k is not None and k not in need:
+                need.add(k)
+                k = parent_of.get(k)
+        order: List[int] = []
+        stack = sorted((k for k in need if parent_of.get(k) is None), reverse=True)
+        while stack:                                   # pre-order: a parent is numbered before its children
+            k = stack.pop()
+            order.append(k)
+            stack.extend(sorted((int(ch) for ch in nodes[k].get("children", []) if int(ch) in need), reverse=True))
+        index = {k: i for i, k in enumerate(order)}
+        n = len(order)
+        sk = {"Name": skin["Name"], "Nodes": order, "Parent": np.array([index.get(parent_of.get(k), -1) for k in order], dtype=np.int32),
+              "RestLocal": np.zeros((n, 4, 4), dtype=F), "RestT": np.zeros((n, 3), dtype=F), "RestR": np.zeros((n, 4), dtype=F),
+              "RestS": np.ones((n, 3), dtype=F), "JointNode": np.array([index[j] for j in skin["Joints"]], dtype=np.int32),
+              "InverseBind": skin["InverseBindMatrices"]}
+        sk["RestR"][:, 3] = 1.0
+        for i, k in enumerate(order):
+            node = nodes[k]
+            if "matrix" in node:
+                sk["RestLocal"][i] = np.asarray(node["matrix"], dtype=F).reshape(4, 4)
+                continue
+            if "translation" in node:
+                sk["RestT"][i] = node["translation"]
+            if "rotation" in node:
+                sk["RestR"][i] = node["rotation"]
+            if "scale" in node:
+                sk["RestS"][i] = node["scale"]
+            sk["RestLocal"][i] = compose_trs(sk["RestT"][i], sk["RestR"][i], sk["RestS"][i])
+        out.append(sk)
+    return out
+
+
+def _gltf_clips(g: "_Gltf") -> List[dict]:
+    """The document's animations: {"Name", "Channels": [{"Node": glTF node index, "Path": "translation" | "rotation" | "scale",
+    "Interpolation": "STEP" | "LINEAR", "Times": (n,) float32, "Values": (n, 3 | 4) float32}]}.  Channels without a target node and
+    morph-target weights are skipped (not built); CUBICSPLINE raises."""
+    out = []
+    for a in g.doc.get("animations", []):
+        chans = []
+        for ch in a.get("channels", []):
+            tgt = ch.get("target", {})
+            if "node" not in tgt or tgt.get("path") not in ("translation", "rotation", "scale"):
+                continue
+            smp = a["samplers"][ch["sampler"]]
+            interp = smp.get("interpolation", "LINEAR")
+            if interp == "CUBICSPLINE":
+                raise ValueError(f"animation {a.get('name', len(out))!r}: CUBICSPLINE interpolation is not supported (STEP and LINEAR are)")
+            if interp not in ("STEP", "LINEAR"):
+                raise ValueError(f"animation {a.get('name', len(out))!r}: unknown interpolation {interp!r}")
+            chans.append({"Node": int(tgt["node"]), "Path": tgt["path"], "Interpolation": interp,
+                          "Times": np.ascontiguousarray(g.accessor(smp["input"]).astype(F).reshape(-1)),
+                          "Values": np.ascontiguousarray(g.accessor(smp["output"]).astype(F))})
+        out.append({"Name": a.get("name", ""), "Channels": chans})
+    return out
+
+
+def _load_gltf(path: str, skins_out: Optional[list] = None, skeletons_out: Optional[list] = None, clips_out: Optional[list] = None) -> List[Mesh]:
     g = _Gltf(path)
     doc = g.doc
     meshes: List[Mesh] = []
+    skins = _gltf_skins(g)
     if skins_out is not None:
-        skins_out.extend(_gltf_skins(g))
+        skins_out.extend(skins)
+    if skeletons_out is not None:
+        skeletons_out.extend(_gltf_skeletons(g, skins))
+    if clips_out is not None:
+        clips_out.extend(_gltf_clips(g))
 
     def process(node_i: int, parent: np.ndarray):
         node = doc["nodes"][node_i]
@@ -326,6 +421,24 @@ class Model:
         self.Lights: list = []             # Light.cs is dead data for the renderer
         self.AnimationFrames: List["Model"] = []
         self.Skins: List[dict] = []        # glTF skins (build-defined): joint node indices and inverse bind matrices, see _gltf_skins
+        self.Skeletons: List[dict] = []    # one per skin: its joints and their ancestors in topological order, see _gltf_skeletons
+        self.Clips: List[dict] = []        # glTF animations: channels with key times and values, see _gltf_clips
+
+    def ClipChannels(self, skeleton: int, clip: int) -> list:
+        """Clips[clip]'s channels on nodes of Skeletons[skeleton], as Skeleton.AddClip takes them: (skeleton node, path,
+        interpolation, times, values).  Channels on other nodes are not the skeleton's."""
+        index = {k: i for i, k in enumerate(self.Skeletons[skeleton]["Nodes"])}
+        return [(index[c["Node"]], c["Path"], c["Interpolation"], c["Times"], c["Values"])
+                for c in self.Clips[clip]["Channels"] if c["Node"] in index]
+
+    def UploadSkeleton(self, device, skeleton: int = 0):
+        """softwarerenderer_amd.Skeleton of Skeletons[skeleton] with every clip of the model added: clip i of the result is Clips[i]."""
+        from .rasterizer import Skeleton
+        sk = self.Skeletons[skeleton]
+        out = Skeleton(device, sk["Parent"], sk["RestLocal"], sk["RestT"], sk["RestR"], sk["RestS"], sk["JointNode"], sk["InverseBind"])
+        for c in range(len(self.Clips)):
+            out.AddClip(self.ClipChannels(skeleton, c))
+        return out
 
     def FramePair(self, time: float, fps: float = 30.0):
         """(i, j, t): the key frames AnimationFrames[i] and [j] around `time` seconds at `fps` frames a second, and the blend
@@ -344,12 +457,14 @@ class Model:
         cached = Model._model_cache.get(path)
         if cached is not None:                                                  # ModelLoader.cs:80-86,118-124
             self.Meshes, self.Lights, self.AnimationFrames, self.Skins = cached.Meshes, cached.Lights, cached.AnimationFrames, cached.Skins
+            self.Skeletons, self.Clips = cached.Skeletons, cached.Clips
             return self
         if os.path.isdir(path):                                                 # a directory = animation frames, :79-115
             files = sorted(f for f in os.listdir(path) if os.path.splitext(f)[1].lower() in Model.SUPPORTED)
             self.AnimationFrames = [Model()._load_single(os.path.join(path, f)) for f in files]
             if self.AnimationFrames:
                 self.Meshes, self.Lights, self.Skins = self.AnimationFrames[0].Meshes, self.AnimationFrames[0].Lights, self.AnimationFrames[0].Skins
+                self.Skeletons, self.Clips = self.AnimationFrames[0].Skeletons, self.AnimationFrames[0].Clips
         elif os.path.isfile(path):
             self._load_single(path)
         else:
@@ -360,8 +475,8 @@ class Model:
     def _load_single(self, path: str) -> "Model":
         ext = os.path.splitext(path)[1].lower()
         if ext == ".gltf":
-            self.Skins = []
-            self.Meshes = _load_gltf(path, self.Skins)
+            self.Skins, self.Skeletons, self.Clips = [], [], []
+            self.Meshes = _load_gltf(path, self.Skins, self.Skeletons, self.Clips)
         elif ext == ".obj":
             self.Meshes = _load_obj(path)
         else:

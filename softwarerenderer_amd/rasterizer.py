@@ -251,6 +251,17 @@ class Device:
     def sync(self):
         self._ck(self._lib.swr_sync(self._ctx))
 
+    def SkinBatch(self, dsts, srcs, pose_set: "PoseSet", instances):
+        """swr_mesh_skin_batch: dsts[k] = srcs[k] skinned by the palette of instances[k] of `pose_set`, all jobs in one kernel launch
+        (word for word what Mesh.SkinFrom gives with that palette).  Two jobs may share a source or an instance."""
+        n = len(dsts)
+        if len(srcs) != n or len(instances) != n:
+            raise ValueError("dsts, srcs and instances must have equal lengths")
+        d = (C.c_void_p * max(n, 1))(*[m._h.value if m is not None else None for m in dsts])
+        q = (C.c_void_p * max(n, 1))(*[m._h.value if m is not None else None for m in srcs])
+        i = np.ascontiguousarray(instances, dtype=np.int32).reshape(-1)
+        self._ck(self._lib.swr_mesh_skin_batch(self._ctx, n, d, q, pose_set._h if pose_set is not None else None, i.ctypes.data if n else None))
+
 
 class PostProgram:
     """A post-process program (swr_post_create): C++ defining `swr_post` (contract in include/swr.h), compiled for the device at
@@ -1025,6 +1036,98 @@ class Mesh:
     def Dispose(self):
         if self._h:
             self._dev._ck(self._dev._lib.swr_mesh_destroy(self._dev._ctx, self._h))
+            self._h = C.c_void_p()
+
+
+# ---- skeletal animation (build-defined; include/swr.h "SKELETAL ANIMATION")
+ANIM_PATHS = {"translation": N.SWR_ANIM_PATH_TRANSLATION, "rotation": N.SWR_ANIM_PATH_ROTATION, "scale": N.SWR_ANIM_PATH_SCALE}
+ANIM_INTERPOLATIONS = {"STEP": N.SWR_ANIM_STEP, "LINEAR": N.SWR_ANIM_LINEAR, "CUBICSPLINE": N.SWR_ANIM_CUBICSPLINE}
+POSE_REQUEST_DTYPE = np.dtype([("clip_a", "<i4"), ("time_a", "<f4"), ("clip_b", "<i4"), ("time_b", "<f4"), ("weight", "<f4")])
+
+
+class Skeleton:
+    """swr_skeleton: nodes in topological order (parent[i] < i, -1 for a root) with their rest matrices and rest T / R / S, the joints
+    (the node each is, its inverse bind matrix) and the clips added to it.  Matrices are 4 x 4, row-major for row vectors."""
+
+    def __init__(self, device: Device, parent, rest_local, rest_t, rest_r, rest_s, joint_node, inverse_bind):
+        self._dev = device
+        par = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        n = int(par.size)
+        loc, t, r, sc = _f32(rest_local, 16 * n), _f32(rest_t, 3 * n), _f32(rest_r, 4 * n), _f32(rest_s, 3 * n)
+        jn = np.ascontiguousarray(joint_node, dtype=np.int32).reshape(-1)
+        ib = _f32(inverse_bind, 16 * int(jn.size))
+        self.n_nodes, self.n_joints, self.n_clips = n, int(jn.size), 0
+        self._h = C.c_void_p()
+        device._ck(device._lib.swr_skeleton_create(device._ctx, n, par.ctypes.data, loc.ctypes.data, t.ctypes.data, r.ctypes.data, sc.ctypes.data,
+                                                   self.n_joints, jn.ctypes.data, ib.ctypes.data, C.byref(self._h)))
+
+    def AddClip(self, channels) -> int:
+        """swr_skeleton_add_clip: `channels` is a sequence of (node, path, interpolation, times, values) -- path one of "translation",
+        "rotation", "scale" (or SWR_ANIM_PATH_*), interpolation "STEP" or "LINEAR" (or SWR_ANIM_*), times n_keys floats, values
+        n_keys x 3 (x 4 for a rotation, xyzw).  Returns the clip's index.  A load-time call: it may wait for the device."""
+        keep, recs = [], (N.AnimChannel * max(len(channels), 1))()
+        for k, (node, path, interp, times, values) in enumerate(channels):
+            path = ANIM_PATHS.get(path, path) if isinstance(path, str) else int(path)
+            interp = ANIM_INTERPOLATIONS.get(interp, interp) if isinstance(interp, str) else int(interp)
+            if isinstance(path, str) or isinstance(interp, str):
+                raise ValueError(f"unknown animation path or interpolation: {path!r}, {interp!r}")
+            tm = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+            va = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+            if va.size != tm.size * (4 if path == N.SWR_ANIM_PATH_ROTATION else 3):
+                raise ValueError("a channel's values must hold 3 floats per key (4 for a rotation)")
+            keep += [tm, va]
+            recs[k] = N.AnimChannel(int(node), path, interp, int(tm.size), tm.ctypes.data, va.ctypes.data)
+        idx = C.c_int(-1)
+        self._dev._ck(self._dev._lib.swr_skeleton_add_clip(self._dev._ctx, self._h, recs, len(channels), C.byref(idx)))
+        self.n_clips = idx.value + 1
+        return idx.value
+
+    def Dispose(self):
+        if self._h:
+            self._dev._ck(self._dev._lib.swr_skeleton_destroy(self._dev._ctx, self._h))
+            self._h = C.c_void_p()
+
+
+class PoseSet:
+    """swr_pose_set: n_instances x n_joints joint matrices on the device -- sampled from a skeleton's clips on the GPU (Sample) or made
+    on the host (Upload) -- that Device.SkinBatch skins a crowd from."""
+
+    def __init__(self, device: Device, n_instances: int, n_joints: int):
+        self._dev, self.n_instances, self.n_joints = device, int(n_instances), int(n_joints)
+        self._h = C.c_void_p()
+        device._ck(device._lib.swr_pose_set_create(device._ctx, self.n_instances, self.n_joints, C.byref(self._h)))
+
+    @staticmethod
+    def Requests(clip_a, time_a, clip_b=-1, time_b=0.0, weight=0.0) -> np.ndarray:
+        """POSE_REQUEST_DTYPE records from scalars or arrays (broadcast against clip_a)."""
+        ca = np.atleast_1d(np.asarray(clip_a, dtype=np.int32))
+        r = np.zeros(ca.shape[0], dtype=POSE_REQUEST_DTYPE)
+        r["clip_a"], r["time_a"], r["clip_b"], r["time_b"], r["weight"] = ca, time_a, clip_b, time_b, weight
+        return r
+
+    def Sample(self, skeleton: Skeleton, requests) -> "PoseSet":
+        """swr_pose_set_sample: instance i from requests[i] (POSE_REQUEST_DTYPE: clip_a, time_a, clip_b or -1, time_b, weight) for
+        i < len(requests) <= n_instances, on the GPU; no host wait."""
+        r = np.ascontiguousarray(requests, dtype=POSE_REQUEST_DTYPE).reshape(-1)
+        self._dev._ck(self._dev._lib.swr_pose_set_sample(self._dev._ctx, self._h, skeleton._h if skeleton is not None else None,
+                                                         r.ctypes.data if r.size else None, int(r.size)))
+        return self
+
+    def Upload(self, first: int, palettes) -> "PoseSet":
+        """swr_pose_set_upload: host-made palettes (n x n_joints x 4 x 4) into instances first .. first + n - 1; no host wait."""
+        p = np.ascontiguousarray(palettes, dtype=np.float32).reshape(-1, self.n_joints * 16)
+        self._dev._ck(self._dev._lib.swr_pose_set_upload(self._dev._ctx, self._h, int(first), int(p.shape[0]), p.ctypes.data if p.size else None))
+        return self
+
+    def Read(self) -> np.ndarray:
+        """swr_pose_set_readback: (n_instances, n_joints, 4, 4) as the device holds them; waits for the set's last write only."""
+        out = np.zeros((self.n_instances, self.n_joints, 4, 4), dtype=np.float32)
+        self._dev._ck(self._dev._lib.swr_pose_set_readback(self._dev._ctx, self._h, out.ctypes.data))
+        return out
+
+    def Dispose(self):
+        if self._h:
+            self._dev._ck(self._dev._lib.swr_pose_set_destroy(self._dev._ctx, self._h))
             self._h = C.c_void_p()
 
 
