@@ -13,7 +13,8 @@ on ties.  It is the reference of every GPU test:
     product, adds with the rounding error recovered (TwoSum), rounds to odd and then to float32 -- one rounding, as the hardware fma
     (held to exact rational arithmetic in the host test).
 
-`rule` and `u_sense` make the three host mutants of the restatement (test_raycast_host.py::test_host_mutants_turn_named_cases_red).
+`rule` and `u_sense` make the three host mutants of the restatement (test_raycast_host.py::test_host_mutants_turn_named_cases_red);
+the `mut` tuple names the further ones of MUTANTS (tests/test_raycast_edges_host.py); with mut=() the arithmetic is untouched.
 
 The case lists: HOST_CASES (KAT, face masks, inclusive edges, degenerate rays, +-0 on the plane), count_case (T triangles, the only hit
 in the last / first), tie cases (coplanar twins, +0.0 / -0.0 twins), shape_case (rays x targets with models of their own and one zero
@@ -128,8 +129,12 @@ def miss_record(target):
     return r
 
 
-def intersect(origin, direction, P, idx, mask, order, fused, u_sense=">"):
-    """RayIntersectsTriangle + `if (distance < 0)` over all triangles: (alive, distance, u, v, normalised direction)."""
+MUTANTS = ("det_back_le", "det_front_ge", "absdet_le", "uv_sum_ge", "dist_le", "key_le_max", "key_unchecked", "key_flush", "fold_le")
+
+
+def intersect(origin, direction, P, idx, mask, order, fused, u_sense=">", mut=(), probe=None):
+    """RayIntersectsTriangle + `if (distance < 0)` over all triangles: (alive, distance, u, v, normalised direction).  `mut` names
+    host mutants (MUTANTS; () = the reference); `probe`, if given, is called with (det, alive before the distance test, alive, dist) and changes nothing."""
     o = np.asarray(origin, dtype=F32)
     d = normalize3v(np.asarray(direction, dtype=F32), order)                 # :69
     tri = np.asarray(idx, dtype=np.int64).reshape(-1)
@@ -141,30 +146,43 @@ def intersect(origin, direction, P, idx, mask, order, fused, u_sense=">"):
         det = dot3v(e1, pvec, order)
         alive = np.ones(tri.shape[0], dtype=bool)
         if mask & 1:
-            alive &= ~(det < EPS)
+            alive &= ~((det <= EPS) if "det_back_le" in mut else (det < EPS))
         if mask & 2:
-            alive &= ~(det > -EPS)
-        alive &= ~(np.abs(det) < EPS)
+            alive &= ~((det >= -EPS) if "det_front_ge" in mut else (det > -EPS))
+        alive &= ~((np.abs(det) <= EPS) if "absdet_le" in mut else (np.abs(det) < EPS))
         inv = F32(1.0) / det
         tvec = o - v0
         u = dot3v(tvec, pvec, order) * inv
         alive &= ~((u < 0) | ((u >= 1) if u_sense == ">=" else (u > 1)))
         qvec = cross3v(tvec, e1, fused)
         v = dot3v(d, qvec, order) * inv
-        alive &= ~((v < 0) | (u + v > 1))
+        alive &= ~((v < 0) | ((u + v >= 1) if "uv_sum_ge" in mut else (u + v > 1)))
         dist = dot3v(e2, qvec, order) * inv
-        alive &= ~(dist < 0)
+        before = alive.copy()
+        alive &= ~((dist <= 0) if "dist_le" in mut else (dist < 0))
+    if probe is not None:
+        probe(det, before, alive, dist)
     return alive, dist, u, v, d, tri
 
 
-def winner(alive, dist, rule="serial"):
+def winner(alive, dist, rule="serial", mut=()):
     """Index of the triangle RaycastInternal keeps, or None.  rule: 'serial' = the reference (strict `<` from float.MaxValue over
     0, 1, 2, ...); 'le' = the mutant `<=` (the LAST of equals); 'rawbits' = the mutant that orders the unsigned distance words
-    without mapping -0.0 to +0.0."""
+    without mapping -0.0 to +0.0.  mut: 'key_le_max' lets float.MaxValue itself win, 'key_unchecked' lets every surviving distance
+    win, NaN and +Inf included, in the order of their words (-0.0 as +0.0), 'key_flush' orders subnormal distances as zero."""
     with np.errstate(all="ignore"):
-        cand = alive & (dist < FLT_MAX)
+        cand = alive & ((dist <= FLT_MAX) if "key_le_max" in mut else (dist < FLT_MAX))
+    if "key_unchecked" in mut:
+        cand = alive.copy()
     if not cand.any():
         return None
+    if "key_unchecked" in mut or "key_flush" in mut:
+        w = np.ascontiguousarray(dist).view(np.uint32).astype(np.uint64)
+        w = np.where(w == 0x80000000, np.uint64(0), w)
+        if "key_flush" in mut:
+            w = np.where(w < 0x00800000, np.uint64(0), w)
+        key = (w << np.uint64(32)) | np.arange(dist.shape[0], dtype=np.uint64)
+        return int(np.argmin(np.where(cand, key, np.uint64(0xffffffffffffffff))))
     if rule == "rawbits":
         key = (np.ascontiguousarray(dist).view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.arange(dist.shape[0], dtype=np.uint64)
         return int(np.argmin(np.where(cand, key, np.uint64(0xffffffffffffffff))))
@@ -174,10 +192,10 @@ def winner(alive, dist, rule="serial"):
     return int(np.argmin(d))                                                 # first occurrence of the minimum; -0.0 == +0.0
 
 
-def raycast(origin, direction, P, N, idx, mask, order, fused, target=0, rule="serial", u_sense=">"):
+def raycast(origin, direction, P, N, idx, mask, order, fused, target=0, rule="serial", u_sense=">", mut=(), probe=None):
     """Physics.Raycast for one ray and one mesh whose world arrays are P, N: one RAY_HIT_DTYPE record."""
-    alive, dist, u, v, d, tri = intersect(origin, direction, P, idx, mask, order, fused, u_sense)
-    w = winner(alive, dist, rule)
+    alive, dist, u, v, d, tri = intersect(origin, direction, P, idx, mask, order, fused, u_sense, mut, probe)
+    w = winner(alive, dist, rule, mut)
     r = miss_record(target)
     if w is None:
         return r
@@ -191,11 +209,11 @@ def raycast(origin, direction, P, N, idx, mask, order, fused, target=0, rule="se
     return r
 
 
-def fold_nearest(row):
-    """The callers' `if (hit && distance < best)` over one ray's records in target order, from "not found"."""
+def fold_nearest(row, mut=()):
+    """The callers' `if (hit && distance < best)` over one ray's records in target order, from "not found" (mut 'fold_le': `<=`)."""
     best = miss_record(-1)
     for r in row:
-        if r["found"] and (not best["found"] or r["distance"] < best["distance"]):
+        if r["found"] and (not best["found"] or (r["distance"] <= best["distance"] if "fold_le" in mut else r["distance"] < best["distance"])):
             best = r.copy()
     return best
 
@@ -396,9 +414,9 @@ def dust2_case():
 
 
 # ============================================================================ a case on the reference
-def reference(lib, variant, case, fused=False, rule="serial", u_sense=">", flag=None):
+def reference(lib, variant, case, fused=False, rule="serial", u_sense=">", flag=None, mut=(), probe=None):
     """(n_rays, n_targets) records of `case` under the oracle build `lib`, its run-time Transform flag `flag` (None = the build's
-    default) and the given Cross model.  The world arrays are kept on the Target per (variant, flag)."""
+    default) and the given Cross model.  The world arrays are kept on the Target per (variant, flag).  `mut` / `probe`: see intersect."""
     from cull_edge_cases import oracle_flags
     order = DOT_ORDER[variant]
     out = np.zeros((case.origins.shape[0], len(case.targets)), dtype=RAY_HIT_DTYPE)
@@ -409,5 +427,5 @@ def reference(lib, variant, case, fused=False, rule="serial", u_sense=">", flag=
                 tg.world[key] = world_arrays(lib, tg.vertices, tg.model, tg.normal_matrix)
         P, N = tg.world[key]
         for r in range(case.origins.shape[0]):
-            out[r, t] = raycast(case.origins[r], case.directions[r], P, N, tg.indices, case.mask, order, fused, t, rule, u_sense)
+            out[r, t] = raycast(case.origins[r], case.directions[r], P, N, tg.indices, case.mask, order, fused, t, rule, u_sense, mut, probe)
     return out

@@ -20,10 +20,8 @@ anywhere: every record of every (ray, target) pair is compared -- found, target,
     has grown under it, on a context of its own;
   - arguments: the INVALID_ARG / UNSUPPORTED cases and the empty calls.
 
-Device mutants (one change in a scratch copy of csrc/, the product library rebuilt, this file run once on it) have NOT been run for
-this file: the two the restatement's host mutants correspond to are `<=` in the key order (ray_key: the HIGHER triangle of equals,
-i.e. ~tri in the low word) and the key without the +-0 mapping; tests/test_raycast_host.py records which cases each turns red in
-the restatement (all five tie cases; zero_twins_minus_first), and test_ties here runs exactly those cases on the device."""
+Device mutants (one change in a scratch copy of csrc/, built as a library of its own, this file and tests/test_gpu_raycast_edges.py
+run once on it): profiles/r25_raycast_edges.md lists them, with the tests each turned red."""
 import ctypes as C
 import os
 
