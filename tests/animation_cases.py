@@ -42,24 +42,53 @@ def same_words(got, want):
 
 
 # ============================================================================ restatement
-def find_key(times, t):
-    """(k, u): key k as stored when u is None, else keys k and k + 1 at u = (t - T[k]) / (T[k+1] - T[k]) (the interpolation decides)."""
+MUTANTS = ("first_lt", "last_gt", "search_lt", "key_at_u0", "norm_stored", "dot_gt", "dot_signbit", "rsqrt_flush", "targeted_by_a_only",
+           "left_nested")
+"""One-token departures from the definition that the restatement can take on request (`mut`, a tuple of these names; () is the
+definition): tests/test_animation_edges_host.py shows which cases of tests/animation_edge_cases.py each one turns red.
+  first_lt            t < T[0] in place of !(t > T[0])            last_gt     t > T[n-1] in place of t >= T[n-1]
+  search_lt           T[mid] < t in the binary search             key_at_u0   an interior key hit exactly returns the stored key
+  norm_stored         stored keys are normalised too              dot_gt      dot > 0 adds
+  dot_signbit         the arm is chosen by dot's sign bit         rsqrt_flush a subnormal ls is taken as 0
+  targeted_by_a_only  the untargeted test ignores clip b          left_nested ((l_i x l_p) x l_pp) x ... up the chain
+A `probe`, where given, is called as probe(kind, **facts):
+  "channel"  once per sampled channel: node, path, interpolation, t, arm ("first" | "last" | "between"), k, u (None unless between),
+             dup_before (T[k-1] == T[k]), dup_after (T[k] == T[k+1]), and dot, ls, inv of the key interpolation (None where no
+             Quaternion.Lerp ran); times and key (the channel's key times and the stored key k)
+  "blend"    once per two-clip Quaternion.Lerp: node, dot, ls, inv
+  "node"     once per node and request: node, targeted ("none" | "a" | "b" | "both"; "a" also for a single clip)"""
+
+
+def find_key(times, t, mut=(), probe=None):
+    """(k, u): key k as stored when u is None, else keys k and k + 1 at u = (t - T[k]) / (T[k+1] - T[k]) (the interpolation decides).
+    probe, where given, is called with (arm, k, u)."""
     tm = np.asarray(times, dtype=F32)
     t = F32(t)
     n = tm.shape[0]
-    if not (t > tm[0]):                       # (a NaN t lands here)
+    if (t < tm[0]) if "first_lt" in mut else (not (t > tm[0])):       # (a NaN t lands here)
+        if probe is not None:
+            probe("first", 0, None)
         return 0, None
-    if t >= tm[n - 1]:
+    if (t > tm[n - 1]) if "last_gt" in mut else (t >= tm[n - 1]):
+        if probe is not None:
+            probe("last", n - 1, None)
         return n - 1, None
     lo, hi = 0, n - 1                         # T[lo] <= t < T[hi]
     while hi - lo > 1:
         mid = (lo + hi) >> 1
-        if tm[mid] <= t:
+        if (tm[mid] < t) if "search_lt" in mut else (tm[mid] <= t):
             lo = mid
         else:
             hi = mid
+    if "key_at_u0" in mut and lo > 0 and t == tm[lo]:
+        if probe is not None:
+            probe("between", lo, None)
+        return lo, None
     with np.errstate(all="ignore"):
-        return lo, F32(F32(t - tm[lo]) / F32(tm[lo + 1] - tm[lo]))
+        u = F32(F32(t - tm[lo]) / F32(tm[lo + 1] - tm[lo]))
+    if probe is not None:
+        probe("between", lo, u)
+    return lo, u
 
 
 def lerp(a, b, u):
@@ -69,30 +98,61 @@ def lerp(a, b, u):
         return (a * u1 + b * u).astype(F32)
 
 
-def quaternion_lerp(a, b, u):
+def _normalised(r, mut=(), probe=None):
+    with np.errstate(all="ignore"):
+        ls = ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3]
+        if "rsqrt_flush" in mut and F32(0.0) < ls < np.finfo(F32).tiny:
+            ls = F32(0.0)
+        inv = F32(1.0) / np.sqrt(ls)
+        if probe is not None:
+            probe(ls, inv)
+        return (r * inv).astype(F32)
+
+
+def quaternion_lerp(a, b, u, mut=(), probe=None):
+    """probe, where given, is called with (dot, ls, inv)."""
     a, b, u = np.asarray(a, dtype=F32).reshape(4), np.asarray(b, dtype=F32).reshape(4), F32(u)
     with np.errstate(all="ignore"):
         u1 = F32(F32(1.0) - u)
         dot = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]
-        r = (u1 * a + u * b) if dot >= F32(0.0) else (u1 * a - u * b)
+        if "dot_gt" in mut:
+            adds = dot > F32(0.0)
+        elif "dot_signbit" in mut:
+            adds = not np.signbit(dot)
+        else:
+            adds = dot >= F32(0.0)
+        r = (u1 * a + u * b) if adds else (u1 * a - u * b)
         r = r.astype(F32)
-        ls = ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3]
-        inv = F32(1.0) / np.sqrt(ls)
-        return (r * inv).astype(F32)
+        return _normalised(r, mut, None if probe is None else (lambda ls, inv: probe(dot, ls, inv)))
 
 
-def blend_values(path, a, b, u):
-    return quaternion_lerp(a, b, u) if path == R else lerp(a, b, u)
+def blend_values(path, a, b, u, mut=(), probe=None):
+    return quaternion_lerp(a, b, u, mut, probe) if path == R else lerp(a, b, u)
 
 
-def sample_channel(ch, t):
+def sample_channel(ch, t, mut=(), probe=None):
     """One channel (node, path, interpolation, times, values) at time t."""
-    _, path, interp, times, values = ch
+    node, path, interp, times, values = ch
     values = np.asarray(values, dtype=F32).reshape(len(times), -1)
-    k, u = find_key(times, t)
+    seen = {}
+    if probe is None:
+        k, u = find_key(times, t, mut)
+    else:
+        k, u = find_key(times, t, mut, lambda arm, k, u: seen.update(arm=arm, k=k, u=u))
     if u is None or interp == STEP:
-        return values[k].copy()
-    return blend_values(path, values[k], values[k + 1], u)
+        out = values[k].copy()
+        if "norm_stored" in mut and path == R:
+            out = _normalised(out, mut)
+    else:
+        out = blend_values(path, values[k], values[k + 1], u, mut,
+                           None if probe is None else (lambda dot, ls, inv: seen.update(dot=dot, ls=ls, inv=inv)))
+    if probe is not None:
+        tm = np.asarray(times, dtype=F32)
+        kk = seen["k"]
+        probe("channel", node=int(node), path=int(path), interpolation=int(interp), t=F32(t), arm=seen["arm"], k=kk, u=seen["u"],
+              dup_before=bool(kk > 0 and tm[kk - 1] == tm[kk]), dup_after=bool(kk + 1 < len(tm) and tm[kk] == tm[kk + 1]),
+              dot=seen.get("dot"), ls=seen.get("ls"), inv=seen.get("inv"), times=tm, key=values[kk])
+    return out
 
 
 def create_from_quaternion(q):
@@ -157,7 +217,7 @@ class Skeleton:
         return d
 
 
-def locals_of(sk, clips, req):
+def locals_of(sk, clips, req, mut=(), probe=None):
     """Every node's local matrix under a request (clip_a, time_a, clip_b, time_b, weight); clips: a list of channel lists."""
     clip_a, time_a, clip_b, time_b, weight = req
     two = clip_b >= 0
@@ -170,19 +230,35 @@ def locals_of(sk, clips, req):
     rest = (sk.rest_t, sk.rest_r, sk.rest_s)
     out = sk.rest_local.copy()
     times = (time_a, time_b)
+    deciding = tables[:1] if "targeted_by_a_only" in mut else tables
     for i in range(sk.n_nodes):
-        if not any((i, p) in tab for tab in tables for p in (T, R, S)):
+        if probe is not None:
+            by = [any((i, p) in tab for p in (T, R, S)) for tab in tables] + [False]
+            probe("node", node=i, targeted="both" if by[0] and by[1] else "a" if by[0] else "b" if by[1] else "none")
+        if not any((i, p) in tab for tab in deciding for p in (T, R, S)):
             continue                                  # untargeted: the rest matrix's words
         trs = []
         for p in (T, R, S):
-            vals = [sample_channel(tab[(i, p)], times[k]) if (i, p) in tab else rest[p][i].copy() for k, tab in enumerate(tables)]
-            trs.append(blend_values(p, vals[0], vals[1], weight) if two else vals[0])
+            vals = [sample_channel(tab[(i, p)], times[k], mut, probe) if (i, p) in tab else rest[p][i].copy() for k, tab in enumerate(tables)]
+            if two:
+                blend_probe = None if probe is None or p != R else (lambda dot, ls, inv, i=i: probe("blend", node=i, dot=dot, ls=ls, inv=inv))
+                trs.append(blend_values(p, vals[0], vals[1], weight, mut, blend_probe))
+            else:
+                trs.append(vals[0])
         out[i] = compose(*trs)
     return out
 
 
-def worlds_of(sk, local):
+def worlds_of(sk, local, mut=(), probe=None):
     world = np.array(local, dtype=F32, copy=True)
+    if "left_nested" in mut:
+        for i in range(sk.n_nodes):
+            chain, p = [world[i]], sk.parent[i]
+            while p >= 0:
+                chain.append(local[p])
+                p = sk.parent[p]
+            world[i] = mul_left_nested(chain)
+        return world
     d = sk.depth()
     for level in range(1, int(d.max()) + 1 if sk.n_nodes else 0):
         nodes = np.nonzero(d == level)[0]
@@ -190,15 +266,15 @@ def worlds_of(sk, local):
     return world
 
 
-def palette_of(sk, clips, req):
-    world = worlds_of(sk, locals_of(sk, clips, req))
+def palette_of(sk, clips, req, mut=(), probe=None):
+    world = worlds_of(sk, locals_of(sk, clips, req, mut, probe), mut, probe)
     if sk.n_joints == 0:
         return np.zeros((0, 4, 4), dtype=F32)
     return mul(sk.inverse_bind, world[sk.joint_node])
 
 
-def palettes_of(sk, clips, requests):
-    return np.stack([palette_of(sk, clips, tuple(r)) for r in requests])
+def palettes_of(sk, clips, requests, mut=(), probe=None):
+    return np.stack([palette_of(sk, clips, tuple(r), mut, probe) for r in requests])
 
 
 # ============================================================================ generators
