@@ -5,6 +5,9 @@
 //     [k_frustum_cull ->] k_vertex -> k_setup -> k_bin<count> -> k_scan_sums/apply -> k_bin<fill> -> k_sort_tiles
 //     (+ the tile order in its last blocks) -> k_cover -> k_raster_c
 // There is no CPU fallback anywhere in this file: every pixel is produced by the HIP kernels.
+// The host side is this file -- the payload and present shapes and the entry points -- over swr_host.h (the types), swr_rtc.h (run-time
+// compilation), swr_flush.h (the flush path), swr_query.h (ray queries, the character update), swr_texture.h (textures and their probes)
+// and swr_deform.h (deforming meshes, skeletal animation); swr_query_layout.h and swr_animation_layout.h hold their layouts without HIP types.
 //
 // Frames in flight (swr_set_pipelining, on by default): the reference's loop renders frames back to back (Renderer.cs:404-419,
 // Rasterizer.cs:163-230), and a frame here has two halves with different bounds -- a front end of record traffic and latency
@@ -56,7 +59,7 @@ using namespace swr;
 #include "swr_host.h"
 #include "swr_rtc.h"
 #include "swr_flush.h"
-#include "swr_query.h"
+#include "swr_query.h"        // (swr_texture.h and swr_deform.h follow the payload shapes they use, below)
 
 namespace {      // shapes several entry points share
 // the band's colour plane as packed RGB floats in device memory, on the context's stream
@@ -288,177 +291,6 @@ int pixel_transfer(swr_context* c, int x, int y, void* plane, size_t bytes, void
     return sync_locked(c);
 }
 
-// swr_texture_update_from_frame: k_frame_to_texture by factors, alpha mode and whether the block-linear copy exists
-using RttKernel = void (*)(const float4*, uint32_t*, uint32_t*, uint32_t, uint32_t);
-RttKernel rtt_kernel(int kx, int ky, bool alpha, bool blocked) {
-    using K = RttKernel;
-    return with_flag<K>(alpha, [&](auto a) -> K { return with_flag<K>(blocked, [&](auto b) -> K { return with_factors<K>(kx, ky, [](auto x, auto y) -> K {
-        return k_frame_to_texture<decltype(x)::value, decltype(y)::value, decltype(a)::value, decltype(b)::value>; }); }); });
-}
-
-// swr_texture_update_from_depth: k_depth_to_texture by factors and whether the block-linear copy exists (the reduction is an argument)
-using DepthTextureKernel = void (*)(const float*, uint32_t*, uint32_t*, uint32_t, uint32_t, int);
-DepthTextureKernel depth_texture_kernel(int kx, int ky, bool blocked) {
-    using K = DepthTextureKernel;
-    return with_flag<K>(blocked, [&](auto b) -> K { return with_factors<K>(kx, ky, [](auto x, auto y) -> K {
-        return k_depth_to_texture<decltype(x)::value, decltype(y)::value, decltype(b)::value>; }); });
-}
-
-// does the call suit the texture's format?  (the texels of both formats are 4 bytes: nothing else tells them apart)
-int texture_format_check(swr_context* c, const swr_texture* t, int format) {
-    if (t->format == format) return SWR_OK;
-    return fail(c, SWR_ERR_INVALID_ARG, format == SWR_TEXTURE_FORMAT_DEPTH32F ? "the texture is not a depth texture (SWR_TEXTURE_FORMAT_DEPTH32F): this call reads or writes depth words"
-                                                                              : "the texture is a depth texture (SWR_TEXTURE_FORMAT_DEPTH32F): use the swr_texture_*_depth calls");
-}
-
-// MIP CHAINS.  offset[l] of a w x h texture's chain of `levels` levels: level l's first texel in the tail
-void mip_offsets(const swr_texture* t, int levels, uint32_t* offset) {
-    uint32_t at = 0;
-    offset[0] = 0;
-    for (int l = 1; l < levels; ++l) { offset[l] = at; at += (uint32_t)mip_level_side(t->w, l) * (uint32_t)mip_level_side(t->h, l); }
-}
-// the record in front of one of t's texel arrays (d_rgba or d_blocked) as t's chain is now, on the context's stream: in front of the
-// texels' own upload at creation, behind the flushed draws (which read the old record) when a chain appears
-hipError_t texture_header_write(swr_context* c, const swr_texture* t, uint8_t* texels) {
-    TextureHeader h = {};
-    h.levels = (uint32_t)t->levels;
-    h.tail = t->levels > 1 ? t->d_tail : nullptr;
-    mip_offsets(t, t->levels, h.offset);
-    hipLaunchKernelGGL(k_texture_header, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<uint32_t*>(texels - SWR_TEXTURE_HEADER_BYTES), h);
-    return hipGetLastError();
-}
-// levels 1 .. L - 1 from the row-major level 0, on the context's stream: two levels per launch (k_mip_downsample<true>) wherever the
-// source level's sides are multiples of 4 and the alignments of its 16-byte loads and 8-byte stores hold, else one
-int mip_generate(swr_context* c, const swr_texture* t) {
-    uint32_t off[SWR_TEXTURE_MAX_LEVELS];
-    mip_offsets(t, t->levels, off);
-    uint32_t* tail = reinterpret_cast<uint32_t*>(t->d_tail);
-    for (int l = 0; l + 1 < t->levels;) {
-        const uint32_t sw = (uint32_t)mip_level_side(t->w, l), sh = (uint32_t)mip_level_side(t->h, l);
-        const uint32_t* src = l == 0 ? reinterpret_cast<const uint32_t*>(t->d_rgba) : tail + off[l];
-        const bool two = l + 2 < t->levels && (sw & 3u) == 0 && (sh & 3u) == 0 && (l == 0 || (off[l] & 3u) == 0) && (off[l + 1] & 1u) == 0;
-        if (two) {
-            const auto [grid, block] = deliver_shape(sw >> 2, sh >> 2);
-            hipLaunchKernelGGL(k_mip_downsample<true>, grid, block, 0, c->stream, src, sw, sh, tail + off[l + 1], tail + off[l + 2]);
-        } else {
-            const auto [grid, block] = deliver_shape((uint32_t)mip_level_side(t->w, l + 1), (uint32_t)mip_level_side(t->h, l + 1));
-            hipLaunchKernelGGL(k_mip_downsample<false>, grid, block, 0, c->stream, src, sw, sh, tail + off[l + 1], (uint32_t*)nullptr);
-        }
-        SWR_HIP(c, hipGetLastError());
-        l += two ? 2 : 1;
-    }
-    // Vertex programs sample textures too, and a pipelined batch runs its k_vertex_user on the front stream: the next such front end
-    // starts behind this point of the raster stream (the hand-over an unpipelined batch leaves, execute_batch).  Front ends flushed
-    // EARLIER need nothing: the raster stream already waits for each of them (front_done), so these writes are behind them
-    if (c->pipelining && c->front_stream && c->r_front_ev) {
-        SWR_HIP(c, hipEventRecord(c->r_front_ev, c->stream));
-        c->r_front_pending = true;
-    }
-    return SWR_OK;
-}
-
-// swr_texture_create / _create_target / _create_depth: w x h 4-byte texels on the context's stream, the caller's or (texels null) the
-// format's empty word: zeros, or float.MinValue.  The array's header (no chain: one level) goes in front of it on the same stream.
-int texture_create(swr_context* c, const void* texels, int w, int h, swr_texture** out, const char* what_failed, int format = SWR_TEXTURE_FORMAT_RGBA8) {
-    if (w <= 0 || h <= 0 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture arguments");
-    if ((uint64_t)w * (uint64_t)h >= (1ull << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "textures of 2^30 texels or more are not supported (32-bit texel index)");
-    swr_texture* t = new swr_texture();
-    t->w = w; t->h = h; t->format = format;
-    const size_t bytes = (size_t)w * h * 4;
-    const float empty_depth = SWR_FLOAT_MINVALUE;
-    int empty = 0;
-    if (format == SWR_TEXTURE_FORMAT_DEPTH32F) memcpy(&empty, &empty_depth, 4);
-    hipError_t e = texels_alloc(&t->d_rgba, bytes);
-    if (e == hipSuccess) e = texture_header_write(c, t, t->d_rgba);
-    if (e == hipSuccess) e = texels ? hipMemcpyAsync(t->d_rgba, texels, bytes, hipMemcpyHostToDevice, c->stream)
-                                    : hipMemsetD32Async((hipDeviceptr_t)t->d_rgba, empty, (size_t)w * h, c->stream);
-    if (e != hipSuccess) {
-        texels_free(t->d_rgba);
-        delete t;
-        c->err = std::string(what_failed) + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
-    }
-    *out = t;
-    return SWR_OK;
-}
-
-// What a texture is updated from: src's colour plane (swr_texture_update_from_frame), program post_id of src between the resolve and
-// the quantiser (_from_post), or src's depth plane (_from_depth).  mode: the alpha mode, or the depth reduction.
-enum UpdateFrom { FROM_FRAME, FROM_POST, FROM_DEPTH };
-// by_face: one face of a cube (swr_texture_update_face_from_*), `face` as the caller gave it -- the same kernels
-// over the face's n x n texels, which start face * n * n texels into the row-major array and into the block-linear copy alike
-struct TextureUpdate { UpdateFrom from; int kx, ky, mode, post_id; int face = 0; bool by_face = false; };
-
-// Both contexts' mutexes are held (one when src == c).  Nothing here waits for a stream (but a first use or growth of src's resolved
-// plane, launch_post_over).
-int texture_update(swr_context* c, swr_texture* t, swr_context* src, const TextureUpdate& u) {
-    const int kx = u.kx, ky = u.ky;
-    const bool posted = u.from == FROM_POST, from_depth = u.from == FROM_DEPTH;
-    if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
-    if (u.by_face && !t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube, swr_texture_create_cube_depth)");
-    if (u.by_face && (u.face < 0 || u.face > 5)) return fail(c, SWR_ERR_INVALID_ARG, "face must be 0 .. 5 (+X, -X, +Y, -Y, +Z, -Z)");
-    const int tw = t->w, th = u.by_face ? t->w : t->h;                             // what the kernel writes: the texture, or one face of it
-    const size_t first = u.by_face ? (size_t)u.face * (size_t)t->w * (size_t)t->w : 0;   // its first texel, in texels
-    if (!from_depth && u.mode != SWR_TEXTURE_ALPHA_OPAQUE && u.mode != SWR_TEXTURE_ALPHA_KEEP)
-        return fail(c, SWR_ERR_INVALID_ARG, "alpha_mode must be SWR_TEXTURE_ALPHA_OPAQUE (0) or SWR_TEXTURE_ALPHA_KEEP (1)");
-    if (from_depth && u.mode != SWR_DEPTH_REDUCE_MAX && u.mode != SWR_DEPTH_REDUCE_MIN && u.mode != SWR_DEPTH_REDUCE_FIRST)
-        return fail(c, SWR_ERR_INVALID_ARG, "reduce must be SWR_DEPTH_REDUCE_MAX (0), SWR_DEPTH_REDUCE_MIN (1) or SWR_DEPTH_REDUCE_FIRST (2)");
-    if (int rc = texture_format_check(c, t, from_depth ? SWR_TEXTURE_FORMAT_DEPTH32F : SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (!resolve_factor_ok(kx) || !resolve_factor_ok(ky)) return fail(c, SWR_ERR_INVALID_ARG, "resolve factors must be 1, 2, 4 or 8");
-    if (src->device != c->device) return fail(c, SWR_ERR_UNSUPPORTED, "the source frame lives on another device");
-    if (src->W > 0 && src->H > 0 && (src->band_ty0 != 0 || band_rows(src) != src->H))
-        return fail(c, SWR_ERR_UNSUPPORTED, "the source context holds only a band of its frame (swr_set_band*)");
-    if ((long long)tw * kx != (long long)src->W || (long long)th * ky != (long long)src->H)
-        return fail(c, SWR_ERR_INVALID_ARG, u.by_face ? "the source frame must measure n * kx by n * ky for a cube map of side n"
-                                                      : "the source frame must measure texture width * kx by texture height * ky");
-    const PostProg* post = nullptr;
-    if (posted) {
-        const auto it = src->posts.find(u.post_id);
-        if (it == src->posts.end()) return fail(c, SWR_ERR_INVALID_ARG, "unknown or destroyed post program id");
-        post = it->second.get();
-        for (const swr_texture* bound : post->tex)
-            if (bound == t) return fail(c, SWR_ERR_INVALID_ARG, "the texture is bound to a slot of the program: a pass may not sample the texture it writes");
-    }
-    // (k_depth_to_texture loads kx words at once; the context's own plane is an allocation's start)
-    if (from_depth && ((uintptr_t)src->depth & 15u)) return fail(c, SWR_ERR_INVALID_ARG, "the source's bound depth buffer must be 16-byte aligned");
-    int rc;
-    // the frame is complete behind this point of src's stream, and c's recorded draws are in front of the kernel on c's stream: they
-    // sample the old texels (raster kernels and k_texture_sample, the only readers of a texture, run on `stream`, never on the front stream)
-    if ((rc = flush_locked(src))) { if (src != c) c->err = src->err; return rc; }
-    if (src != c && (rc = flush_locked(c))) return rc;
-    if (src != c && src->stream != c->stream) {
-        if (!src->rtt_frame_ev) SWR_HIP(c, hipEventCreateWithFlags(&src->rtt_frame_ev, hipEventDisableTiming));
-        SWR_HIP(c, hipEventRecord(src->rtt_frame_ev, src->stream));
-        SWR_HIP(c, hipStreamWaitEvent(c->stream, src->rtt_frame_ev, 0));
-    }
-    const bool blocked = t->d_blocked != nullptr;         // (made by swr_texture_set_filter: both sides are multiples of 4)
-    uint32_t* const d_rgba = reinterpret_cast<uint32_t*>(t->d_rgba) + first;
-    uint32_t* const d_blocked = blocked ? reinterpret_cast<uint32_t*>(t->d_blocked) + first : nullptr;
-    if (post) {
-        // (the resolve writes src's plane and the program may sample src's textures: both behind rtt_frame_ev, and src's later work --
-        // a present, an update of such a texture -- behind rtt_done_ev)
-        if ((rc = launch_post_over(c, src, post, u.mode == SWR_TEXTURE_ALPHA_KEEP ? POST_TEXELS_KEEP : POST_TEXELS_OPAQUE, kx, ky, d_rgba, d_blocked))) return rc;
-    } else {
-        const auto [grid, block] = deliver_shape((uint32_t)tw, (uint32_t)th);
-        if (from_depth)
-            hipLaunchKernelGGL(depth_texture_kernel(kx, ky, blocked), grid, block, 0, c->stream, (const float*)src->depth,
-                               d_rgba, d_blocked, (uint32_t)tw, (uint32_t)th, u.mode);
-        else
-            hipLaunchKernelGGL(rtt_kernel(kx, ky, u.mode == SWR_TEXTURE_ALPHA_KEEP, blocked), grid, block, 0, c->stream, (const float4*)src->color,
-                               d_rgba, d_blocked, (uint32_t)tw, (uint32_t)th);
-        SWR_HIP(c, hipGetLastError());
-    }
-    // a chain is a property of the texture: its levels follow the new level 0, on the same stream (a texture without one: nothing)
-    if (t->levels > 1 && (rc = mip_generate(c, t))) return rc;
-    if (src != c && src->stream != c->stream) {
-        // src's next raster, clear or upload may not overwrite the frame under the kernel
-        if (!c->rtt_done_ev) SWR_HIP(c, hipEventCreateWithFlags(&c->rtt_done_ev, hipEventDisableTiming));
-        SWR_HIP(c, hipEventRecord(c->rtt_done_ev, c->stream));
-        SWR_HIP(c, hipStreamWaitEvent(src->stream, c->rtt_done_ev, 0));
-    }
-    return SWR_OK;
-}
-
 // swr_program_validate* / swr_post_validate: the compiler's messages, NUL-terminated and truncated to the caller's buffer
 void copy_log(const std::string& msg, char* log, int log_len) {
     if (!log || log_len <= 0) return;
@@ -466,6 +298,9 @@ void copy_log(const std::string& msg, char* log, int log_len) {
     memcpy(log, msg.data(), n); log[n] = '\0';
 }
 }  // namespace
+
+#include "swr_texture.h"
+#include "swr_deform.h"
 
 extern "C" {
 
@@ -820,30 +655,6 @@ int swr_texture_create_depth(swr_context* c, const float* depth, int w, int h, s
     return texture_create(c, depth, w, h, out, depth ? "texture upload failed: " : "texture allocation failed: ", SWR_TEXTURE_FORMAT_DEPTH32F);
 }
 
-namespace {
-// swr_texture_update_from_frame / _from_post / _from_depth under the mutexes of both contexts
-int texture_update_locked(swr_context* c, swr_texture* t, swr_context* src, const TextureUpdate& u) {
-    if (!c) return SWR_ERR_INVALID_ARG;
-    if (!src || src == c) {
-        std::lock_guard<std::mutex> lock_(c->mu);
-        (void)hipSetDevice(c->device);
-        return texture_update(c, t, c, u);
-    }
-    std::lock(c->mu, src->mu);                            // (both, in an order that cannot deadlock against the opposite call)
-    std::lock_guard<std::mutex> lock_c(c->mu, std::adopt_lock), lock_s(src->mu, std::adopt_lock);
-    (void)hipSetDevice(c->device);
-    return texture_update(c, t, src, u);
-}
-
-// swr_texture_readback / _readback_depth: the row-major texels of a texture of `format`
-int texture_readback(swr_context* c, const swr_texture* t, void* out, int format) {
-    if (!t || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback arguments");
-    if (int rc = texture_format_check(c, t, format)) return rc;
-    SWR_HIP(c, hipMemcpyAsync(out, t->d_rgba, (size_t)t->w * t->h * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-}  // namespace
-
 int swr_texture_update_from_frame(swr_context* c, swr_texture* t, swr_context* src, int kx, int ky, int alpha_mode) {
     return texture_update_locked(c, t, src, TextureUpdate{ FROM_FRAME, kx, ky, alpha_mode, 0 });
 }
@@ -857,187 +668,20 @@ int swr_texture_update_from_depth(swr_context* c, swr_texture* t, swr_context* s
 int swr_texture_readback(swr_context* c, const swr_texture* t, uint8_t* rgba8) { SWR_ENTER(c); return texture_readback(c, t, rgba8, SWR_TEXTURE_FORMAT_RGBA8); }
 int swr_texture_readback_depth(swr_context* c, const swr_texture* t, float* out) { SWR_ENTER(c); return texture_readback(c, t, out, SWR_TEXTURE_FORMAT_DEPTH32F); }
 
-int swr_texture_format(swr_context* c, const swr_texture* t, int* format) {
-    SWR_ENTER(c);
-    if (!t || !format) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_format arguments");
-    *format = t->format;
-    return SWR_OK;
-}
-
-int swr_texture_set_filter(swr_context* c, swr_texture* t, int bilinear) {
-    SWR_ENTER(c);
-    if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
-    t->bilinear = bilinear != 0;          // read when a draw is recorded
-    if (t->bilinear && !t->d_blocked && (t->w & 3) == 0 && (t->h & 3) == 0) {
-        // the four taps of a bilinear fetch: one 64-byte line 9 times out of 16 from a block-linear copy, two lines always from the
-        // row-major original (same stream as the upload and as the raster kernels that will read it)
-        SWR_HIP(c, texels_alloc(&t->d_blocked, (size_t)t->w * t->h * 4));
-        SWR_HIP(c, texture_header_write(c, t, t->d_blocked));          // (a copy of d_rgba's: the same levels, the same tail)
-        const int blocks = (int)std::min<size_t>(((size_t)t->w * t->h + 255) / 256, 2048 * 8);
-        hipLaunchKernelGGL(k_block_texture, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t*)t->d_rgba, (uint32_t*)t->d_blocked, t->w, t->h);
-        SWR_HIP(c, hipGetLastError());
-    }
-    return SWR_OK;
-}
-
-int swr_texture_destroy(swr_context* c, swr_texture* t) {
-    SWR_ENTER(c);
-    if (!t) return SWR_OK;
-    int rc = flush_and_sync_locked(c); if (rc) return rc;
-    for (auto& p : c->posts)                              // a later present reads "no texture" there
-        for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
-    for (auto& p : c->progs)                              // a later draw captures "no texture" there (recorded ones were flushed above)
-        for (const swr_texture*& bound : p.second->tex) if (bound == t) bound = nullptr;
-    texels_free(t->d_rgba);
-    texels_free(t->d_blocked);
-    if (t->d_tail) (void)hipFree(t->d_tail);
-    delete t;
-    return SWR_OK;
-}
-
-int swr_texture_sample(swr_context* c, const swr_texture* t, const float* uv, int n, float* out) {
-    SWR_ENTER(c);
-    if (!t || !uv || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample arguments");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (n == 0) return SWR_OK;
-    const size_t off_out = ((size_t)n * 8 + 15) & ~(size_t)15;
-    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 16);
-    if (rc) return rc;
-    float2* d_uv = c->d_scratch.as<float2>();
-    float4* d_out = reinterpret_cast<float4*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
-    SWR_HIP(c, hipMemcpyAsync(d_uv, uv, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_sample, dim3((n + 255) / 256), dim3(256), 0, c->stream, t->d_rgba, t->w, t->h, d_uv, n, d_out);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-int swr_texture_sample_depth(swr_context* c, const swr_texture* t, const float* uv_ref, int n, float* out) {
-    SWR_ENTER(c);
-    if (!t || !uv_ref || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_depth arguments");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_DEPTH32F)) return rc;
-    if (n == 0) return SWR_OK;
-    const size_t off_out = ((size_t)n * 12 + 15) & ~(size_t)15;
-    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 8);
-    if (rc) return rc;
-    float* d_in = c->d_scratch.as<float>();
-    float2* d_out = reinterpret_cast<float2*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
-    SWR_HIP(c, hipMemcpyAsync(d_in, uv_ref, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_sample_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float*)d_in, n, d_out);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-// ---- mip chains
-int swr_texture_generate_mipmaps(swr_context* c, swr_texture* t) {
-    SWR_ENTER(c);
-    if (!t) return fail(c, SWR_ERR_INVALID_ARG, "texture is null");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (t->cube && (t->w & (t->w - 1)) != 0)
-        return fail(c, SWR_ERR_UNSUPPORTED, "a cube map's chain needs a power-of-two side (per-face level sizes are out of scope, DESIGN.md section 27)");
-    const int L = texture_full_levels(t);                    // (a cube's chain ends where a face is one texel)
-    if (L == 1) return SWR_OK;                               // 1 x 1: a chain of one level, which it has
-    // immediate-mode semantics without a host wait (swr_texture_update_from_frame's): the recorded draws go first and read the old
-    // record -- the device reads it when a kernel runs, so the order on the stream is what "earlier" and "later" mean
-    int rc = flush_locked(c); if (rc) return rc;
-    if (!t->d_tail) {
-        uint32_t off[SWR_TEXTURE_MAX_LEVELS];
-        mip_offsets(t, L, off);
-        const size_t texels = (size_t)off[L - 1] + (size_t)mip_level_side(t->w, L - 1) * (size_t)mip_level_side(t->h, L - 1);
-        SWR_HIP(c, hipMalloc((void**)&t->d_tail, texels * 4));
-    }
-    if (t->levels != L) {
-        t->levels = L;
-        SWR_HIP(c, texture_header_write(c, t, t->d_rgba));
-        if (t->d_blocked) SWR_HIP(c, texture_header_write(c, t, t->d_blocked));
-    }
-    return mip_generate(c, t);
-}
-
-int swr_texture_levels(swr_context* c, const swr_texture* t, int* levels) {
-    SWR_ENTER(c);
-    if (!t || !levels) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_levels arguments");
-    *levels = t->levels;
-    return SWR_OK;
-}
-
-int swr_texture_level_size(swr_context* c, const swr_texture* t, int level, int* w, int* h) {
-    SWR_ENTER(c);
-    if (!t || !w || !h) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_level_size arguments");
-    if (level < 0 || level >= texture_full_levels(t)) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the texture's full chain (0 .. floor(log2(max(w, h))))");
-    *w = mip_level_side(t->w, level); *h = mip_level_side(t->h, level);
-    return SWR_OK;
-}
-
-int swr_texture_readback_level(swr_context* c, const swr_texture* t, int level, uint8_t* rgba8) {
-    SWR_ENTER(c);
-    if (!t || !rgba8) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback_level arguments");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (level < 0 || level >= t->levels) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the levels the texture has (swr_texture_levels)");
-    if (level == 0) return texture_readback(c, t, rgba8, SWR_TEXTURE_FORMAT_RGBA8);
-    uint32_t off[SWR_TEXTURE_MAX_LEVELS];
-    mip_offsets(t, t->levels, off);
-    const size_t bytes = (size_t)mip_level_side(t->w, level) * (size_t)mip_level_side(t->h, level) * 4;
-    SWR_HIP(c, hipMemcpyAsync(rgba8, t->d_tail + (size_t)off[level] * 4, bytes, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-int swr_texture_sample_lod(swr_context* c, const swr_texture* t, const float* uv_lod, int n, float* out_rgba) {
-    SWR_ENTER(c);
-    if (!t || !uv_lod || !out_rgba || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_lod arguments");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (n == 0) return SWR_OK;
-    const size_t off_out = ((size_t)n * 12 + 15) & ~(size_t)15;
-    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 16);
-    if (rc) return rc;
-    float* d_in = c->d_scratch.as<float>();
-    float4* d_out = reinterpret_cast<float4*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
-    SWR_HIP(c, hipMemcpyAsync(d_in, uv_lod, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_sample_lod, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float*)d_in, n, d_out);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-int swr_texture_lod(swr_context* c, const swr_texture* t, const float* grads, int n, float* out_lod) {
-    SWR_ENTER(c);
-    if (!t || !grads || !out_lod || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_lod arguments");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (n == 0) return SWR_OK;
-    const size_t off_out = (size_t)n * 16;
-    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 4);
-    if (rc) return rc;
-    float4* d_in = c->d_scratch.as<float4>();
-    float* d_out = reinterpret_cast<float*>(reinterpret_cast<char*>(c->d_scratch.p) + off_out);
-    SWR_HIP(c, hipMemcpyAsync(d_in, grads, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_lod, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out_lod, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-// ---- cube maps: an n x 6 n texture, face f in rows [f n, (f + 1) n)
-namespace {
-int cube_create(swr_context* c, const void* texels, int n, swr_texture** out, int format) {
-    if (n < 1 || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad cube map arguments");
-    if (6ull * (uint64_t)n * (uint64_t)n >= (1ull << 30)) return fail(c, SWR_ERR_INVALID_ARG, "cube maps of 2^30 texels or more are not supported (32-bit texel index)");
-    const int rc = texture_create(c, texels, n, 6 * n, out, texels ? "texture upload failed: " : "texture allocation failed: ", format);
-    if (rc == SWR_OK) (*out)->cube = true;
-    return rc;
-}
-}  // namespace
-
+int swr_texture_format(swr_context* c, const swr_texture* t, int* format) { SWR_ENTER(c); return texture_format(c, t, format); }
+int swr_texture_set_filter(swr_context* c, swr_texture* t, int bilinear) { SWR_ENTER(c); return texture_set_filter(c, t, bilinear); }
+int swr_texture_destroy(swr_context* c, swr_texture* t) { SWR_ENTER(c); return texture_destroy(c, t); }
+int swr_texture_sample(swr_context* c, const swr_texture* t, const float* uv, int n, float* out) { SWR_ENTER(c); return texture_sample(c, t, uv, n, out); }
+int swr_texture_sample_depth(swr_context* c, const swr_texture* t, const float* uv_ref, int n, float* out) { SWR_ENTER(c); return texture_sample_depth(c, t, uv_ref, n, out); }
+int swr_texture_generate_mipmaps(swr_context* c, swr_texture* t) { SWR_ENTER(c); return texture_generate_mipmaps(c, t); }
+int swr_texture_levels(swr_context* c, const swr_texture* t, int* levels) { SWR_ENTER(c); return texture_levels(c, t, levels); }
+int swr_texture_level_size(swr_context* c, const swr_texture* t, int level, int* w, int* h) { SWR_ENTER(c); return texture_level_size(c, t, level, w, h); }
+int swr_texture_readback_level(swr_context* c, const swr_texture* t, int level, uint8_t* rgba8) { SWR_ENTER(c); return texture_readback_level(c, t, level, rgba8); }
+int swr_texture_sample_lod(swr_context* c, const swr_texture* t, const float* uv_lod, int n, float* out_rgba) { SWR_ENTER(c); return texture_sample_lod(c, t, uv_lod, n, out_rgba); }
+int swr_texture_lod(swr_context* c, const swr_texture* t, const float* grads, int n, float* out_lod) { SWR_ENTER(c); return texture_lod(c, t, grads, n, out_lod); }
 int swr_texture_create_cube(swr_context* c, const uint8_t* rgba8, int n, swr_texture** out) { SWR_ENTER(c); return cube_create(c, rgba8, n, out, SWR_TEXTURE_FORMAT_RGBA8); }
 int swr_texture_create_cube_depth(swr_context* c, const float* depth, int n, swr_texture** out) { SWR_ENTER(c); return cube_create(c, depth, n, out, SWR_TEXTURE_FORMAT_DEPTH32F); }
-
-int swr_texture_is_cube(swr_context* c, const swr_texture* t, int* n) {
-    SWR_ENTER(c);
-    if (!t || !n) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_is_cube arguments");
-    *n = t->cube ? t->w : 0;
-    return SWR_OK;
-}
-
+int swr_texture_is_cube(swr_context* c, const swr_texture* t, int* n) { SWR_ENTER(c); return texture_is_cube(c, t, n); }
 int swr_texture_update_face_from_frame(swr_context* c, swr_texture* t, int face, swr_context* src, int kx, int ky, int alpha_mode) {
     return texture_update_locked(c, t, src, TextureUpdate{ FROM_FRAME, kx, ky, alpha_mode, 0, face, true });
 }
@@ -1048,22 +692,7 @@ int swr_texture_update_face_from_post(swr_context* c, swr_texture* t, int face, 
     return texture_update_locked(c, t, src, TextureUpdate{ FROM_POST, kx, ky, alpha_mode, post_id, face, true });
 }
 
-int swr_texture_readback_face(swr_context* c, const swr_texture* t, int face, int level, void* out) {
-    SWR_ENTER(c);
-    if (!t || !out) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_readback_face arguments");
-    if (!t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube, swr_texture_create_cube_depth)");
-    if (face < 0 || face > 5) return fail(c, SWR_ERR_INVALID_ARG, "face must be 0 .. 5 (+X, -X, +Y, -Y, +Z, -Z)");
-    if (level < 0 || level >= t->levels) return fail(c, SWR_ERR_INVALID_ARG, "the level is outside the levels the texture has (swr_texture_levels)");
-    const size_t n = (size_t)(t->w >> level);
-    const uint8_t* from = t->d_rgba;
-    if (level > 0) {
-        uint32_t off[SWR_TEXTURE_MAX_LEVELS];
-        mip_offsets(t, t->levels, off);
-        from = t->d_tail + (size_t)off[level] * 4;
-    }
-    SWR_HIP(c, hipMemcpyAsync(out, from + (size_t)face * n * n * 4, n * n * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
+int swr_texture_readback_face(swr_context* c, const swr_texture* t, int face, int level, void* out) { SWR_ENTER(c); return texture_readback_face(c, t, face, level, out); }
 
 int swr_cube_face_view(int face, const float* eye, float* view) {
     if (face < 0 || face > 5 || !eye || !view) return SWR_ERR_INVALID_ARG;
@@ -1082,58 +711,9 @@ int swr_cube_face_view(int face, const float* eye, float* view) {
     return SWR_OK;
 }
 
-int swr_texture_cube_face(swr_context* c, const float* dirs, int n, int* out_face, float* out_st) {
-    SWR_ENTER(c);
-    if (!dirs || !out_face || !out_st || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_cube_face arguments");
-    if (n == 0) return SWR_OK;
-    // faces and (s, t) come back in one block: n x (face, s, t) would interleave types, so two blocks, the second 16-byte aligned
-    const size_t off_face = ((size_t)n * 12 + 15) & ~(size_t)15, off_st = off_face + (((size_t)n * 4 + 15) & ~(size_t)15);
-    int rc = ensure(c, c->d_scratch, off_st + (size_t)n * 8);
-    if (rc) return rc;
-    char* base = reinterpret_cast<char*>(c->d_scratch.p);
-    SWR_HIP(c, hipMemcpyAsync(base, dirs, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_cube_face, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float*)base, n, (int*)(base + off_face), (float2*)(base + off_st));
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out_face, base + off_face, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    SWR_HIP(c, hipMemcpyAsync(out_st, base + off_st, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-int swr_texture_sample_cube(swr_context* c, const swr_texture* t, const float* dir_lod, int n, float* out_rgba) {
-    SWR_ENTER(c);
-    if (!t || !dir_lod || !out_rgba || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_cube arguments");
-    if (!t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube)");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_RGBA8)) return rc;
-    if (n == 0) return SWR_OK;
-    const size_t off_out = (size_t)n * 16;
-    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 16);
-    if (rc) return rc;
-    float4* d_in = c->d_scratch.as<float4>();
-    float4* d_out = d_in + n;
-    SWR_HIP(c, hipMemcpyAsync(d_in, dir_lod, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_sample_cube, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
-
-int swr_texture_sample_cube_depth(swr_context* c, const swr_texture* t, const float* dir_ref, int n, float* out) {
-    SWR_ENTER(c);
-    if (!t || !dir_ref || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad texture_sample_cube_depth arguments");
-    if (!t->cube) return fail(c, SWR_ERR_INVALID_ARG, "the texture is not a cube map (swr_texture_create_cube_depth)");
-    if (int rc = texture_format_check(c, t, SWR_TEXTURE_FORMAT_DEPTH32F)) return rc;
-    if (n == 0) return SWR_OK;
-    const size_t off_out = (size_t)n * 16;
-    int rc = ensure(c, c->d_scratch, off_out + (size_t)n * 8);
-    if (rc) return rc;
-    float4* d_in = c->d_scratch.as<float4>();
-    float2* d_out = reinterpret_cast<float2*>(d_in + n);
-    SWR_HIP(c, hipMemcpyAsync(d_in, dir_ref, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_texture_sample_cube_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, texture_slot_of(t), (const float4*)d_in, n, d_out);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    return sync_locked(c);
-}
+int swr_texture_cube_face(swr_context* c, const float* dirs, int n, int* out_face, float* out_st) { SWR_ENTER(c); return texture_cube_face(c, dirs, n, out_face, out_st); }
+int swr_texture_sample_cube(swr_context* c, const swr_texture* t, const float* dir_lod, int n, float* out_rgba) { SWR_ENTER(c); return texture_sample_cube(c, t, dir_lod, n, out_rgba); }
+int swr_texture_sample_cube_depth(swr_context* c, const swr_texture* t, const float* dir_ref, int n, float* out) { SWR_ENTER(c); return texture_sample_cube_depth(c, t, dir_ref, n, out); }
 
 int swr_mesh_create(swr_context* c, const swr_vertex* v, int nv, const uint16_t* idx, int ni, swr_mesh** out) { SWR_ENTER(c); return make_mesh(c, v, nv, idx, ni, false, out); }
 
@@ -1145,515 +725,29 @@ int swr_mesh_destroy(swr_context* c, swr_mesh* m) {
     return SWR_OK;
 }
 
-// ---- deforming meshes: key-frame blend and matrix-palette skinning into a retained mesh
-namespace {
-// a retained mesh of this context, or the message why not
-int deform_mesh_check(swr_context* c, const swr_mesh* m, const char* null_msg) {
-    if (!m) return fail(c, SWR_ERR_INVALID_ARG, null_msg);
-    if (m->transient) return fail(c, SWR_ERR_INVALID_ARG, "a transient mesh (swr_render_mesh_arrays) cannot be deformed, copied or read back");
-    if (m->owner != c) return fail(c, SWR_ERR_INVALID_ARG, "the mesh belongs to another context");
-    return SWR_OK;
+// ---- deforming meshes and skeletal animation (section 29): swr_deform.h
+int swr_mesh_create_like(swr_context* c, const swr_mesh* src, swr_mesh** out) { SWR_ENTER(c); return mesh_create_like(c, src, out); }
+int swr_mesh_readback(swr_context* c, const swr_mesh* mesh, swr_vertex* out) { SWR_ENTER(c); return mesh_readback(c, mesh, out); }
+int swr_mesh_blend(swr_context* c, swr_mesh* dst, const swr_mesh* a, const swr_mesh* b, float t) { SWR_ENTER(c); return mesh_blend(c, dst, a, b, t); }
+int swr_mesh_set_skin(swr_context* c, swr_mesh* m, const uint16_t* joints4, const float* weights4) { SWR_ENTER(c); return mesh_set_skin(c, m, joints4, weights4); }
+int swr_mesh_skin(swr_context* c, swr_mesh* dst, const swr_mesh* src, const float* palette, int n_joints) { SWR_ENTER(c); return mesh_skin(c, dst, src, palette, n_joints); }
+int swr_mesh_skin_batch(swr_context* c, int n, swr_mesh* const* dst, const swr_mesh* const* src, const swr_pose_set* set, const int32_t* instance) {
+    SWR_ENTER(c); return mesh_skin_batch(c, n, dst, src, set, instance);
 }
-
-bool batch_reads(const std::vector<DrawCmd>& draws, const swr_mesh* m) {
-    for (const DrawCmd& d : draws) if (d.mesh == m) return true;
-    return false;
-}
-
-// Everything that must happen before a kernel may WRITE dst's vertices; returns the stream it runs on.
-//   A. immediate-mode semantics: draws recorded so far that reference dst are launched first (they see the old vertices) -- and only
-//      then: a loop that deforms sixteen players and draws them stays one batch;
-//   B. an optimistic batch in flight that references dst may be replayed later (validate_locked), and a replay runs the front end
-//      again: it must read the vertices the batch saw, so the streams are drained and the batches validated before the first write
-//      (transient meshes solve the same problem through c->garbage: their buffers are not reused before the streams were idle).
-//      A loop that presents every frame has retired those batches in swr_present_wait: nothing to wait for there.
-// The deform runs where make_mesh uploads (use_front_stream): only front-end kernels read a mesh, and every front end issued later
-// is behind it -- on the front stream by stream order, on the context's stream through f_tail_pending (execute_batch).
-int deform_begin(swr_context* c, const swr_mesh* dst, hipStream_t* stream) {
-    int rc;
-    if (batch_reads(c->draws, dst) && (rc = flush_locked(c))) return rc;
-    bool in_flight = false;
-    for (const Batch& b : c->inflight) in_flight = in_flight || batch_reads(b.draws, dst);
-    if (in_flight && (rc = sync_locked(c))) return rc;
-    if ((rc = ensure_front_stream(c))) return rc;
-    *stream = use_front_stream(c);
-    return SWR_OK;
-}
-
-// ... and after it: what the host knows about dst's old vertices is void.
-//   C. readers on the ray stream (swr_raycast, swr_character_update, swr_mesh_readback) are ordered behind swr_mesh::uploaded: it is
-//      recorded again behind the deform.  The query entry points return only after their kernels finished (they wait for their own
-//      result under the context mutex), so no ray-stream reader of dst is in flight when a deform is issued;
-//   D. the bounding sphere is computed again on first use (swr_mesh_bounds, swr_render_mesh_culled follow the pose);
-//   E. the host-side box is gone: band_rejects keeps the draw on every rank (conservative and correct).
-int deform_end(swr_context* c, swr_mesh* dst, hipStream_t stream) {
-    SWR_HIP(c, hipEventRecord(dst->uploaded, stream));
-    dst->posed.reset();
-    dst->upload_seen = false;
-    dst->bounds_ready = false;
-    dst->has_box = false;
-    return SWR_OK;
-}
-
-// A palette's way to the device without a wait (F): the first slot whose last kernel is over, else a new one.
-int palette_slot(swr_context* c, size_t bytes, PaletteSlot** out, bool device_copy = true) {
-    PaletteSlot* s = nullptr;
-    const size_t n = c->palettes.size();
-    for (size_t k = 0; k < n && !s; ++k) {
-        PaletteSlot& q = c->palettes[(c->palette_next + k) % n];
-        if (q.busy && hipEventQuery(q.done) == hipSuccess) q.busy = false;
-        if (!q.busy) { s = &q; c->palette_next = (c->palette_next + k + 1) % n; }
-    }
-    if (!s && n < SWR_PALETTE_SLOTS_MAX) {
-        c->palettes.emplace_back();
-        s = &c->palettes.back();
-        SWR_HIP(c, hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
-    }
-    if (!s) {       // back-pressure: SWR_PALETTE_SLOTS_MAX palettes queued and none read yet
-        s = &c->palettes[c->palette_next % n];
-        c->palette_next = (c->palette_next + 1) % n;
-        SWR_HIP(c, hipEventSynchronize(s->done));
-        s->busy = false;
-    }
-    // (a free slot's buffers are idle: growing them frees nothing a kernel reads)
-    if (s->host.cap < bytes) SWR_HIP(c, ensure_pinned(s->host, std::max<size_t>(bytes, 4096)));
-    // (device_copy = false: staging for a copy that goes elsewhere, swr_pose_set_upload)
-    if (device_copy) { int rc = ensure(c, s->dev, std::max<size_t>(bytes, 4096)); if (rc) return rc; }
-    *out = s;
-    return SWR_OK;
-}
-}  // namespace
-
-int swr_mesh_create_like(swr_context* c, const swr_mesh* src, swr_mesh** out) {
-    SWR_ENTER(c);
-    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "out is null");
-    int rc = deform_mesh_check(c, src, "the source mesh is null"); if (rc) return rc;
-    if ((rc = ensure_front_stream(c))) return rc;
-    swr_mesh* m = new swr_mesh();
-    m->n_verts = src->n_verts; m->n_idx = src->n_idx; m->owner = c;
-    memcpy(m->box_lo, src->box_lo, sizeof m->box_lo); memcpy(m->box_hi, src->box_hi, sizeof m->box_hi);
-    m->has_box = src->has_box;
-    const size_t vbytes = (size_t)src->n_verts * sizeof(swr_vertex), ibytes = (size_t)src->n_idx * 2;
-    // behind src's upload or its last deform, on their stream: the arrays do not cross PCIe again
-    const hipStream_t s = use_front_stream(c);
-    hipError_t e = hipSuccess;
-    if (vbytes) { e = hipMalloc((void**)&m->d_verts, vbytes); if (e == hipSuccess) m->cap_verts = vbytes; }
-    if (e == hipSuccess && ibytes) { e = hipMalloc((void**)&m->d_idx, ibytes + 8); if (e == hipSuccess) m->cap_idx = ibytes + 8; }
-    if (e == hipSuccess && vbytes) e = hipMemcpyAsync(m->d_verts, src->d_verts, vbytes, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && ibytes) e = hipMemcpyAsync(m->d_idx, src->d_idx, ibytes, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->uploaded, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(m->uploaded, s);
-    if (e != hipSuccess) {
-        destroy_mesh(m);
-        c->err = std::string("mesh copy failed: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
-    }
-    *out = m;
-    return SWR_OK;
-}
-
-int swr_mesh_readback(swr_context* c, const swr_mesh* mesh, swr_vertex* out) {
-    SWR_ENTER(c);
-    int rc = deform_mesh_check(c, mesh, "the mesh is null"); if (rc) return rc;
-    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "the destination is null");
-    if (mesh->n_verts == 0) return SWR_OK;
-    // a reader on the ray stream: behind the upload or the last deform (swr_mesh::uploaded) and behind nothing else -- recorded draws
-    // are not flushed, a frame in flight is not waited for
-    if ((rc = ensure_ray_stream(c))) return rc;
-    swr_mesh* m = const_cast<swr_mesh*>(mesh);
-    if (!m->upload_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, m->posed ? m->posed->ev : m->uploaded, 0)); m->upload_seen = true; }
-    SWR_HIP(c, hipMemcpyAsync(out, m->d_verts, (size_t)m->n_verts * sizeof(swr_vertex), hipMemcpyDeviceToHost, c->ray_stream));
-    SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
-    return SWR_OK;
-}
-
-int swr_mesh_blend(swr_context* c, swr_mesh* dst, const swr_mesh* a, const swr_mesh* b, float t) {
-    SWR_ENTER(c);
-    int rc;
-    if ((rc = deform_mesh_check(c, dst, "the destination mesh is null"))) return rc;
-    if ((rc = deform_mesh_check(c, a, "key frame a is null"))) return rc;
-    if ((rc = deform_mesh_check(c, b, "key frame b is null"))) return rc;
-    if (dst == a || dst == b) return fail(c, SWR_ERR_INVALID_ARG, "the destination mesh is one of the key frames (make a target with swr_mesh_create_like)");
-    if (a->n_verts != dst->n_verts || b->n_verts != dst->n_verts) return fail(c, SWR_ERR_INVALID_ARG, "the key frames and the destination must have equal vertex counts");
-    if (dst->n_verts == 0) return SWR_OK;
-    hipStream_t s = nullptr;
-    if ((rc = deform_begin(c, dst, &s))) return rc;
-    const uint32_t n_words = 3u * (uint32_t)dst->n_verts;
-    hipLaunchKernelGGL(k_mesh_blend, dim3((n_words + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK), dim3(SWR_DEFORM_BLOCK), 0, s,
-                       reinterpret_cast<const float4*>(a->d_verts), reinterpret_cast<const float4*>(b->d_verts),
-                       reinterpret_cast<float4*>(dst->d_verts), n_words, t);
-    SWR_HIP(c, hipGetLastError());
-    return deform_end(c, dst, s);
-}
-
-int swr_mesh_set_skin(swr_context* c, swr_mesh* m, const uint16_t* joints4, const float* weights4) {
-    SWR_ENTER(c);
-    int rc = deform_mesh_check(c, m, "the mesh is null"); if (rc) return rc;
-    if ((joints4 == nullptr) != (weights4 == nullptr)) return fail(c, SWR_ERR_INVALID_ARG, "pass both joints4 and weights4, or NULL for both (which removes the attributes)");
-    if (!joints4) {
-        // (hipFree waits for the device: a queued k_mesh_skin has read them by then)
-        if (m->d_joints) SWR_HIP(c, hipFree(m->d_joints));
-        m->d_joints = nullptr;
-        if (m->d_weights) SWR_HIP(c, hipFree(m->d_weights));
-        m->d_weights = nullptr;
-        m->max_joint = -1; m->has_skin = false;
-        return SWR_OK;
-    }
-    const size_t nv = (size_t)m->n_verts;
-    int max_joint = -1;
-    for (size_t i = 0; i < 4 * nv; ++i) max_joint = std::max(max_joint, (int)joints4[i]);
-    if ((rc = ensure_front_stream(c))) return rc;
-    if (nv) {
-        // a second call replaces the attributes in place, on the stream the skinning kernels run on (behind those queued so far)
-        if (!m->d_joints) SWR_HIP(c, hipMalloc((void**)&m->d_joints, nv * sizeof(ushort4)));
-        if (!m->d_weights) SWR_HIP(c, hipMalloc((void**)&m->d_weights, nv * sizeof(float4)));
-        const hipStream_t s = use_front_stream(c);
-        SWR_HIP(c, hipMemcpyAsync(m->d_joints, joints4, nv * sizeof(ushort4), hipMemcpyHostToDevice, s));
-        SWR_HIP(c, hipMemcpyAsync(m->d_weights, weights4, nv * sizeof(float4), hipMemcpyHostToDevice, s));
-    }
-    m->max_joint = max_joint; m->has_skin = true;
-    return SWR_OK;
-}
-
-int swr_mesh_skin(swr_context* c, swr_mesh* dst, const swr_mesh* src, const float* palette, int n_joints) {
-    SWR_ENTER(c);
-    int rc;
-    if ((rc = deform_mesh_check(c, dst, "the destination mesh is null"))) return rc;
-    if ((rc = deform_mesh_check(c, src, "the source mesh is null"))) return rc;
-    if (!palette) return fail(c, SWR_ERR_INVALID_ARG, "the palette is null");
-    if (dst == src) return fail(c, SWR_ERR_INVALID_ARG, "the destination mesh is the source (make a target with swr_mesh_create_like)");
-    if (src->n_verts != dst->n_verts) return fail(c, SWR_ERR_INVALID_ARG, "the source and the destination must have equal vertex counts");
-    if (!src->has_skin) return fail(c, SWR_ERR_INVALID_ARG, "the source mesh has no skin attributes (swr_mesh_set_skin)");
-    if (n_joints > 65535) return fail(c, SWR_ERR_UNSUPPORTED, "a palette holds at most 65535 joints (16-bit joint indices)");
-    if (n_joints <= src->max_joint) return fail(c, SWR_ERR_INVALID_ARG, "n_joints must exceed the largest joint index the source's skin attributes use");
-    if (dst->n_verts == 0) return SWR_OK;
-    hipStream_t s = nullptr;
-    if ((rc = deform_begin(c, dst, &s))) return rc;
-    const size_t bytes = (size_t)n_joints * 64;
-    PaletteSlot* slot = nullptr;
-    if ((rc = palette_slot(c, bytes, &slot))) return rc;
-    memcpy(slot->host.p, palette, bytes);
-    SWR_HIP(c, hipMemcpyAsync(slot->dev.p, slot->host.p, bytes, hipMemcpyHostToDevice, s));
-    const dim3 grid(((uint32_t)dst->n_verts + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK), block(SWR_DEFORM_BLOCK);
-    hipLaunchKernelGGL(k_mesh_skin, grid, block, 0, s, (const swr_vertex*)src->d_verts, (const ushort4*)src->d_joints,
-                       (const float4*)src->d_weights, (const float*)slot->dev.p, dst->d_verts, (uint32_t)dst->n_verts, c->nm_flags);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipEventRecord(slot->done, s));
-    slot->busy = true;
-    return deform_end(c, dst, s);
-}
-
-// ---- skeletal animation: clips to palettes on the GPU, one skin launch for a crowd
-namespace {
-int skeleton_check(swr_context* c, const swr_skeleton* k) {
-    if (!k) return fail(c, SWR_ERR_INVALID_ARG, "the skeleton is null");
-    if (k->owner != c) return fail(c, SWR_ERR_INVALID_ARG, "the skeleton belongs to another context");
-    return SWR_OK;
-}
-int pose_set_check(swr_context* c, const swr_pose_set* p) {
-    if (!p) return fail(c, SWR_ERR_INVALID_ARG, "the pose set is null");
-    if (p->owner != c) return fail(c, SWR_ERR_INVALID_ARG, "the pose set belongs to another context");
-    return SWR_OK;
-}
-// behind a write of the set on stream s: what swr_pose_set_readback orders itself by
-int pose_set_written(swr_context* c, swr_pose_set* p, hipStream_t s) {
-    SWR_HIP(c, hipEventRecord(p->written, s));
-    p->written_seen = false;
-    return SWR_OK;
-}
-void destroy_skeleton(swr_skeleton* k) {
-    if (k->d_static) (void)hipFree(k->d_static);
-    if (k->d_clips) (void)hipFree(k->d_clips);
-    delete k;
-}
-void destroy_pose_set(swr_pose_set* p) {
-    if (p->d_palettes) (void)hipFree(p->d_palettes);
-    if (p->d_worlds) (void)hipFree(p->d_worlds);
-    if (p->written) (void)hipEventDestroy(p->written);
-    delete p;
-}
-}  // namespace
-
 int swr_skeleton_create(swr_context* c, int n_nodes, const int32_t* parent, const float* rest_local, const float* rest_t,
                         const float* rest_r, const float* rest_s, int n_joints, const int32_t* joint_node, const float* inverse_bind,
                         swr_skeleton** out) {
-    SWR_ENTER(c);
-    if (!out || !parent || !rest_local || !rest_t || !rest_r || !rest_s) return fail(c, SWR_ERR_INVALID_ARG, "a skeleton array is null");
-    if (n_nodes < 1 || n_joints < 0) return fail(c, SWR_ERR_INVALID_ARG, "a skeleton has at least one node and no negative joint count");
-    if (n_joints > 0 && (!joint_node || !inverse_bind)) return fail(c, SWR_ERR_INVALID_ARG, "joint_node or inverse_bind is null");
-    if (n_nodes > SWR_SKELETON_MAX_NODES || n_joints > 65535) return fail(c, SWR_ERR_UNSUPPORTED, "a skeleton holds at most 65535 nodes and 65535 joints");
-    const size_t nn = (size_t)n_nodes, nj = (size_t)n_joints;
-    std::vector<int32_t> depth(nn), order(nn);
-    int n_levels = 0;
-    for (size_t i = 0; i < nn; ++i) {
-        if (parent[i] < -1 || parent[i] >= (int32_t)i) return fail(c, SWR_ERR_INVALID_ARG, "nodes must be in topological order: parent[i] < i, or -1 for a root");
-        depth[i] = parent[i] < 0 ? 0 : depth[(size_t)parent[i]] + 1;
-        n_levels = std::max(n_levels, depth[i] + 1);
-    }
-    for (size_t j = 0; j < nj; ++j)
-        if (joint_node[j] < 0 || joint_node[j] >= n_nodes) return fail(c, SWR_ERR_INVALID_ARG, "a joint's node index is out of range");
-    // the level table: nodes by depth, in index order within a level (a counting sort)
-    std::vector<int32_t> level_start((size_t)n_levels + 1, 0);
-    for (size_t i = 0; i < nn; ++i) ++level_start[(size_t)depth[i] + 1];
-    for (int l = 0; l < n_levels; ++l) level_start[(size_t)l + 1] += level_start[(size_t)l];
-    { std::vector<int32_t> at(level_start.begin(), level_start.end() - 1); for (size_t i = 0; i < nn; ++i) order[(size_t)at[(size_t)depth[i]]++] = (int32_t)i; }
-    // one blob of 32-bit words, the matrices first (16-byte loads)
-    const size_t o_local = 0, o_ib = o_local + 16 * nn, o_t = o_ib + 16 * nj, o_r = o_t + 3 * nn, o_s = o_r + 4 * nn, o_parent = o_s + 3 * nn,
-                 o_order = o_parent + nn, o_level = o_order + nn, o_joint = o_level + (size_t)n_levels + 1, words = o_joint + nj;
-    std::vector<uint32_t> blob(words);
-    memcpy(&blob[o_local], rest_local, 64 * nn); memcpy(&blob[o_t], rest_t, 12 * nn); memcpy(&blob[o_r], rest_r, 16 * nn);
-    memcpy(&blob[o_s], rest_s, 12 * nn); memcpy(&blob[o_parent], parent, 4 * nn); memcpy(&blob[o_order], order.data(), 4 * nn);
-    memcpy(&blob[o_level], level_start.data(), 4 * ((size_t)n_levels + 1));
-    if (nj) { memcpy(&blob[o_ib], inverse_bind, 64 * nj); memcpy(&blob[o_joint], joint_node, 4 * nj); }
-    swr_skeleton* k = new swr_skeleton();
-    k->owner = c; k->n_nodes = n_nodes; k->n_joints = n_joints; k->n_levels = n_levels;
-    k->clips.assign(1, 0u);
-    hipError_t e = hipMalloc(&k->d_static, words * 4);
-    if (e == hipSuccess) e = hipMemcpy(k->d_static, blob.data(), words * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        destroy_skeleton(k);
-        c->err = std::string("skeleton upload failed: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
-    }
-    *out = k;
-    return SWR_OK;
+    SWR_ENTER(c); return skeleton_create(c, n_nodes, parent, rest_local, rest_t, rest_r, rest_s, n_joints, joint_node, inverse_bind, out);
 }
-
-int swr_skeleton_destroy(swr_context* c, swr_skeleton* k) {
-    SWR_ENTER(c);
-    if (!k) return SWR_OK;
-    int rc = skeleton_check(c, k); if (rc) return rc;
-    destroy_skeleton(k);                       // (hipFree waits for the device: a queued k_pose_sample has read it by then)
-    return SWR_OK;
-}
-
+int swr_skeleton_destroy(swr_context* c, swr_skeleton* k) { SWR_ENTER(c); return skeleton_destroy(c, k); }
 int swr_skeleton_add_clip(swr_context* c, swr_skeleton* k, const swr_anim_channel* channels, int n_channels, int* clip_index) {
-    SWR_ENTER(c);
-    int rc = skeleton_check(c, k); if (rc) return rc;
-    if (!clip_index || n_channels < 0 || (n_channels > 0 && !channels)) return fail(c, SWR_ERR_INVALID_ARG, "channels or clip_index is null, or n_channels is negative");
-    const size_t nn = (size_t)k->n_nodes;
-    size_t words = k->clips.size() + 3 * nn;
-    std::vector<uint8_t> taken(3 * nn, 0);
-    for (int i = 0; i < n_channels; ++i) {
-        const swr_anim_channel& ch = channels[i];
-        if (ch.interpolation == SWR_ANIM_CUBICSPLINE) return fail(c, SWR_ERR_UNSUPPORTED, "CUBICSPLINE interpolation is not supported (STEP and LINEAR are)");
-        if (ch.interpolation != SWR_ANIM_STEP && ch.interpolation != SWR_ANIM_LINEAR) return fail(c, SWR_ERR_INVALID_ARG, "unknown interpolation");
-        if (ch.node < 0 || ch.node >= k->n_nodes) return fail(c, SWR_ERR_INVALID_ARG, "a channel's node index is out of range");
-        if (ch.path < SWR_ANIM_PATH_TRANSLATION || ch.path > SWR_ANIM_PATH_SCALE) return fail(c, SWR_ERR_INVALID_ARG, "a channel's path is none of translation, rotation, scale");
-        if (ch.n_keys < 1) return fail(c, SWR_ERR_INVALID_ARG, "a channel needs at least one key");
-        if (!ch.times || !ch.values) return fail(c, SWR_ERR_INVALID_ARG, "a channel's times or values are null");
-        uint8_t& t = taken[3 * (size_t)ch.node + (size_t)ch.path];
-        if (t) return fail(c, SWR_ERR_INVALID_ARG, "two channels target the same node and path");
-        t = 1;
-        for (int q = 0; q + 1 < ch.n_keys; ++q)
-            if (!(ch.times[q + 1] >= ch.times[q])) return fail(c, SWR_ERR_INVALID_ARG, "key times must not decrease (or be NaN)");
-        words += 2 + (size_t)ch.n_keys * (ch.path == SWR_ANIM_PATH_ROTATION ? 5 : 4);
-    }
-    if (words >= ((size_t)1 << 30)) return fail(c, SWR_ERR_UNSUPPORTED, "the skeleton's clips exceed 2^30 words");
-    // the new blob on the host, then in a new allocation; the old one is freed once the device is idle (a queued k_pose_sample may
-    // read it) -- a load-time call
-    std::vector<uint32_t> blob = k->clips;
-    const uint32_t base = (uint32_t)blob.size();
-    blob.resize(words, 0u);
-    size_t at = base + 3 * nn;
-    for (int i = 0; i < n_channels; ++i) {
-        const swr_anim_channel& ch = channels[i];
-        const size_t comps = ch.path == SWR_ANIM_PATH_ROTATION ? 4 : 3, nk = (size_t)ch.n_keys;
-        blob[base + 3 * (size_t)ch.node + (size_t)ch.path] = (uint32_t)at;
-        blob[at] = (uint32_t)ch.interpolation; blob[at + 1] = (uint32_t)ch.n_keys;
-        memcpy(&blob[at + 2], ch.times, 4 * nk);
-        memcpy(&blob[at + 2 + nk], ch.values, 4 * nk * comps);
-        at += 2 + nk * (1 + comps);
-    }
-    uint32_t* d_new = nullptr;
-    SWR_HIP(c, hipMalloc((void**)&d_new, words * 4));
-    hipError_t e = hipMemcpy(d_new, blob.data(), words * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && k->d_clips) { e = hipDeviceSynchronize(); ++c->host_syncs; }
-    if (e != hipSuccess) { (void)hipFree(d_new); SWR_HIP(c, e); }
-    if (k->d_clips) (void)hipFree(k->d_clips);
-    k->d_clips = d_new;
-    k->clips.swap(blob);
-    *clip_index = (int)k->clip_base.size();
-    k->clip_base.push_back(base);
-    return SWR_OK;
+    SWR_ENTER(c); return skeleton_add_clip(c, k, channels, n_channels, clip_index);
 }
-
-int swr_pose_set_create(swr_context* c, int n_instances, int n_joints, swr_pose_set** out) {
-    SWR_ENTER(c);
-    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "out is null");
-    if (n_instances < 1 || n_joints < 1) return fail(c, SWR_ERR_INVALID_ARG, "a pose set has at least one instance and one joint");
-    if (n_joints > 65535 || (size_t)n_instances * (size_t)n_joints > ((size_t)1 << 24))
-        return fail(c, SWR_ERR_UNSUPPORTED, "a pose set holds at most 65535 joints per instance and 2^24 matrices");
-    swr_pose_set* p = new swr_pose_set();
-    p->owner = c; p->n_instances = n_instances; p->n_joints = n_joints;
-    const size_t bytes = (size_t)n_instances * (size_t)n_joints * 64;
-    hipError_t e = hipMalloc((void**)&p->d_palettes, bytes);
-    if (e == hipSuccess) e = hipMemset(p->d_palettes, 0, bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);          // (the streams of a context do not wait for the null stream)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->written, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        destroy_pose_set(p);
-        c->err = std::string("pose set allocation failed: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
-    }
-    *out = p;
-    return SWR_OK;
-}
-
-int swr_pose_set_destroy(swr_context* c, swr_pose_set* p) {
-    SWR_ENTER(c);
-    if (!p) return SWR_OK;
-    int rc = pose_set_check(c, p); if (rc) return rc;
-    destroy_pose_set(p);                       // (hipFree waits for the device: the kernels queued on the set are over by then)
-    return SWR_OK;
-}
-
-int swr_pose_set_sample(swr_context* c, swr_pose_set* p, const swr_skeleton* k, const swr_pose_request* requests, int n) {
-    SWR_ENTER(c);
-    int rc;
-    if ((rc = pose_set_check(c, p)) || (rc = skeleton_check(c, k))) return rc;
-    if (n < 0 || n > p->n_instances) return fail(c, SWR_ERR_INVALID_ARG, "n must be within 0 .. n_instances");
-    if (n > 0 && !requests) return fail(c, SWR_ERR_INVALID_ARG, "requests is null");
-    if (k->n_joints != p->n_joints) return fail(c, SWR_ERR_INVALID_ARG, "the pose set's joint count is not the skeleton's");
-    const int n_clips = (int)k->clip_base.size();
-    for (int i = 0; i < n; ++i)
-        if (requests[i].clip_a < 0 || requests[i].clip_a >= n_clips || requests[i].clip_b >= n_clips)
-            return fail(c, SWR_ERR_INVALID_ARG, "a request names a clip the skeleton does not have");
-    if (n == 0) return SWR_OK;
-    if ((rc = ensure_front_stream(c))) return rc;
-    if (p->world_nodes < k->n_nodes) {
-        // the node matrices grow to the largest skeleton the set was sampled with (hipFree waits for the device: the first sample, once)
-        if (p->d_worlds) { SWR_HIP(c, hipFree(p->d_worlds)); p->d_worlds = nullptr; p->world_nodes = 0; }
-        SWR_HIP(c, hipMalloc((void**)&p->d_worlds, (size_t)p->n_instances * (size_t)k->n_nodes * 64));
-        p->world_nodes = k->n_nodes;
-    }
-    const hipStream_t s = use_front_stream(c);
-    const size_t bytes = (size_t)n * sizeof(PoseRequestDev);
-    PaletteSlot* slot = nullptr;
-    if ((rc = palette_slot(c, bytes, &slot))) return rc;
-    PoseRequestDev* rq = static_cast<PoseRequestDev*>(slot->host.p);
-    for (int i = 0; i < n; ++i) {
-        const swr_pose_request& r = requests[i];
-        rq[i] = PoseRequestDev{ k->clip_base[(size_t)r.clip_a], r.time_a, r.clip_b < 0 ? SWR_ANIM_NO_CLIP : k->clip_base[(size_t)r.clip_b], r.time_b, r.weight };
-    }
-    SWR_HIP(c, hipMemcpyAsync(slot->dev.p, slot->host.p, bytes, hipMemcpyHostToDevice, s));
-    const size_t nn = (size_t)k->n_nodes, nj = (size_t)k->n_joints;
-    const float* f = static_cast<const float*>(k->d_static);
-    SkeletonDev sk{};
-    sk.rest_local = f; sk.inverse_bind = f + 16 * nn; sk.rest_t = sk.inverse_bind + 16 * nj; sk.rest_r = sk.rest_t + 3 * nn; sk.rest_s = sk.rest_r + 4 * nn;
-    sk.parent = reinterpret_cast<const int32_t*>(sk.rest_s + 3 * nn); sk.order = sk.parent + nn; sk.level_start = sk.order + nn;
-    sk.joint_node = sk.level_start + (size_t)k->n_levels + 1;
-    sk.n_nodes = (uint32_t)k->n_nodes; sk.n_joints = (uint32_t)k->n_joints; sk.n_levels = (uint32_t)k->n_levels;
-    hipLaunchKernelGGL(k_pose_sample, dim3((uint32_t)n), dim3(SWR_POSE_BLOCK), 0, s, sk, (const uint32_t*)k->d_clips,
-                       (const PoseRequestDev*)slot->dev.p, reinterpret_cast<float4*>(p->d_worlds), reinterpret_cast<float4*>(p->d_palettes),
-                       (uint32_t)p->n_joints * 16u);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipEventRecord(slot->done, s));
-    slot->busy = true;
-    return pose_set_written(c, p, s);
-}
-
-int swr_pose_set_upload(swr_context* c, swr_pose_set* p, int first, int n, const float* palettes) {
-    SWR_ENTER(c);
-    int rc = pose_set_check(c, p); if (rc) return rc;
-    if (first < 0 || n < 0 || first > p->n_instances || n > p->n_instances - first) return fail(c, SWR_ERR_INVALID_ARG, "first .. first + n - 1 must be instances of the set");
-    if (n > 0 && !palettes) return fail(c, SWR_ERR_INVALID_ARG, "palettes is null");
-    if (n == 0) return SWR_OK;
-    if ((rc = ensure_front_stream(c))) return rc;
-    const hipStream_t s = use_front_stream(c);
-    const size_t stride = (size_t)p->n_joints * 16, bytes = (size_t)n * stride * 4;
-    PaletteSlot* slot = nullptr;
-    if ((rc = palette_slot(c, bytes, &slot, false))) return rc;
-    memcpy(slot->host.p, palettes, bytes);
-    SWR_HIP(c, hipMemcpyAsync(p->d_palettes + (size_t)first * stride, slot->host.p, bytes, hipMemcpyHostToDevice, s));
-    SWR_HIP(c, hipEventRecord(slot->done, s));
-    slot->busy = true;
-    return pose_set_written(c, p, s);
-}
-
-int swr_pose_set_readback(swr_context* c, const swr_pose_set* set, float* out) {
-    SWR_ENTER(c);
-    int rc = pose_set_check(c, set); if (rc) return rc;
-    if (!out) return fail(c, SWR_ERR_INVALID_ARG, "the destination is null");
-    // a reader on the ray stream, as swr_mesh_readback: behind the set's last write and behind nothing else
-    if ((rc = ensure_ray_stream(c))) return rc;
-    swr_pose_set* p = const_cast<swr_pose_set*>(set);
-    if (!p->written_seen) { SWR_HIP(c, hipStreamWaitEvent(c->ray_stream, p->written, 0)); p->written_seen = true; }
-    SWR_HIP(c, hipMemcpyAsync(out, p->d_palettes, (size_t)p->n_instances * (size_t)p->n_joints * 64, hipMemcpyDeviceToHost, c->ray_stream));
-    SWR_HIP(c, hipStreamSynchronize(c->ray_stream));
-    return SWR_OK;
-}
-
-int swr_mesh_skin_batch(swr_context* c, int n, swr_mesh* const* dst, const swr_mesh* const* src, const swr_pose_set* set, const int32_t* instance) {
-    SWR_ENTER(c);
-    int rc = pose_set_check(c, set); if (rc) return rc;
-    if (n < 0) return fail(c, SWR_ERR_INVALID_ARG, "n is negative");
-    if (n == 0) return SWR_OK;
-    if (!dst || !src || !instance) return fail(c, SWR_ERR_INVALID_ARG, "dst, src or instance is null");
-    std::vector<const swr_mesh*> dsts((size_t)n);
-    uint64_t blocks = 0;
-    for (int k = 0; k < n; ++k) {
-        if ((rc = deform_mesh_check(c, dst[k], "a destination mesh is null"))) return rc;
-        if ((rc = deform_mesh_check(c, src[k], "a source mesh is null"))) return rc;
-        if (src[k]->n_verts != dst[k]->n_verts) return fail(c, SWR_ERR_INVALID_ARG, "a job's source and destination must have equal vertex counts");
-        if (!src[k]->has_skin) return fail(c, SWR_ERR_INVALID_ARG, "a source mesh has no skin attributes (swr_mesh_set_skin)");
-        if (instance[k] < 0 || instance[k] >= set->n_instances) return fail(c, SWR_ERR_INVALID_ARG, "an instance is not one of the pose set's");
-        if (set->n_joints <= src[k]->max_joint) return fail(c, SWR_ERR_INVALID_ARG, "the pose set's n_joints must exceed the largest joint index a source's skin attributes use");
-        dsts[(size_t)k] = dst[k];
-        blocks += ((uint64_t)dst[k]->n_verts + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK;
-    }
-    std::sort(dsts.begin(), dsts.end());
-    if (std::adjacent_find(dsts.begin(), dsts.end()) != dsts.end()) return fail(c, SWR_ERR_INVALID_ARG, "a destination mesh appears twice in the batch");
-    for (int k = 0; k < n; ++k)
-        if (std::binary_search(dsts.begin(), dsts.end(), src[k])) return fail(c, SWR_ERR_INVALID_ARG, "a destination mesh is a job's source (make a target with swr_mesh_create_like)");
-    if (blocks == 0) return SWR_OK;
-    if (blocks > 0x7fffffffull) return fail(c, SWR_ERR_UNSUPPORTED, "the batch exceeds 2^31 blocks of vertices");
-    // deform_begin's rules A and B, once over all destinations
-    const auto reads_a_dst = [&](const std::vector<DrawCmd>& draws) {
-        for (const DrawCmd& d : draws) if (std::binary_search(dsts.begin(), dsts.end(), (const swr_mesh*)d.mesh)) return true;
-        return false;
-    };
-    if (reads_a_dst(c->draws) && (rc = flush_locked(c))) return rc;
-    bool in_flight = false;
-    for (const Batch& b : c->inflight) in_flight = in_flight || reads_a_dst(b.draws);
-    if (in_flight && (rc = sync_locked(c))) return rc;
-    if ((rc = ensure_front_stream(c))) return rc;
-    const hipStream_t s = use_front_stream(c);
-    // the job table: jobs with vertices, by first block
-    PaletteSlot* slot = nullptr;
-    if ((rc = palette_slot(c, (size_t)n * sizeof(SkinJob), &slot))) return rc;
-    SkinJob* jobs = static_cast<SkinJob*>(slot->host.p);
-    uint32_t n_jobs = 0, first_block = 0;
-    for (int k = 0; k < n; ++k) {
-        if (dst[k]->n_verts == 0) continue;
-        jobs[n_jobs++] = SkinJob{ src[k]->d_verts, src[k]->d_joints, src[k]->d_weights, dst[k]->d_verts, (uint32_t)dst[k]->n_verts, first_block,
-                                  (uint32_t)instance[k] * (uint32_t)set->n_joints * 16u, 0u };
-        first_block += ((uint32_t)dst[k]->n_verts + SWR_DEFORM_BLOCK - 1u) / SWR_DEFORM_BLOCK;
-    }
-    SWR_HIP(c, hipMemcpyAsync(slot->dev.p, slot->host.p, (size_t)n_jobs * sizeof(SkinJob), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_mesh_skin_batch, dim3(first_block), dim3(SWR_DEFORM_BLOCK), 0, s, (const SkinJob*)slot->dev.p, n_jobs,
-                       (const float*)set->d_palettes, c->nm_flags);
-    SWR_HIP(c, hipGetLastError());
-    SWR_HIP(c, hipEventRecord(slot->done, s));
-    slot->busy = true;
-    // deform_end for every destination, with ONE event behind the kernel for rule C instead of one per mesh: the destinations share it
-    std::shared_ptr<SharedEvent> ev;
-    for (auto& e : c->pose_events) if (e.use_count() == 1) { ev = e; break; }          // no mesh holds it: its waits were issued long ago
-    if (!ev) {
-        ev = std::make_shared<SharedEvent>();
-        SWR_HIP(c, hipEventCreateWithFlags(&ev->ev, hipEventDisableTiming));
-        c->pose_events.push_back(ev);
-    }
-    SWR_HIP(c, hipEventRecord(ev->ev, s));
-    for (int k = 0; k < n; ++k) {
-        if (dst[k]->n_verts == 0) continue;
-        dst[k]->posed = ev;
-        dst[k]->upload_seen = false;
-        dst[k]->bounds_ready = false;
-        dst[k]->has_box = false;
-    }
-    return SWR_OK;
-}
+int swr_pose_set_create(swr_context* c, int n_instances, int n_joints, swr_pose_set** out) { SWR_ENTER(c); return pose_set_create(c, n_instances, n_joints, out); }
+int swr_pose_set_destroy(swr_context* c, swr_pose_set* p) { SWR_ENTER(c); return pose_set_destroy(c, p); }
+int swr_pose_set_sample(swr_context* c, swr_pose_set* p, const swr_skeleton* k, const swr_pose_request* requests, int n) { SWR_ENTER(c); return pose_set_sample(c, p, k, requests, n); }
+int swr_pose_set_upload(swr_context* c, swr_pose_set* p, int first, int n, const float* palettes) { SWR_ENTER(c); return pose_set_upload(c, p, first, n, palettes); }
+int swr_pose_set_readback(swr_context* c, const swr_pose_set* set, float* out) { SWR_ENTER(c); return pose_set_readback(c, set, out); }
 
 int swr_set_state(swr_context* c, float near_clip, float far_clip, int debug_mode) {
     SWR_ENTER(c);
@@ -1887,7 +981,7 @@ int swr_interpolate(swr_context* c, const float* verts60, const float* w, int n,
     SWR_ENTER(c);
     if (!verts60 || !w || !out || n < 0) return fail(c, SWR_ERR_INVALID_ARG, "bad interpolate arguments");
     if (n == 0) return SWR_OK;
-    const size_t off_w = 256, off_o = 256 + (((size_t)n * 12 + 15) & ~(size_t)15);
+    const size_t off_w = 256, off_o = 256 + query_align((size_t)n * 12);
     int rc = ensure(c, c->d_scratch, off_o + (size_t)n * 96);
     if (rc) return rc;
     char* base = reinterpret_cast<char*>(c->d_scratch.p);

@@ -814,8 +814,7 @@ int make_mesh(swr_context* c, const swr_vertex* v, int nv, const uint16_t* idx, 
     if (e == hipSuccess && !transient) e = hipEventRecord(m->uploaded, use_front_stream(c));
     if (e != hipSuccess) {
         destroy_mesh(m);
-        c->err = std::string("mesh upload failed: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+        return fail_hip(c, "mesh upload failed: ", e);
     }
     *out = m;
     return SWR_OK;

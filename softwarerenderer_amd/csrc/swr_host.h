@@ -1,5 +1,6 @@
 // swr_host.h -- host side of libswr_hip.so: the context and batch types, device buffers, the frame-slot ring, band geometry,
-// timing spans, the front stream, run-time values as kernel template arguments.  Included by swr_api.hip only (the library's one translation unit).
+// timing spans, the front stream, run-time values as kernel template arguments.  Included by swr_api.hip only (the library's one translation
+// unit), in front of swr_rtc.h, swr_flush.h, swr_query.h, swr_texture.h and swr_deform.h.
 #pragma once
 #include <memory>
 #include <type_traits>
@@ -36,7 +37,7 @@ struct swr_mesh {
 struct swr_skeleton {
     swr_context* owner = nullptr;
     int n_nodes = 0, n_joints = 0, n_levels = 0;
-    void* d_static = nullptr;                 // parent | order | level_start | rest_local | rest_t | rest_r | rest_s | joint_node | inverse_bind
+    void* d_static = nullptr;                 // one blob of 32-bit words, laid out by skeleton_layout (swr_animation_layout.h)
     uint32_t* d_clips = nullptr;
     std::vector<uint32_t> clips;              // the clip blob (swr_animation.hip.h), word 0 unused
     std::vector<uint32_t> clip_base;          // word offset of each clip's node table
@@ -305,6 +306,11 @@ namespace {
     } while (0)
 
 int fail(swr_context* c, int code, const char* msg) { c->err = msg; return code; }
+// ... and a HIP error behind `what` ("texture upload failed: "), for the calls that clean up before they report
+int fail_hip(swr_context* c, const char* what, hipError_t e) {
+    c->err = std::string(what) + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? SWR_ERR_OOM : SWR_ERR_HIP;
+}
 
 int ensure(swr_context* c, DevBuf& b, size_t bytes, bool zero_new = false) {
     if (bytes <= b.cap) return SWR_OK;

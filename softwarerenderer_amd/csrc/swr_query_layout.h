@@ -1,5 +1,5 @@
 // swr_query_layout.h -- where the pieces of a ray query and of a character update lie in their device blocks (d_ray, d_char) and in
-// the host block that mirrors them, in bytes, and which host block a call goes through.  No HIP types: pure functions of a call's
+// the host block that mirrors them, in bytes, which host block a call goes through, and where a batched probe's records lie in d_scratch.  No HIP types: pure functions of a call's
 // counts (tests/test_query_layout_host.py builds them with the host compiler).  swr_query.h asserts the two record sizes.
 #pragma once
 #include <cstddef>
@@ -9,6 +9,16 @@ namespace swr {
 constexpr size_t kRayTargetBytes = 152;      // sizeof(RayTarget), swr_raycast.hip.h
 constexpr size_t kCharWorkBytes = 168;       // sizeof(CharWork), swr_character.hip.h
 constexpr size_t query_align(size_t b) { return (b + 15) & ~(size_t)15; }
+// d_scratch of a batched probe (swr_texture.h): n input records at 0, then each output array at the next multiple of 16
+// (out_bytes[1] == 0: one output).  total: what the block must hold.
+struct ProbeLayout { size_t off_out[2], total; };
+inline ProbeLayout probe_layout(int n, size_t in_bytes, size_t out0_bytes, size_t out1_bytes) {
+    const size_t N = (size_t)n;
+    ProbeLayout l;
+    l.off_out[0] = query_align(N * in_bytes); l.off_out[1] = l.off_out[0] + query_align(N * out0_bytes);
+    l.total = out1_bytes ? l.off_out[1] + N * out1_bytes : l.off_out[0] + N * out0_bytes;
+    return l;
+}
 // small queries (a slide attempt: 111 rays x 11 meshes, 4.4 KB each way) go through one pinned block; large ones use pageable memory
 constexpr size_t kQueryStagedBytes = (size_t)1 << 20;
 constexpr bool query_is_staged(size_t up_bytes, size_t down_bytes) { return up_bytes + down_bytes <= kQueryStagedBytes; }
